@@ -10,6 +10,14 @@ One "step" = one ef_process_frame_dev() over one 640x480 synthetic RGB-D frame (
 already resident in HBM.  N > 1: rank r replays its own independent sequence (seed 0xEF0001 + r) on GPU r
 ("replicas only", no data-path collective); RCCL is used once to gather the per-rank stats.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, pre-rolls and warms up, times --steps frames and prints the line.  Everything else it can measure (per-frame
+times and rooflines on the frames behind the timed region, `value_200_steps`, the box calibration, the side legs, the CPU baseline and
+the ATE against it) runs only with --full:
+
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full
+
+--dump-outputs DIR writes what the timed path computed in its last step (pose, surfel map) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -46,6 +54,57 @@ SELF_CHECK = 200    # frames behind the probe frames, timed as ONE more region o
                     # (~12 ms), where +-3 % of run-to-run noise decides every comparison; the longer region of the same run shows it in the record itself
 PREROLL = 100   # untimed frames before --warmup: the map reaches its steady state (stable surfels, model-fed tracker, clean() removing
                # stale unstable surfels) whatever --steps / --warmup the caller chose, so the timed region is the representative workload
+DISTINCT_FRAMES = 512   # at most this many frames are rendered (~0.3 s of host time each); a longer replay runs back and forth over them
+DUMP_BYTES = 64 << 20   # --dump-outputs: the budget of all files together
+
+
+def frame_index(k: int, n_distinct: int) -> int:
+    """frame of the sequence shown at replay step k: 0, 1, .., n_distinct - 1, n_distinct - 2, .., 1, 0, 1, ..  (the camera turns round
+    at either end, so consecutive steps stay one frame's motion apart); the identity while k < n_distinct"""
+    if n_distinct < 2:
+        return 0
+    p = k % (2 * n_distinct - 2)
+    return p if p < n_distinct else 2 * n_distinct - 2 - p
+
+
+def replay_frames(seed: int, n: int, w: int = W, h: int = H, ranks_on_host: int = 1, cache: str | None = None):
+    """the n frames of a replay: the first min(n, DISTINCT_FRAMES) frames of the sequence, then back and forth over them (frame_index).
+    The list holds references, so a frame rendered once is also uploaded once (see upload_frames)."""
+    nd = min(n, DISTINCT_FRAMES)
+    path = f"{cache}.{w}x{h}.{nd}.npz" if cache else None
+    if path and os.path.exists(path):
+        z = np.load(path)
+        distinct = [(z["rgb"][k], z["depth"][k], z["T"][k]) for k in range(nd)]
+    else:
+        distinct = generate_frames(seed, nd, w, h, ranks_on_host)
+        if path:
+            np.savez(path, rgb=np.stack([f[0] for f in distinct]), depth=np.stack([f[1] for f in distinct]), T=np.stack([f[2] for f in distinct]))
+    return [distinct[frame_index(k, nd)] for k in range(n)]
+
+
+def upload_frames(api, frames):
+    """device copies of a replay's frames, one per distinct frame object"""
+    up = {}
+    for r, d, _ in frames:
+        if id(r) not in up:
+            up[id(r)] = (api.DevBuf.from_array(r), api.DevBuf.from_array(d))
+    return [up[id(r)] for r, _, _ in frames]
+
+
+def dump_outputs(ef, out_dir):
+    """What a caller of the timed path holds after its last step: the camera pose and the surfel map (ef_get_pose, ef_map_download).
+    A map above the budget is written as a fixed, seeded sample of its rows (in map order), with the full row count beside it."""
+    os.makedirs(out_dir, exist_ok=True)
+    T = np.asarray(ef.get_T_wc(), np.float64).reshape(4, 4)
+    surfels = np.asarray(ef.downloadMap(), np.float32)
+    n = len(surfels)
+    cap = (DUMP_BYTES - 4096) // surfels[:1].nbytes if n else 0
+    if n > cap:
+        rows = np.sort(np.random.default_rng(0xEF0D).choice(n, cap, replace=False))
+        surfels = surfels[rows]
+    np.save(os.path.join(out_dir, "pose_T_wc.npy"), T)
+    np.save(os.path.join(out_dir, "map_surfels.npy"), np.ascontiguousarray(surfels))
+    np.save(os.path.join(out_dir, "map_count.npy"), np.array([n], np.float64))
 
 
 def generate_frames(seed: int, n: int, w: int = W, h: int = H, ranks_on_host: int = 1):
@@ -428,11 +487,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="besides the headline: per-frame times and rooflines on the frames behind the timed region, "
+                    "value_200_steps, the box calibration, the side legs of the N = 1 line and the CPU baseline (off by default)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the timed path computed in its last step as DIR/<name>.npy "
+                    "(pose_T_wc float64 4x4, map_surfels float32 [n, 12] or a seeded sample of its rows within 64 MB, map_count); rank 0")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--probe-inside", action="store_true", help="development: sample the roofline kernels inside the timed region (1 frame in 8) "
                     "instead of on the frames that follow it")
     ap.add_argument("--frames-cache", default=None, help="development: keep the generated synthetic frames in this .npz between runs "
-                    "(A/B runs of library variants on one GPU box, tools/ab_bench.py); never used by the driver")
+                    "(A/B runs of library variants on one GPU box); never needed for the headline")
     ap.add_argument("--width", type=int, default=W, help="1280 (with --height 960) = BASELINE.json configs[2]; NOT the headline metric")
     ap.add_argument("--height", type=int, default=H)
     ap.add_argument("--host-frames", action="store_true", help="hand the frames over as HOST buffers (ef_process_frame: copy into pinned "
@@ -451,7 +514,7 @@ def main():
     ap.add_argument("--preseed", type=int, default=0, help="SURVEY 8(d) config 3: start from a map of about this many surfels sampled on the "
                     "scene's surfaces (radius 4 mm, confidence 12) brought in with ef_map_upload + ef_restore_state instead of seeding from "
                     "the first frame; with --width 1280 --height 960 --preseed 1048576 = BASELINE.json configs[2], the HBM-bound map")
-    ap.add_argument("--no-side-legs", action="store_true", help="skip the extra keys of the N = 1 line (host-frame path, reference-rounding "
+    ap.add_argument("--no-side-legs", action="store_true", help="with --full: skip the extra keys of the N = 1 line (host-frame path, reference-rounding "
                     "build, closed loop, odometry only, hipGraph replay, configs[4], configs[2])")
     ap.add_argument("--preroll", type=int, default=PREROLL, help="development (PMC passes on a pre-seeded map): untimed frames before the warm-up; "
                     "the driver's command never sets it (100: the map's steady state)")
@@ -475,34 +538,22 @@ def main():
     if world > 1:   # N ranks enqueue ~20 k launches/s each from one host: every rank keeps to its own share of the cores
         multi.pin_rank_to_cores(local_rank, world)
     plain = not (a.stand_in_engine or a.host_frames or a.close_loops or a.graph or a.track_only or a.library or a.preseed or a.per_step_tracker or a.round3_tracker or a.probe_inside or a.fused_step or a.input_overlap or a.preroll != PREROLL)
-    side = world == 1 and plain and (w, h) == (W, H) and not a.no_side_legs   # the extra keys ride on the default N = 1 line only
+    side = a.full and world == 1 and plain and (w, h) == (W, H) and not a.no_side_legs   # the extra keys ride on the default N = 1 line only
+    # the frames behind the timed region: sampled kernels (--full), or nothing but the headline
+    probe = PROBE_FRAMES if a.full and not a.probe_inside else 0
 
     # synthetic frames first: the generator forks worker processes, which must happen before HIP / RCCL are initialised
-    # frame 0 seeds the map (tick 1); pre-roll and warm-up are never timed; the last PROBE_FRAMES frames continue the same replay with
-    # the per-kernel sampling switched on (a sampled launch carries profiling timestamps, which the timed region is kept free of)
-    self_check = SELF_CHECK if (side or (world == 1 and plain and (w, h) == (W, H))) and a.steps < SELF_CHECK else 0
-    n_frames = 1 + a.preroll + a.warmup + a.steps + PROBE_FRAMES + self_check
+    # frame 0 seeds the map (tick 1); pre-roll and warm-up are never timed; with --full the last PROBE_FRAMES frames continue the same replay
+    # with the per-kernel sampling switched on (a sampled launch carries profiling timestamps, which the timed region is kept free of)
+    self_check = SELF_CHECK if a.full and world == 1 and plain and (w, h) == (W, H) and a.steps < SELF_CHECK else 0
+    n_frames = 1 + a.preroll + a.warmup + a.steps + probe + self_check
     seed = multi.sequence_seed(rank)
-    cache = f"{a.frames_cache}.{rank}.{w}x{h}.{n_frames}.npz" if a.frames_cache else None
-    if cache and os.path.exists(cache):
-        z = np.load(cache)
-        frames = [(z["rgb"][k], z["depth"][k], z["T"][k]) for k in range(n_frames)]
-    else:
-        frames = generate_frames(seed, n_frames, w, h, ranks_on_host=world)
-        if cache:
-            np.savez(cache, rgb=np.stack([f[0] for f in frames]), depth=np.stack([f[1] for f in frames]), T=np.stack([f[2] for f in frames]))
+    frames = replay_frames(seed, n_frames, w, h, ranks_on_host=world, cache=f"{a.frames_cache}.{rank}" if a.frames_cache else None)
     big = None
     BIG = dict(w=1280, h=960, preroll=16, warmup=24, steps=60, probe=8, preseed=1 << 20)   # (a long warm-up: the GPU idles for seconds while the host samples the map)
     if side:   # configs[2] for the extra key: 1280x960, ~1 M pre-seeded surfels (fewer frames: the map is mature from the start)
         nb = 1 + BIG["preroll"] + BIG["warmup"] + BIG["steps"] + BIG["probe"]
-        bcache = f"{a.frames_cache}.{rank}.1280x960.{nb}.npz" if a.frames_cache else None
-        if bcache and os.path.exists(bcache):
-            z = np.load(bcache)
-            big = [(z["rgb"][k], z["depth"][k], z["T"][k]) for k in range(nb)]
-        else:
-            big = generate_frames(seed, nb, BIG["w"], BIG["h"])
-            if bcache:
-                np.savez(bcache, rgb=np.stack([f[0] for f in big]), depth=np.stack([f[1] for f in big]), T=np.stack([f[2] for f in big]))
+        big = replay_frames(seed, nb, BIG["w"], BIG["h"], cache=f"{a.frames_cache}.{rank}" if a.frames_cache else None)
 
     import torch
     import torch.distributed as dist
@@ -531,7 +582,7 @@ def main():
         gpu, stats_device = torch.cuda, "cuda"
     ef = make_engine(api, w, h, local_rank, stream, close_loops=a.close_loops, graph=a.graph, per_step=a.per_step_tracker, fused_step=a.fused_step,
                      input_overlap=a.input_overlap, round3=a.round3_tracker)
-    dev = [(api.DevBuf.from_array(r), api.DevBuf.from_array(d)) for r, d, _ in frames]
+    dev = upload_frames(api, frames)
     k0 = 0
     n_pre = 0
     if a.preseed:
@@ -565,22 +616,26 @@ def main():
         dist.barrier()
     gpu.synchronize()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:   # the state the last timed step left behind, before anything else runs on this engine
+        dump_outputs(ef, a.dump_outputs)
     per_frame_ms, rtracker = [], None
-    if a.stand_in_engine:
-        for k in range(first_timed + a.steps, first_timed + a.steps + PROBE_FRAMES):
+    if probe and a.stand_in_engine:
+        for k in range(first_timed + a.steps, first_timed + a.steps + probe):
             step(k)
-    elif not a.probe_inside:   # the same replay goes on: per-frame times, then the sampled kernels (see probe_frames_run)
-        per_frame_ms, rtracker = probe_frames_run(ef, lib, step, first_timed + a.steps, PROBE_FRAMES, torch, w, h)
+    elif probe:   # the same replay goes on: per-frame times, then the sampled kernels (see probe_frames_run)
+        per_frame_ms, rtracker = probe_frames_run(ef, lib, step, first_timed + a.steps, probe, torch, w, h)
 
     # pose error of the timed run against the generating trajectory (sanity, not the parity bar)
     T = ef.get_T_wc()
-    Tgt = frames[first_timed + a.steps - 1 + (0 if a.probe_inside else PROBE_FRAMES)][2]
+    Tgt = frames[first_timed + a.steps - 1 + probe][2]
     err_t = float(np.linalg.norm(T[:3, 3] - Tgt[:3, 3]))
     count = ef.lastCount()
-    stable = int((ef.downloadMap()[:, 3] > ef.getConfidenceThreshold()).sum()) if rank == 0 else 0
-    roofline, roofline_splat = rooflines(lib, ef, w, h, (f"last third of the {PROBE_FRAMES} frames that follow the timed region (same replay, same map; "
-                                                          "launch-per-step script, bit-identical results)"
-                                                         if not a.probe_inside else "sampled frames inside the timed region"))
+    stable = int((ef.downloadMap()[:, 3] > ef.getConfidenceThreshold()).sum()) if rank == 0 and a.full else None
+    roofline = roofline_splat = None
+    if a.full or a.probe_inside:
+        roofline, roofline_splat = rooflines(lib, ef, w, h, (f"last third of the {PROBE_FRAMES} frames that follow the timed region (same replay, same map; "
+                                                              "launch-per-step script, bit-identical results)"
+                                                             if not a.probe_inside else "sampled frames inside the timed region"))
     value_200 = None
     if self_check and not a.stand_in_engine and not a.probe_inside:   # the same replay goes on: one more, longer timed region (never `value`)
         lib.ef_kernel_timing(ef.h, C.c_int(0))
@@ -603,16 +658,17 @@ def main():
     agg = multi.aggregate(allstats)
     t_max, value = agg["t_max"], agg["value"]
     calib = None
-    try:   # box calibration (GPU boxes of the pool differ by 10-20 %): what an empty kernel and a 16 MiB copy cost on THIS box, back to back
-        if a.stand_in_engine:
-            raise RuntimeError("stand-in engine: nothing to calibrate")
-        e_us, s_us = C.c_float(0), C.c_float(0)
-        if lib.ef_dev_calibrate(C.c_void_p(stream), C.byref(e_us), C.byref(s_us)) == 0:
-            calib = {"empty_kernel_us": round(e_us.value, 3), "copy_16MiB_us": round(s_us.value, 3),
-                     "copy_16MiB_GBps": round(2 * 16.777216e6 / (s_us.value * 1e-6) / 1e9, 1) if s_us.value > 0 else None,
-                     "what": "200 back-to-back launches each on the bench's stream, averaged between two events (launch gaps included)"}
-    except Exception as e:
-        calib = {"error": repr(e)}
+    if a.full:
+        try:   # box calibration (GPU boxes of the pool differ by 10-20 %): what an empty kernel and a 16 MiB copy cost on THIS box, back to back
+            if a.stand_in_engine:
+                raise RuntimeError("stand-in engine: nothing to calibrate")
+            e_us, s_us = C.c_float(0), C.c_float(0)
+            if lib.ef_dev_calibrate(C.c_void_p(stream), C.byref(e_us), C.byref(s_us)) == 0:
+                calib = {"empty_kernel_us": round(e_us.value, 3), "copy_16MiB_us": round(s_us.value, 3),
+                         "copy_16MiB_GBps": round(2 * 16.777216e6 / (s_us.value * 1e-6) / 1e9, 1) if s_us.value > 0 else None,
+                         "what": "200 back-to-back launches each on the bench's stream, averaged between two events (launch gaps included)"}
+        except Exception as e:
+            calib = {"error": repr(e)}
     mode = ("HOST frames (pinned staging + PCIe upload timed), " if a.host_frames else "") + \
            ("closeLoops (fern database + global closure + local closure every frame, timeDelta 200), " if a.close_loops else "open loop, ") + \
            ("tracker replayed from a hipGraph, " if a.graph else "") + ("ODOMETRY ONLY in the timed region (no fusion), " if a.track_only else "") + \
@@ -657,10 +713,11 @@ def main():
                            "frames": len(per_frame_ms), "what": "GPU time of single frames (events between frames) right behind the timed region"}
                           if per_frame_ms else None),
     }
-    out["config"]["stable_surfels_end"] = int(stable)
+    out["config"]["stable_surfels_end"] = stable
     gpu_poses = None
     try:
-        gpu_poses, _ = ef.trajectory()
+        if a.full:   # (for the ATE against the CPU baseline)
+            gpu_poses, _ = ef.trajectory()
     except Exception:
         pass
     ef.close()
@@ -695,7 +752,7 @@ def main():
         except Exception as e:
             legs["four_sequences_on_one_gpu_fps"] = {"error": repr(e)}
         try:
-            bdev = [(api.DevBuf.from_array(r), api.DevBuf.from_array(d)) for r, d, _ in big]
+            bdev = upload_frames(api, big)
             leg = side_leg(torch, api, big, bdev, BIG["w"], BIG["h"], local_rank, stream, BIG["steps"], BIG["warmup"], BIG["preroll"],
                            seed=seed, preseed_n=BIG["preseed"], probe_frames=BIG["probe"])
             leg["what"] = ("BASELINE configs[2] as SURVEY 8(d) defines it: 1280x960 stream on a map pre-seeded with ~1 M surfels (ef_map_upload of "
@@ -706,7 +763,7 @@ def main():
             legs["config2_1280x960_1M"] = {"error": repr(e)}
         out["side_legs"] = legs
     faulthandler.cancel_dump_traceback_later()
-    if not a.no_cpu_baseline and world == 1:   # rank 0 at N=1 only (the scaling runs reuse the N=1 figure)
+    if a.full and not a.no_cpu_baseline and world == 1:   # rank 0 at N=1 only (the scaling runs reuse the N=1 figure)
         oracle_poses = []
         out["cpu_baseline"] = cpu_baseline(frames[: min(len(frames), 40)], w=w, h=h, poses_out=oracle_poses)
         # BASELINE.json's metric names "ATE vs reference pose": the CPU leg above ran the reference's restatement over the first frames

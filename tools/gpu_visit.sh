@@ -4,8 +4,8 @@
 #   ab           200-step bench of the default library and of the listed variants on THIS box (same frames): AB_LIBS="- fast nofma_fast"
 #   pytest:<expr>   python -m pytest tests -m gpu -k <expr>
 #   ab2          in-process A/B (tools/ab_bench.py): AB_SPECS="d d@2 fast"
-#   prof         rocprofv3 --kernel-trace --stats of the driver's command (no CPU baseline, no side legs)
-#   bench        the driver's command as the driver runs it (side legs + CPU baseline) -> <tag>_bench_driver_cmd.json
+#   prof         rocprofv3 --kernel-trace --stats of bench.py --full (no CPU baseline, no side legs)
+#   bench        bench.py --full (side legs + CPU baseline) -> <tag>_bench_full.json
 #   pmc          HBM-side traffic: FETCH_SIZE / WRITE_SIZE passes + calibration (tools/pmc_traffic.sh), then tools/pmc_json.py -> profiles/pmc_traffic.json
 #   pmcbig       the same passes on BASELINE configs[2] (tools/pmc_traffic_big.sh) -> <tag>_pmc_traffic_1280x960.json
 #   factorial    tools/parity_factorial.py -> <tag>_parity_factorial.json
@@ -13,6 +13,7 @@
 #   variant:<v>  libefusion_hip_<v>.so beside the default: phase clocks (<v>_clocks), the frame / reference / steady-state parity tests through it
 #   clocks       phase clocks of the persistent tracker (libefusion_hip_clocks.so: python -m elasticfusion_amd.build --variant clocks)
 tag=${1:-run}; shift
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $out
 cd $GRAFT_REPO_ROOT
@@ -29,15 +30,15 @@ for what in "$@"; do
       tail -25 $out/${tag}_gpu_tests_k.log | cut -c1-300 ;;
     ab2)   # in-process A/B (tools/ab_bench.py): AB_SPECS="d d@2 fast"
       timeout 400 python tools/ab_bench.py ${AB_ARGS:-} ${AB_SPECS:-d fast} 2>&1 | grep -v "^$" | tee -a $out/${tag}_ab.log | tail -12 ;;
-    prof)   # rocprofv3 kernel stats of the driver's command (no CPU baseline, no side legs)
+    prof)   # rocprofv3 kernel stats of bench.py --full (no CPU baseline, no side legs)
       cd /tmp
-      timeout 240 rocprofv3 --kernel-trace --stats -d /tmp/prof -o ${tag} --output-format csv -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-side-legs --steps 20 --warmup 5 > $out/${tag}_prof_stdout.log 2>&1
+      timeout 240 rocprofv3 --kernel-trace --stats -d /tmp/prof -o ${tag} --output-format csv -- python "$root"/bench.py --full --no-cpu-baseline --no-side-legs --steps 20 --warmup 5 > $out/${tag}_prof_stdout.log 2>&1
       find /tmp/prof -name "${tag}_kernel_stats.csv" -exec cp {} $out/${tag}_bench_kernel_stats.csv \;
       head -30 $out/${tag}_bench_kernel_stats.csv | cut -c1-160; tail -2 $out/${tag}_prof_stdout.log | cut -c1-600
       cd $GRAFT_REPO_ROOT ;;
     bench)
-      timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/${tag}_bench_driver_cmd.json 2> $out/${tag}_bench_driver_cmd.err; echo "bench (driver's command) rc=$?"
-      cut -c1-700 $out/${tag}_bench_driver_cmd.json; tail -2 $out/${tag}_bench_driver_cmd.err ;;
+      timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/${tag}_bench_full.json 2> $out/${tag}_bench_full.err; echo "bench --full rc=$?"
+      cut -c1-700 $out/${tag}_bench_full.json; tail -2 $out/${tag}_bench_full.err ;;
     pmc)
       bash tools/pmc_traffic.sh ${tag}_pmc 2>&1 | tail -12
       python tools/pmc_json.py ${tag}_pmc --out $out/${tag}_pmc_traffic.json 2>&1 | tail -30 ;;
@@ -71,7 +72,7 @@ print(s['motion_error_against_the_generating_trajectory_m'])" ;;
             +*) lib="--${v#+}" ;;
             *) lib="--library $GRAFT_REPO_ROOT/elasticfusion_amd/libefusion_hip_$v.so" ;;
           esac
-          timeout 300 python bench.py --no-cpu-baseline --no-side-legs --steps 200 --warmup 20 --frames-cache /tmp/efframes $lib 2>/dev/null | python -c "
+          timeout 300 python bench.py --full --no-cpu-baseline --no-side-legs --steps 200 --warmup 20 --frames-cache /tmp/efframes $lib 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print('[$v]', d['value'], 'fps', d['ms_per_step'], 'ms', d.get('frame_time_ms'))" | tee -a $out/${tag}_ab.log

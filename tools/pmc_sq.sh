@@ -3,11 +3,12 @@
 # WAIT_ANY (parked: s_waitcnt / barrier / s_sleep), WAIT_INST_ANY (issue stall), ACTIVE_INST_VALU / _LDS, and the LDS bank conflicts.
 # usage (GPU box, repo root): bash tools/pmc_sq.sh <tag> [bench.py arguments]
 tag=${1:-sq}; shift
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pmc_sq
 timeout 240 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT \
-  -d /tmp/pmc_sq -o p --output-format csv -- python $GRAFT_REPO_ROOT/bench.py --steps 12 --warmup 3 --no-cpu-baseline --no-side-legs "$@" > $out/${tag}_sq_stdout.log 2>&1
+  -d /tmp/pmc_sq -o p --output-format csv -- python "$root"/bench.py --full --steps 12 --warmup 3 --no-cpu-baseline --no-side-legs "$@" > $out/${tag}_sq_stdout.log 2>&1
 f=$(find /tmp/pmc_sq -name "p_counter_collection.csv" | head -1)
 python - "$f" > $out/${tag}_sq_per_kernel.csv <<'PY'
 import csv, sys, collections, re

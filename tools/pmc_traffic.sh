@@ -4,6 +4,7 @@
 # usage (GPU box, repo root): bash tools/pmc_traffic.sh <tag> [extra bench.py arguments, e.g. --per-step-tracker: the launch-per-step script,
 # in which the level-0 normal equations are a launch of their own (k_se3_accum_fast); without it the tracker is k_track_fast]
 tag=${1:-pmc}
+root=$(cd "$(dirname "$0")/.." && pwd)
 shift
 extra="$@"
 out=$GRAFT_REPO_ROOT/gpurun_out
@@ -12,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp
 for ctr in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmc_$ctr
   timeout 200 rocprofv3 --kernel-trace --pmc $ctr -d /tmp/pmc_$ctr -o p --output-format csv -- \
-      python $GRAFT_REPO_ROOT/bench.py --steps 12 --warmup 3 --no-cpu-baseline --no-side-legs --frames-cache /tmp/efframes_pmc $extra > $out/${tag}_${ctr}_stdout.log 2>&1
+      python "$root"/bench.py --full --steps 12 --warmup 3 --no-cpu-baseline --no-side-legs --frames-cache /tmp/efframes_pmc $extra > $out/${tag}_${ctr}_stdout.log 2>&1
   f=$(find /tmp/pmc_$ctr -name "p_counter_collection.csv" | head -1)
   echo "$ctr -> $f"
   python - "$f" "$ctr" > $out/${tag}_${ctr}_per_kernel.csv <<'PY'

@@ -4,13 +4,14 @@
 # tools/pmc_traffic.sh (FETCH_SIZE counts half the bytes on gfx950: 2047.3 B per counted KB; WRITE_SIZE 1024).
 # usage (GPU box, repo root): bash tools/pmc_traffic_big.sh <tag>
 tag=${1:-pmcbig}
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 for ctr in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmcb_$ctr
   timeout 150 rocprofv3 --kernel-trace --pmc $ctr -d /tmp/pmcb_$ctr -o p --output-format csv -- \
-      python $GRAFT_REPO_ROOT/bench.py --width 1280 --height 960 --preseed 1048576 --preroll 10 --steps 8 --warmup 2 --no-cpu-baseline --no-side-legs --frames-cache /tmp/efframes_pmcb > $out/${tag}_${ctr}_stdout.log 2>&1
+      python "$root"/bench.py --full --width 1280 --height 960 --preseed 1048576 --preroll 10 --steps 8 --warmup 2 --no-cpu-baseline --no-side-legs --frames-cache /tmp/efframes_pmcb > $out/${tag}_${ctr}_stdout.log 2>&1
   f=$(find /tmp/pmcb_$ctr -name "p_counter_collection.csv" | head -1)
   python - "$f" "$ctr" > $out/${tag}_${ctr}_per_kernel.csv <<'PY'
 import csv, sys, collections
