@@ -46,6 +46,12 @@ class ef_timing(C.Structure):
     _fields_ = [("name", C.c_char_p), ("ms", c_f)]
 
 
+class ef_render_params(C.Structure):
+    _fields_ = [("width", c_i), ("height", c_i), ("fx", c_f), ("fy", c_f), ("cx", c_f), ("cy", c_f), ("T_wc", C.c_double * 16),
+                ("max_depth", c_f), ("threshold", c_f), ("draw_unstable", c_i), ("color_type", c_i), ("draw_window", c_i),
+                ("time", c_i), ("time_delta", c_i)]
+
+
 DATATERM = np.dtype([("zero", np.int16, 2), ("one", np.int16, 2), ("diff", np.float32), ("valid", np.uint8),
                      ("pad", np.uint8, 3)])
 
@@ -721,6 +727,58 @@ class ElasticFusion:
         got = c_u32(0)
         _chk(lib().ef_map_download(self.h, _ptr(out), c_u32(n), C.byref(got)), self.h)
         return out[:got.value].copy()
+
+    # --- GlobalModel::renderPointCloud without OpenGL (ef_render_model) ---
+    RENDER_OUTPUTS = dict(rgba=(np.uint8, 4), depth=(np.float32, 1), vertex=(np.float32, 4), normal=(np.float32, 4), index=(np.uint32, 1))
+
+    def renderParams(self, T_wc=None, width=None, height=None, fx=None, fy=None, cx=None, cy=None, threshold=None, drawUnstable=False,
+                     drawNormals=False, drawColors=False, drawWindow=False, drawTimes=False, time=None, timeDelta=None,
+                     maxDepth=1000.0) -> ef_render_params:
+        """ef_render_params: None = the context's default (ef_default_render_params: frame camera, current pose, getConfidenceThreshold(),
+        getTick(), getTimeDelta()); the colour type is the reference's drawNormals ? 1 : drawColors ? 2 : drawTimes ? 3 : 0"""
+        p = ef_render_params()
+        _chk(lib().ef_default_render_params(self.h, C.byref(p)), self.h)
+        if T_wc is not None:
+            p.T_wc[:] = [float(v) for v in np.asarray(T_wc, np.float64).reshape(16)]
+        for name, v in (("width", width), ("height", height)):
+            if v is not None:
+                setattr(p, name, int(v))
+        for name, v in (("fx", fx), ("fy", fy), ("cx", cx), ("cy", cy), ("threshold", threshold)):
+            if v is not None:
+                setattr(p, name, float(v))
+        if time is not None:
+            p.time = int(time)
+        if timeDelta is not None:
+            p.time_delta = int(timeDelta)
+        p.max_depth = float(maxDepth)
+        p.draw_unstable = int(bool(drawUnstable))
+        p.color_type = 1 if drawNormals else 2 if drawColors else 3 if drawTimes else 0
+        p.draw_window = int(bool(drawWindow))
+        return p
+
+    def renderPointCloud(self, T_wc=None, width=None, height=None, fx=None, fy=None, cx=None, cy=None, threshold=None,
+                         drawUnstable=False, drawNormals=False, drawColors=False, drawWindow=False, drawTimes=False, time=None,
+                         timeDelta=None, maxDepth=1000.0, outputs=("rgba",)) -> dict:
+        """GlobalModel::renderPointCloud (GlobalModel.cpp:286-350) into host images: the current map seen from the pinhole camera
+        {width, height, fx, fy, cx, cy} at T_wc (world <- camera).  outputs: any of rgba (H x W x 4 u8), depth (H x W f32), vertex /
+        normal (H x W x 4 f32, camera frame, w = confidence / radius), index (H x W u32, row of downloadMap(); 0xFFFFFFFF = nothing)."""
+        p = self.renderParams(T_wc, width, height, fx, fy, cx, cy, threshold, drawUnstable, drawNormals, drawColors, drawWindow, drawTimes,
+                              time, timeDelta, maxDepth)
+        unknown = [o for o in outputs if o not in self.RENDER_OUTPUTS]
+        if unknown:
+            raise ValueError(f"unknown render outputs {unknown}")
+        res = {}
+        for o in outputs:
+            dt, ch = self.RENDER_OUTPUTS[o]
+            res[o] = np.zeros((max(p.height, 0), max(p.width, 0)) + ((ch,) if ch > 1 else ()), dt)
+        args = [_ptr(res[o]) if o in res else None for o in ("rgba", "depth", "vertex", "normal", "index")]
+        _chk(lib().ef_render_model(self.h, C.byref(p), *args), self.h)
+        return res
+
+    def renderPointCloudDevice(self, params: ef_render_params, rgba=None, depth=None, vertex=None, normal=None, index=None):
+        """ef_render_model_dev: raw device pointers (int, c_void_p or None), enqueued on the context's stream without synchronising"""
+        args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (rgba, depth, vertex, normal, index)]
+        _chk(lib().ef_render_model_dev(self.h, C.byref(params), *args), self.h)
 
     def setReferenceDownload(self, on=True):
         """downloadMap / savePly read what GlobalModel::downloadMap reads (the pre-clean buffer, quirk Q14) instead of model()"""

@@ -5,6 +5,7 @@
 // host<->device round trips (the reference has ~70 blocking ones).
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <cmath>
 #include <stdio.h>
 #include <string.h>
 #include <limits>
@@ -190,6 +191,12 @@ struct ef_ctx {
   std::vector<hipEvent_t> ka_start, ka_stop;   // the persistent tracker launch (fast order)
   eft::KernelProbe probe_all{nullptr, nullptr, 0, 0};
   hipStream_t debug_stream = nullptr;          // ef_debug_occupy
+  // ef_render_model: its own z-buffer (never the frame's) and, for host-pointer renders, a device landing area for the requested outputs;
+  // both allocated on first use, grown on demand, freed by ef_destroy
+  unsigned long long* render_zbuf = nullptr;
+  size_t render_zbuf_n = 0;
+  uint8_t* render_out = nullptr;
+  size_t render_out_bytes = 0;
 };
 
 namespace {
@@ -1142,6 +1149,8 @@ void ctx_free(ef_ctx* c) {
   for (auto e : c->ka_stop) (void)hipEventDestroy(e);
   for (auto e : c->ks_start) (void)hipEventDestroy(e);
   for (auto e : c->ks_stop) (void)hipEventDestroy(e);
+  if (c->render_zbuf) (void)hipFree(c->render_zbuf);
+  if (c->render_out) (void)hipFree(c->render_out);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
 }
 
@@ -2557,6 +2566,115 @@ int ef_op_clean(const ef_cam* cam, const double* T16, int time, const uint32_t* 
                 uint32_t newCount, float* surfels_out, uint32_t* outCount, void* s_) {
   return ef_op_clean_deform(cam, T16, time, index, vc, ct, nr, confThreshold, timeDelta, maxDepth, surfels, count, newUnstable, newCount,
                             nullptr, 0, nullptr, 0, surfels_out, outCount, s_);
+}
+
+}  // extern "C"
+
+// ================================================================================================
+// GlobalModel::renderPointCloud without OpenGL (include/ef_hip.h; kernels in ef_render.inc)
+// ================================================================================================
+namespace {
+// the parameters are checked before the context: with a NULL context the message goes where ef_last_error(NULL) finds it
+int render_check(ef_ctx* c, const ef_render_params* p, const char* fn) {
+  std::string& err = c ? c->err : g_create_error;
+  const char* why = nullptr;
+  if (!p) why = "null params";
+  else if (p->width < 1 || p->width > 4096 || p->height < 1 || p->height > 4096) why = "width and height must lie in 1 .. 4096";
+  else if (p->color_type < 0 || p->color_type > 3) why = "color_type must be 0 .. 3";
+  else if (!std::isfinite(p->fx) || !std::isfinite(p->fy) || !std::isfinite(p->cx) || !std::isfinite(p->cy) || p->fx == 0.f || p->fy == 0.f)
+    why = "intrinsics must be finite with non-zero focal lengths";
+  else if (!c) why = "null context";
+  if (!why) return EF_OK;
+  err = std::string(fn) + ": " + why;
+  return EF_EINVAL;
+}
+// the render's z-buffer: grown to P keys, 0xFF bytes (ZBUF_EMPTY) once; every resolve leaves it so
+int render_zbuf(ef_ctx* c, size_t P) {
+  if (c->render_zbuf_n >= P) return EF_OK;
+  EF_HIP(c, hipStreamSynchronize(c->stream));   // (a render still queued may use the old one)
+  if (c->render_zbuf) { (void)hipFree(c->render_zbuf); c->render_zbuf = nullptr; c->render_zbuf_n = 0; }
+  hipError_t e = hipMalloc((void**)&c->render_zbuf, P * sizeof(unsigned long long));
+  if (e != hipSuccess) { c->render_zbuf = nullptr; c->err = std::string("hipMalloc (render z-buffer): ") + hipGetErrorString(e); return EF_ENOMEM; }
+  c->render_zbuf_n = P;
+  EF_HIP(c, hipMemsetAsync(c->render_zbuf, 0xFF, P * sizeof(unsigned long long), c->stream));
+  return EF_OK;
+}
+int render_enqueue(ef_ctx* c, const ef_render_params* p, const efm::RenderOut& out) {
+  {
+    // never inside a capture: a render recorded into a graph would be replayed with every frame
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    EF_HIP(c, hipStreamIsCapturing(c->stream, &cs));
+    if (cs != hipStreamCaptureStatusNone) { c->err = "ef_render_model: the context's stream is being captured"; return EF_ESTATE; }
+  }
+  const size_t P = (size_t)p->width * p->height;
+  const int r = render_zbuf(c, P);
+  if (r != EF_OK) return r;
+  efm::RenderArgs a{};
+  a.cam = efm::Cam{p->width, p->height, p->fx, p->fy, p->cx, p->cy};
+  float pose_f[16];
+  pose_mats(p->T_wc, a.Tcw, pose_f);
+  a.maxDepth = p->max_depth;
+  a.threshold = p->threshold;
+  a.drawUnstable = p->draw_unstable != 0;
+  a.colorType = p->color_type;
+  a.drawWindow = p->draw_window != 0;
+  a.time = p->time;
+  a.timeDelta = p->time_delta;
+  efm::render_model(a, c->maps[c->cur], &c->st->map_counts[c->cur], c->render_zbuf, out, c->stream);
+  EF_HIP(c, hipGetLastError());
+  return EF_OK;
+}
+}  // namespace
+extern "C" {
+
+int ef_default_render_params(ef_ctx* c, ef_render_params* p) {
+  if (!c) return EF_EINVAL;
+  if (!p) { c->err = "ef_default_render_params: null params"; return EF_EINVAL; }
+  memset(p, 0, sizeof(*p));
+  const int r = ef_get_pose(c, p->T_wc);
+  if (r != EF_OK) return r;
+  p->width = c->cam.cols; p->height = c->cam.rows;
+  p->fx = c->cam.fx; p->fy = c->cam.fy; p->cx = c->cam.cx; p->cy = c->cam.cy;
+  p->max_depth = 1000.0f;   // the GUI's far plane
+  p->threshold = c->cfg.confidence;
+  p->time = c->tick;
+  p->time_delta = c->cfg.time_delta;
+  return EF_OK;
+}
+int ef_render_model_dev(ef_ctx* c, const ef_render_params* p, uint8_t* rgba, float* depth, float* vertex, float* normal, uint32_t* index) {
+  const int r = render_check(c, p, "ef_render_model_dev");
+  if (r != EF_OK) return r;
+  DeviceGuard dg_(c);
+  return render_enqueue(c, p, efm::RenderOut{(uchar4*)rgba, depth, (float4*)vertex, (float4*)normal, index});
+}
+int ef_render_model(ef_ctx* c, const ef_render_params* p, uint8_t* rgba, float* depth, float* vertex, float* normal, uint32_t* index) {
+  int r = render_check(c, p, "ef_render_model");
+  if (r != EF_OK) return r;
+  DeviceGuard dg_(c);
+  const size_t P = (size_t)p->width * p->height;
+  // the requested outputs land in one device area (grown on demand), then are copied out
+  const size_t sz[5] = {rgba ? P * 4 : 0, depth ? P * 4 : 0, vertex ? P * 16 : 0, normal ? P * 16 : 0, index ? P * 4 : 0};
+  const size_t bytes = sz[0] + sz[1] + sz[2] + sz[3] + sz[4];
+  if (bytes > c->render_out_bytes) {
+    EF_HIP(c, hipStreamSynchronize(c->stream));
+    if (c->render_out) { (void)hipFree(c->render_out); c->render_out = nullptr; c->render_out_bytes = 0; }
+    hipError_t e = hipMalloc((void**)&c->render_out, bytes);
+    if (e != hipSuccess) { c->render_out = nullptr; c->err = std::string("hipMalloc (render outputs): ") + hipGetErrorString(e); return EF_ENOMEM; }
+    c->render_out_bytes = bytes;
+  }
+  void* host[5] = {rgba, depth, vertex, normal, index};
+  void* dev[5] = {};
+  size_t off = 0;
+  for (int i = 0; i < 5; ++i) {
+    if (sz[i]) dev[i] = c->render_out + off;
+    off += sz[i];
+  }
+  r = render_enqueue(c, p, efm::RenderOut{(uchar4*)dev[0], (float*)dev[1], (float4*)dev[2], (float4*)dev[3], (uint32_t*)dev[4]});
+  if (r != EF_OK) return r;
+  for (int i = 0; i < 5; ++i)
+    if (sz[i]) EF_HIP(c, hipMemcpyAsync(host[i], dev[i], sz[i], hipMemcpyDeviceToHost, c->stream));
+  EF_HIP(c, hipStreamSynchronize(c->stream));
+  return EF_OK;
 }
 
 }  // extern "C"

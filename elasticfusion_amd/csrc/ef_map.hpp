@@ -156,4 +156,21 @@ void sample_graph(SurfelSoA map, const unsigned* count_dev, int stride, int max_
 // candidates -> AoS "newUnstable" list in draw order (operator tier / tests)
 void candidates_to_aos(Candidates cand, float* aos, unsigned* count_dev, const CompactScratch& cs, hipStream_t s);
 
+// ---- GlobalModel::renderPointCloud, headless (ef_render.inc; ef_render_model of include/ef_hip.h) ----
+struct RenderArgs {
+  Cam cam;
+  float Tcw[16];   // float T_wc^-1, row-major (pose_mats)
+  float maxDepth, threshold;
+  int drawUnstable, colorType, drawWindow, time, timeDelta;
+};
+struct RenderOut {   // row-major images; a null pointer is not written
+  uchar4* rgba;
+  float* depth;
+  float4* vertex;
+  float4* normal;
+  uint32_t* index;
+};
+// zbuf: cols x rows keys, all ZBUF_EMPTY on entry and on return
+void render_model(const RenderArgs& a, SurfelSoA map, const unsigned* count_dev, unsigned long long* zbuf, RenderOut out, hipStream_t s);
+
 }  // namespace efm

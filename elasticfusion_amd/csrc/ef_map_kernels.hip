@@ -1491,4 +1491,6 @@ void sample_graph(SurfelSoA map, const unsigned* count_dev, int stride, int max_
   hipLaunchKernelGGL(k_sample_graph, dim3(ceil_div(max_nodes, 256)), dim3(256), 0, s, map, count_dev, stride, max_nodes, (float4*)out4, n_out);
 }
 
+#include "ef_render.inc"
+
 }  // namespace efm

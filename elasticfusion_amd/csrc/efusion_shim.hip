@@ -285,6 +285,27 @@ std::vector<float> GlobalModelView::downloadMap() {
   m.resize((size_t)n * 12);
   return m;
 }
+void GlobalModelView::renderPointCloudImage(const Camera& camera, const SE3d& T_wc, float threshold, bool drawUnstable, bool drawNormals,
+                                            bool drawColors, bool drawWindow, bool drawTimes, int time, int timeDelta,
+                                            std::vector<uint8_t>& rgba, float maxDepth) {
+  ef_render_params p;
+  chk(ef_default_render_params(C(ctx), &p), ctx, "renderPointCloudImage");
+  p.width = camera.width; p.height = camera.height;
+  p.fx = camera.fx; p.fy = camera.fy; p.cx = camera.cx; p.cy = camera.cy;
+  T_wc.matrix(p.T_wc);
+  p.max_depth = maxDepth;
+  p.threshold = threshold;
+  p.draw_unstable = drawUnstable;
+  p.color_type = drawNormals ? 1 : drawColors ? 2 : drawTimes ? 3 : 0;   // GlobalModel.cpp:304
+  p.draw_window = drawWindow;
+  p.time = time;
+  p.time_delta = timeDelta;
+  if (camera.width < 1 || camera.height < 1 || camera.width > 4096 || camera.height > 4096) {
+    chk(ef_render_model(C(ctx), &p, nullptr, nullptr, nullptr, nullptr, nullptr), ctx, "renderPointCloudImage");   // the library's EF_EINVAL
+  }
+  rgba.resize((size_t)camera.width * camera.height * 4);
+  chk(ef_render_model(C(ctx), &p, rgba.data(), nullptr, nullptr, nullptr, nullptr), ctx, "renderPointCloudImage");
+}
 
 std::vector<uint8_t> IndexMapView::image() {
   std::vector<uint8_t> v((size_t)w * h * 4);

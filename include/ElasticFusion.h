@@ -178,6 +178,27 @@ class GlobalModelView {
   unsigned int lastCount();                 // GlobalModel::lastCount()
   // GlobalModel::downloadMap(): count x 12 floats {x,y,z,conf} {colour,0,initTime,lastTime} {nx,ny,nz,radius}
   std::vector<float> downloadMap();
+  // GlobalModel::renderPointCloud (GlobalModel.h:46-56) without OpenGL: the map as it stands (model(), whatever setReferenceDownload says)
+  // drawn on the device into a W*H*4 u8 RGBA image, row major, alpha 255 where a surfel is drawn and 0 elsewhere (ef_render_model).
+  // After the camera and the pose the arguments are the reference's: the GL MVP becomes a pinhole camera + pose (world <- camera) and
+  // drawPoints (the point program) is not provided.  time / timeDelta are the reference's getTick() / getTimeDelta(); maxDepth culls
+  // surfels farther than that from the camera (the GUI's far plane).  The name differs on purpose: the reference's GL draw call (mvp,
+  // drawPoints, the current framebuffer) stays one of the lines a front end has to change, and it reads "no member named
+  // renderPointCloud" instead of an overload that almost matches.
+  struct Camera { int width = 640, height = 480; float fx = 420.f, fy = 420.f, cx = 320.f, cy = 240.f; };
+  void renderPointCloudImage(const Camera& camera, const SE3d& T_wc, float threshold, bool drawUnstable, bool drawNormals, bool drawColors,
+                        bool drawWindow, bool drawTimes, int time, int timeDelta, std::vector<uint8_t>& rgba, float maxDepth = 1000.f);
+#ifdef EFUSION_USE_SOPHUS
+  void renderPointCloudImage(const Camera& camera, const Sophus::SE3d& T_wc, float threshold, bool drawUnstable, bool drawNormals,
+                        bool drawColors, bool drawWindow, bool drawTimes, int time, int timeDelta, std::vector<uint8_t>& rgba,
+                        float maxDepth = 1000.f) {
+    const auto R = T_wc.rotationMatrix();
+    const auto& t = T_wc.translation();
+    const double M[16] = {R(0, 0), R(0, 1), R(0, 2), t(0), R(1, 0), R(1, 1), R(1, 2), t(1), R(2, 0), R(2, 1), R(2, 2), t(2), 0, 0, 0, 1};
+    renderPointCloudImage(camera, SE3d::fromMatrix(M), threshold, drawUnstable, drawNormals, drawColors, drawWindow, drawTimes, time,
+                          timeDelta, rgba, maxDepth);
+  }
+#endif
  private:
   friend class ::efusion::ElasticFusion;
   void* ctx = nullptr;

@@ -369,6 +369,43 @@ int ef_set_frame_to_frame_rgb(ef_ctx*, int v);
 int ef_set_confidence_threshold(ef_ctx*, float v);
 int ef_set_depth_cutoff(ef_ctx*, float v);
 
+/* ---- GlobalModel::renderPointCloud (GlobalModel.cpp:286-350) without OpenGL: the current map, the buffer ef_map_download reads with the
+ * reference download off, drawn on the device from any pinhole camera and pose into plain row-major images.  A surfel is drawn when
+ * conf > threshold || draw_unstable (draw_global_surface.vert:44) and 0 <= z_cam <= max_depth; there is no time-window cull.  Its footprint
+ * and its ray / disc intersection are the model prediction's (ef_op_combined_predict), with this camera.  Nearest wins, ties go to the lower
+ * surfel row; an unstable surfel drawn under draw_unstable competes at z + radius (its outputs still carry the real z).  RGBA is shaded per
+ * surfel as draw_global_surface.geom:49-79 does: with s = |n.x + n.y + n.z| of the stored normal n, color_type 0 (lit) 0.5 s + 0.1,
+ * 1 (normals) n, 2 (colours) the surfel's colour, 3 (times) the init-time ramp times s + 0.1; with draw_window a surfel whose last time
+ * lies more than time_delta before `time` is dimmed to a quarter; each channel roundf(clamp(c, 0, 1) * 255), alpha 255.
+ * Outputs (any may be NULL: not written), width x height each:
+ *   rgba u8 x 4 (0 where nothing is drawn)         depth  f32 (camera z; 0)
+ *   vertex f32 x 4 camera frame, w = confidence     normal f32 x 4 camera frame, w = radius
+ *   index u32: the surfel's row in ef_map_download (0xFFFFFFFF where nothing is drawn)
+ * Work is enqueued on the context's stream behind the frames before it; it changes nothing a frame reads. */
+typedef struct ef_render_params {
+  int width, height;          /* 1 .. 4096 each */
+  float fx, fy, cx, cy;
+  double T_wc[16];            /* world <- camera, row-major, as ef_get_pose returns it */
+  float max_depth;            /* far cull in metres (the GUI's far plane, 1000, by default) */
+  float threshold;            /* getConfidenceThreshold() by default */
+  int draw_unstable;          /* drawUnstable */
+  int color_type;             /* 0 lit, 1 normals, 2 colours, 3 times: drawNormals ? 1 : drawColors ? 2 : drawTimes ? 3 : 0 */
+  int draw_window;            /* drawWindow */
+  int time;                   /* getTick() by default */
+  int time_delta;             /* getTimeDelta() by default */
+} ef_render_params;
+/* the frame camera, the current pose (synchronises), the context's confidence threshold, tick and time delta, max_depth 1000, colour
+ * type 0, both switches off */
+int ef_default_render_params(ef_ctx* ctx, ef_render_params* params);
+/* HOST output pointers; synchronises.  EF_EINVAL for a NULL params, a size outside 1 .. 4096, a colour type outside 0 .. 3,
+ * non-finite intrinsics or a NULL context, before anything is read or enqueued (the parameters are checked first; with a NULL context
+ * ef_last_error(NULL) has the message). */
+int ef_render_model(ef_ctx* ctx, const ef_render_params* params, uint8_t* rgba, float* depth, float* vertex, float* normal,
+                    uint32_t* index);
+/* the same with DEVICE output pointers: enqueued on the context's stream, no synchronisation (as ef_process_frame_dev) */
+int ef_render_model_dev(ef_ctx* ctx, const ef_render_params* params, uint8_t* rgba_dev, float* depth_dev, float* vertex_dev,
+                        float* normal_dev, uint32_t* index_dev);
+
 /* named internal images, copied to HOST (synchronises); for tests and for a front-end's drawing code */
 enum ef_image {
   EF_IMG_DEPTH_FILTERED = 0,      /* u16  */

@@ -7,13 +7,21 @@
 //   efusion_replay -l seq.klg [-w 640 -h 480] [-cal fx fy cx cy] [-d depthCut] [-c confidence] [-t timeDelta]
 //                  [-fo] [-nso] [-ftf] [-i icpWeight] [-e endFrame] [-ply] [-dev N] [-q]
 //                  [-cl [-ic icpCountThresh] [-ie icpErrThresh] [-cv covThresh] [-pt photoThresh] [-ft fernThresh] [-rl]] [-icl] [-f]
+//                  [-render DIR [-render-every N] [-render-cam w h fx fy cx cy] [-render-mode lit|normals|colors|times] [-render-unstable]
+//                   [-render-window]]
 //
 // The flags and their defaults are MainController's (MainController.cpp:69-104: -c 10, -d 3, -i 10, -ie 4e-05, -cv 1e-05, -pt 115,
 // -ft 0.3095, -t 200, -ic 40000; -rl relocalisation, -icl the ICL-NUIM conventions, -f flipped colours, -fo, -nso, -ftf, -e, -q) with one
 // difference: open loop (the reference's -o) is the default here and -cl selects the closed loop (fern database, global and local
 // closures, built-in optimiser).  Like the reference's run loop, the last frame of a log is not processed (RawLogReader::hasMore, see
 // include/efusion_klg.hpp); -all processes every frame.
+//
+// -render DIR writes what the GUI's global-model view shows (MainController.cpp:353-363: GlobalModel::renderPointCloud from the camera,
+// with getConfidenceThreshold(), getTick(), getTimeDelta()), here from the current pose, as binary PPMs DIR/render_NNNNNN.ppm after every
+// N-th processed frame (NNNNNN = the frame's index from 0; frames 0, N, 2N, ...).  The camera defaults to the GUI's (640x480, fx = fy = 420,
+// Tools/GUI.h:73); surfels not drawn are black.  Without -render nothing is drawn and the outputs are those of a run without it.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -26,6 +34,18 @@
 
 using efusion::KlgReader;
 
+// binary PPM (P6) of the RGB channels of a row-major RGBA image
+static void write_ppm(const std::string& path, int w, int h, const std::vector<uint8_t>& rgba) {
+  FILE* f = std::fopen(path.c_str(), "wb");
+  if (!f) throw std::runtime_error("cannot write " + path);
+  std::fprintf(f, "P6\n%d %d\n255\n", w, h);
+  std::vector<uint8_t> rgb((size_t)w * h * 3);
+  for (size_t i = 0; i < (size_t)w * h; ++i)
+    for (int k = 0; k < 3; ++k) rgb[i * 3 + k] = rgba[i * 4 + k];
+  const bool ok = std::fwrite(rgb.data(), 1, rgb.size(), f) == rgb.size();
+  if (std::fclose(f) != 0 || !ok) throw std::runtime_error("cannot write " + path);
+}
+
 int main(int argc, char** argv) {
   std::string log;
   int w = 640, h = 480, timeDelta = 200, end = -1, dev = 0;
@@ -34,6 +54,10 @@ int main(int argc, char** argv) {
   int icpCountThresh = 40000;                                                                 // :78
   bool fastOdom = false, so3 = true, ftf = false, ply = false, quiet = false, closeLoops = false, allFrames = false, solve = false;
   bool reloc = false, iclnuim = false, flipColors = false;
+  std::string renderDir;
+  int renderEvery = 1;
+  efusion::GlobalModelView::Camera renderCam;   // 640x480, fx = fy = 420, centre (320, 240)
+  bool renderNormals = false, renderColors = false, renderTimes = false, renderUnstable = false, renderWindow = false;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     auto next = [&](int n = 1) { if (i + n >= argc) { std::fprintf(stderr, "missing value for %s\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -64,9 +88,23 @@ int main(int argc, char** argv) {
     else if (a == "-solve") solve = true;     // kept for old command lines: -cl always closes loops with the built-in optimiser now
     else if (a == "-o") closeLoops = false;   // the default here (the reference closes loops unless -o is given)
     else if (a == "-cl") closeLoops = true;   // local loop closure front half every frame, time window from -t
+    else if (a == "-render") renderDir = next();
+    else if (a == "-render-every") renderEvery = std::atoi(next());
+    else if (a == "-render-cam") {
+      renderCam.width = std::atoi(next()); renderCam.height = std::atoi(next());
+      renderCam.fx = std::atof(next()); renderCam.fy = std::atof(next()); renderCam.cx = std::atof(next()); renderCam.cy = std::atof(next());
+    }
+    else if (a == "-render-mode") {
+      const std::string m = next();
+      renderNormals = m == "normals"; renderColors = m == "colors"; renderTimes = m == "times";
+      if (m != "lit" && !renderNormals && !renderColors && !renderTimes) { std::fprintf(stderr, "unknown render mode %s\n", m.c_str()); return 2; }
+    }
+    else if (a == "-render-unstable") renderUnstable = true;
+    else if (a == "-render-window") renderWindow = true;
     else { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); return 2; }
   }
   if (log.empty()) { std::fprintf(stderr, "usage: efusion_replay -l file.klg [...]\n"); return 2; }
+  if (renderEvery < 1) { std::fprintf(stderr, "-render-every needs a positive value\n"); return 2; }
   try {
     Resolution::getInstance(w, h);
     Intrinsics::getInstance(fx, fy, cx, cy);
@@ -80,10 +118,19 @@ int main(int argc, char** argv) {
     int attempts = 0, opened = 0;
     const auto t0 = std::chrono::steady_clock::now();
     int n = 0;
+    std::vector<uint8_t> rgba;
     while (reader.hasMore() && (end < 0 || n < end)) {
       reader.getNext();
       eFusion.processFrame(reader.rgb.data(), (const uint16_t*)reader.depth.data(), reader.timestamp, 1.0f);
       if (closeLoops) { const ef_local_loop& L = eFusion.getLocalLoop(); attempts += L.attempted; opened += L.gates_ok; }
+      if (!renderDir.empty() && n % renderEvery == 0) {
+        eFusion.getGlobalModel().renderPointCloudImage(renderCam, eFusion.get_T_wc_pod(), eFusion.getConfidenceThreshold(), renderUnstable,
+                                                       renderNormals, renderColors, renderWindow, renderTimes, eFusion.getTick(),
+                                                       eFusion.getTimeDelta(), rgba);
+        char name[32];
+        std::snprintf(name, sizeof(name), "/render_%06d.ppm", n);
+        write_ppm(renderDir + name, renderCam.width, renderCam.height, rgba);
+      }
       ++n;
     }
     eFusion.synchronize();
