@@ -780,6 +780,66 @@ class ElasticFusion:
         args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (rgba, depth, vertex, normal, index)]
         _chk(lib().ef_render_model_dev(self.h, C.byref(params), *args), self.h)
 
+    # --- stable surfel IDs and per-surfel labels (ef_set_surfel_ids / ef_enable_labels / ef_fuse_labels) ---
+    def _labelView(self, view):
+        """renderParams keywords -> ef_render_params (None for no keywords: the C default view)"""
+        if not view:
+            return None
+        return self.renderParams(**view)
+
+    def setSurfelIds(self, on=True):
+        """every surfel carries a uint32 ID >= 1 (downloadMap()[:, 5] viewed as uint32), unique for the context's lifetime"""
+        _chk(lib().ef_set_surfel_ids(self.h, c_i(int(bool(on)))), self.h)
+
+    def surfelIds(self) -> np.ndarray:
+        n = self.lastCount()
+        out = np.zeros(max(n, 1), np.uint32)
+        got = c_u32(0)
+        _chk(lib().ef_get_surfel_ids(self.h, _ptr(out), c_u32(n), C.byref(got)), self.h)
+        return out[:got.value].copy()
+
+    def enableLabels(self, numClasses: int):
+        """a float32 [rows][numClasses] table that follows the map by ID (0: off)"""
+        self.numClasses = int(numClasses)
+        _chk(lib().ef_enable_labels(self.h, c_i(int(numClasses))), self.h)
+
+    def fuseLabels(self, probs: np.ndarray, **view):
+        """one observation: probs C x H x W float32 for the view given by renderParams keywords (none: the frame camera, drawUnstable)"""
+        p = self._labelView(view)
+        probs = np.ascontiguousarray(probs, np.float32)
+        _chk(lib().ef_fuse_labels(self.h, None if p is None else C.byref(p), _ptr(probs)), self.h)
+
+    def fuseLabelsDevice(self, probs_dev, params: ef_render_params | None = None):
+        """ef_fuse_labels_dev: a raw device pointer to C x H x W float32, enqueued on the context's stream"""
+        _chk(lib().ef_fuse_labels_dev(self.h, None if params is None else C.byref(params), P(int(probs_dev.value if isinstance(probs_dev, P) else probs_dev))), self.h)
+
+    def labels(self):
+        """(ids, probs): the current rows' IDs and their C floats each, in map row order"""
+        n = self.lastCount()
+        ids = np.zeros(max(n, 1), np.uint32)
+        probs = np.zeros((max(n, 1), max(getattr(self, "numClasses", 1), 1)), np.float32)
+        got = c_u32(0)
+        _chk(lib().ef_get_labels(self.h, _ptr(ids), _ptr(probs), c_u32(n), C.byref(got)), self.h)
+        return ids[:got.value].copy(), probs[:got.value].copy()
+
+    def setLabels(self, probs: np.ndarray):
+        """the whole table: one row of C floats per surfel, in surfelIds() order"""
+        probs = np.ascontiguousarray(probs, np.float32).reshape(-1, getattr(self, "numClasses", 1))
+        _chk(lib().ef_set_labels(self.h, _ptr(probs), c_u32(len(probs))), self.h)
+
+    def renderLabels(self, **view):
+        """(label H x W int32, prob H x W float32) of the view given by renderParams keywords; -1 / 0 where nothing is drawn"""
+        p = self.renderParams(**view)
+        label = np.zeros((p.height, p.width), np.int32)
+        prob = np.zeros((p.height, p.width), np.float32)
+        _chk(lib().ef_render_labels(self.h, C.byref(p), _ptr(label), _ptr(prob)), self.h)
+        return label, prob
+
+    def renderLabelsDevice(self, params: ef_render_params, label=None, prob=None):
+        """ef_render_labels_dev: raw device pointers (int, c_void_p or None), enqueued on the context's stream"""
+        args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (label, prob)]
+        _chk(lib().ef_render_labels_dev(self.h, C.byref(params), *args), self.h)
+
     def setReferenceDownload(self, on=True):
         """downloadMap / savePly read what GlobalModel::downloadMap reads (the pre-clean buffer, quirk Q14) instead of model()"""
         _chk(lib().ef_set_reference_download(self.h, c_i(int(on))), self.h)

@@ -197,6 +197,24 @@ struct ef_ctx {
   size_t render_zbuf_n = 0;
   uint8_t* render_out = nullptr;
   size_t render_out_bytes = 0;
+  // stable surfel IDs and labels (ef_set_surfel_ids / ef_enable_labels; kernels in ef_labels.inc).  ids_state (device, kept for the context's
+  // lifetime once allocated): [0] the next ID, [1] the shape flag of ids_check, [2 + k] the row count of label alignment k.  The table and
+  // the ID list it was aligned to exist twice (ping-pong, label_cur the live half), label_rows rows each, grown on demand.  label_known is
+  // the map count as of label_known_frames frames (stamps.size()): an upper bound of the count needs no device round trip.
+  bool ids_on = false, ids_bad = false;
+  unsigned* ids_state = nullptr;
+  int label_C = 0, label_cur = 0;
+  float* label_tab[2] = {};
+  uint32_t* label_ids[2] = {};
+  size_t label_rows = 0, label_bound = 0;
+  size_t label_known = 0, label_known_frames = 0, label_ev_frames = 0;
+  unsigned* label_count_h = nullptr;       // pinned: the count each label call leaves behind, valid once label_ev has completed
+  hipEvent_t label_ev = nullptr;
+  bool label_ev_pending = false;
+  uint32_t* label_index = nullptr;         // the view's index image
+  size_t label_index_n = 0;
+  uint8_t* label_stage = nullptr;          // host-pointer calls: the probability image in, the label images out
+  size_t label_stage_bytes = 0;
 };
 
 namespace {
@@ -1151,8 +1169,21 @@ void ctx_free(ef_ctx* c) {
   for (auto e : c->ks_stop) (void)hipEventDestroy(e);
   if (c->render_zbuf) (void)hipFree(c->render_zbuf);
   if (c->render_out) (void)hipFree(c->render_out);
+  for (int k = 0; k < 2; ++k) {
+    if (c->label_tab[k]) (void)hipFree(c->label_tab[k]);
+    if (c->label_ids[k]) (void)hipFree(c->label_ids[k]);
+  }
+  if (c->ids_state) (void)hipFree(c->ids_state);
+  if (c->label_index) (void)hipFree(c->label_index);
+  if (c->label_stage) (void)hipFree(c->label_stage);
+  if (c->label_count_h) (void)hipHostFree(c->label_count_h);
+  if (c->label_ev) (void)hipEventDestroy(c->label_ev);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
 }
+
+// surfel IDs around the map's download / upload (defined with the label entry points at the end of this file)
+int ids_prepare(ef_ctx* c, const char* fn);
+int ids_uploaded(ef_ctx* c, uint32_t count);
 
 }  // namespace
 
@@ -1682,6 +1713,10 @@ int ef_map_count(ef_ctx* c, uint32_t* count) {
 int ef_map_download(ef_ctx* c, float* surfels, uint32_t max_surfels, uint32_t* count) {
   if (!c || !count) return EF_EINVAL;
   DeviceGuard dg_(c);
+  if (c->ids_on) {   // rows created since the last ID-consuming call get theirs first
+    const int ri = ids_prepare(c, "ef_map_download");
+    if (ri != EF_OK) return ri;
+  }
   uint32_t n = 0;
   int r = ef_map_count(c, &n);
   if (r != EF_OK) return r;
@@ -1726,6 +1761,7 @@ int ef_map_upload(ef_ctx* c, const float* surfels, uint32_t count) {
     EF_HIP(c, e);
   }
   hipLaunchKernelGGL(k_set_count, dim3(1), dim3(64), 0, c->stream, &c->st->map_counts[c->cur], count);
+  if (c->ids_on) return ids_uploaded(c, count);
   return EF_OK;
 }
 int ef_get_pose_qt(ef_ctx* c, double* q4_t3) {
@@ -2678,3 +2714,362 @@ int ef_render_model(ef_ctx* c, const ef_render_params* p, uint8_t* rgba, float* 
 }
 
 }  // extern "C"
+
+// ================================================================================================
+// Stable surfel IDs and per-surfel label fusion (include/ef_hip.h; kernels in ef_labels.inc)
+// ================================================================================================
+namespace {
+int capture_check(ef_ctx* c, const char* fn) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  EF_HIP(c, hipStreamIsCapturing(c->stream, &cs));
+  if (cs != hipStreamCaptureStatusNone) { c->err = std::string(fn) + ": the context's stream is being captured"; return EF_ESTATE; }
+  return EF_OK;
+}
+// the lazy numbering every ID-consuming call starts with
+int ids_prepare(ef_ctx* c, const char* fn) {
+  if (c->ids_bad) {
+    c->err = std::string(fn) + ": the uploaded map's ID lane (float 5 of each surfel) is not a strictly increasing non-zero prefix followed by "
+             "a zero suffix";
+    return EF_ESTATE;
+  }
+  efm::ids_assign(c->maps[c->cur], &c->st->map_counts[c->cur], c->ids_state, c->stream);
+  EF_HIP(c, hipGetLastError());
+  return EF_OK;
+}
+int read_count(ef_ctx* c, uint32_t* n) {
+  EF_HIP(c, hipMemcpyAsync(n, &c->st->map_counts[c->cur], sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  EF_HIP(c, hipStreamSynchronize(c->stream));
+  return EF_OK;
+}
+// An upper bound of the map count without a device round trip: the count a label call left behind (once its event has completed) or an
+// upload set, plus one image of new surfels per frame since (the first frame seeds at most width x height, fusion appends fewer).
+size_t labels_count_bound(ef_ctx* c) {
+  if (c->label_ev_pending && hipEventQuery(c->label_ev) == hipSuccess) {
+    c->label_known = *c->label_count_h;
+    c->label_known_frames = c->label_ev_frames;
+    c->label_ev_pending = false;
+  }
+  const size_t P = (size_t)c->cam.cols * c->cam.rows;
+  const size_t b = c->label_known + (c->stamps.size() - c->label_known_frames) * P;
+  return b < c->capacity ? b : c->capacity;
+}
+void labels_free(ef_ctx* c) {
+  for (int k = 0; k < 2; ++k) {
+    if (c->label_tab[k]) (void)hipFree(c->label_tab[k]);
+    if (c->label_ids[k]) (void)hipFree(c->label_ids[k]);
+    c->label_tab[k] = nullptr;
+    c->label_ids[k] = nullptr;
+  }
+  c->label_rows = 0;
+  c->label_C = 0;
+}
+// table and ID lists for at least the map count; waits for the device only when the bound outgrows them
+int labels_reserve(ef_ctx* c) {
+  c->label_bound = labels_count_bound(c);
+  if (c->label_bound <= c->label_rows) return EF_OK;
+  uint32_t n = 0;
+  int r = read_count(c, &n);
+  if (r != EF_OK) return r;
+  unsigned np[2] = {0, 0};
+  EF_HIP(c, hipMemcpy(np, c->ids_state + 2, sizeof(np), hipMemcpyDeviceToHost));
+  c->label_known = n;
+  c->label_known_frames = c->stamps.size();
+  c->label_ev_pending = false;
+  c->label_bound = n;
+  if (n <= c->label_rows) return EF_OK;
+  const size_t P = (size_t)c->cam.cols * c->cam.rows, C = (size_t)c->label_C;
+  size_t rows = (size_t)n + std::max((size_t)n / 4, P);
+  if (rows > c->capacity) rows = c->capacity;
+  float* tab[2] = {};
+  uint32_t* ids[2] = {};
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+    e = hipMalloc((void**)&tab[k], rows * C * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&ids[k], rows * sizeof(uint32_t));
+  }
+  if (e != hipSuccess) {
+    for (int k = 0; k < 2; ++k) { if (tab[k]) (void)hipFree(tab[k]); if (ids[k]) (void)hipFree(ids[k]); }
+    c->err = std::string("hipMalloc (label table): ") + hipGetErrorString(e);
+    return EF_ENOMEM;
+  }
+  const int w = c->label_cur;   // the live alignment moves over; the other half is rewritten by the next one
+  const size_t keep = std::min((size_t)np[w], c->label_rows);
+  if (keep) {
+    EF_HIP(c, hipMemcpyAsync(tab[w], c->label_tab[w], keep * C * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    EF_HIP(c, hipMemcpyAsync(ids[w], c->label_ids[w], keep * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    EF_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  const int C_keep = c->label_C;
+  labels_free(c);
+  c->label_C = C_keep;
+  for (int k = 0; k < 2; ++k) { c->label_tab[k] = tab[k]; c->label_ids[k] = ids[k]; }
+  c->label_rows = rows;
+  return EF_OK;
+}
+// what every label call starts with: IDs for the new rows, then the table re-aligned to the current rows
+int labels_begin(ef_ctx* c, const char* fn) {
+  int r = capture_check(c, fn);
+  if (r != EF_OK) return r;
+  if (!c->label_C) { c->err = std::string(fn) + ": labels are off (ef_enable_labels)"; return EF_ESTATE; }
+  r = ids_prepare(c, fn);
+  if (r != EF_OK) return r;
+  r = labels_reserve(c);
+  if (r != EF_OK) return r;
+  const int w = c->label_cur;
+  efm::LabelAlign a{c->maps[c->cur], &c->st->map_counts[c->cur], c->label_ids[w], c->label_tab[w], c->ids_state + 2 + w,
+                    c->label_ids[w ^ 1], c->label_tab[w ^ 1], c->ids_state + 2 + (w ^ 1), c->label_C, 1.0f / (float)c->label_C};
+  efm::labels_align(a, (unsigned)c->label_bound, c->stream);
+  EF_HIP(c, hipGetLastError());
+  c->label_cur ^= 1;
+  // the count this call saw, for the next call's bound
+  EF_HIP(c, hipMemcpyAsync(c->label_count_h, &c->st->map_counts[c->cur], sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+  EF_HIP(c, hipEventRecord(c->label_ev, c->stream));
+  c->label_ev_frames = c->stamps.size();
+  c->label_ev_pending = true;
+  return EF_OK;
+}
+int grow(ef_ctx* c, uint8_t** buf, size_t* have, size_t bytes, const char* what) {
+  if (bytes <= *have) return EF_OK;
+  EF_HIP(c, hipStreamSynchronize(c->stream));
+  if (*buf) { (void)hipFree(*buf); *buf = nullptr; *have = 0; }
+  hipError_t e = hipMalloc((void**)buf, bytes);
+  if (e != hipSuccess) { *buf = nullptr; c->err = std::string("hipMalloc (") + what + "): " + hipGetErrorString(e); return EF_ENOMEM; }
+  *have = bytes;
+  return EF_OK;
+}
+// the view's index image into label_index, exactly as ef_render_model draws it
+int labels_index(ef_ctx* c, const ef_render_params* p) {
+  const size_t P = (size_t)p->width * p->height;
+  size_t have = c->label_index_n * sizeof(uint32_t);
+  const int r = grow(c, (uint8_t**)&c->label_index, &have, P * sizeof(uint32_t), "label index image");
+  if (r != EF_OK) return r;
+  c->label_index_n = have / sizeof(uint32_t);
+  return render_enqueue(c, p, efm::RenderOut{nullptr, nullptr, nullptr, nullptr, c->label_index});
+}
+// refusals before any GPU work; the view is checked with the render's rules
+int labels_check(ef_ctx* c, const ef_render_params* view, bool view_required, const void* probs, bool probs_required, const char* fn) {
+  std::string& err = c ? c->err : g_create_error;
+  if (probs_required && !probs) { err = std::string(fn) + ": null probability image"; return EF_EINVAL; }
+  if (view || view_required) return render_check(c, view, fn);
+  if (!c) { err = std::string(fn) + ": null context"; return EF_EINVAL; }
+  return EF_OK;
+}
+int labels_view(ef_ctx* c, const ef_render_params* view, ef_render_params* q) {
+  if (view) { *q = *view; return EF_OK; }
+  const int r = ef_default_render_params(c, q);
+  q->draw_unstable = 1;
+  return r;
+}
+int fuse_enqueue(ef_ctx* c, const ef_render_params* q, const float* probs_dev) {
+  int r = labels_index(c, q);
+  if (r != EF_OK) return r;
+  efm::LabelFuse f{};
+  f.map = c->maps[c->cur];
+  f.count_dev = &c->st->map_counts[c->cur];
+  f.cam = efm::Cam{q->width, q->height, q->fx, q->fy, q->cx, q->cy};
+  float pose_f[16];
+  pose_mats(q->T_wc, f.Tcw, pose_f);
+  f.index = c->label_index;
+  f.probs = probs_dev;
+  f.tab = c->label_tab[c->label_cur];
+  f.C = c->label_C;
+  efm::labels_fuse(f, (unsigned)c->label_bound, c->stream);
+  EF_HIP(c, hipGetLastError());
+  return EF_OK;
+}
+int render_labels_enqueue(ef_ctx* c, const ef_render_params* p, int32_t* label, float* prob) {
+  int r = labels_index(c, p);
+  if (r != EF_OK) return r;
+  efm::labels_gather(c->label_index, p->width * p->height, c->label_tab[c->label_cur], c->label_C, label, prob, c->stream);
+  EF_HIP(c, hipGetLastError());
+  return EF_OK;
+}
+}  // namespace
+extern "C" {
+
+int ef_set_surfel_ids(ef_ctx* c, int on) {
+  if (!c) { g_create_error = "ef_set_surfel_ids: null context"; return EF_EINVAL; }
+  DeviceGuard dg_(c);
+  int r = capture_check(c, "ef_set_surfel_ids");
+  if (r != EF_OK) return r;
+  if ((on != 0) == c->ids_on) return EF_OK;
+  if (on && !c->ids_state) {
+    const unsigned init[4] = {1u, 0u, 0u, 0u};
+    EF_HIP(c, hipMalloc((void**)&c->ids_state, sizeof(init)));
+    EF_HIP(c, hipMemcpy(c->ids_state, init, sizeof(init), hipMemcpyHostToDevice));
+    EF_HIP(c, hipHostMalloc((void**)&c->label_count_h, sizeof(unsigned)));
+    EF_HIP(c, hipEventCreateWithFlags(&c->label_ev, hipEventDisableTiming));
+  }
+  if (!on) labels_free(c);
+  // on: the lane is numbered from the counter by the next ID-consuming call (1 .. N the first time); off: as if IDs had never been on
+  efm::ids_zero(c->maps[c->cur], &c->st->map_counts[c->cur], c->capacity, c->stream);
+  EF_HIP(c, hipGetLastError());
+  c->ids_on = on != 0;
+  c->ids_bad = false;
+  return EF_OK;
+}
+
+int ef_get_surfel_ids(ef_ctx* c, uint32_t* ids, uint32_t max_ids, uint32_t* count) {
+  if (!c || !count) { (c ? c->err : g_create_error) = c ? "ef_get_surfel_ids: null count" : "ef_get_surfel_ids: null context"; return EF_EINVAL; }
+  DeviceGuard dg_(c);
+  int r = capture_check(c, "ef_get_surfel_ids");
+  if (r != EF_OK) return r;
+  if (!c->ids_on) { c->err = "ef_get_surfel_ids: surfel IDs are off (ef_set_surfel_ids)"; return EF_ESTATE; }
+  r = ids_prepare(c, "ef_get_surfel_ids");
+  if (r != EF_OK) return r;
+  uint32_t n = 0;
+  r = read_count(c, &n);
+  if (r != EF_OK) return r;
+  if (n > max_ids) n = max_ids;
+  *count = n;
+  if (!ids || !n) return EF_OK;
+  uint32_t* tmp = nullptr;
+  EF_HIP(c, hipMalloc((void**)&tmp, (size_t)n * sizeof(uint32_t)));
+  efm::ids_gather(c->maps[c->cur], n, tmp, c->stream);
+  hipError_t e = hipMemcpyAsync(ids, tmp, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(tmp);
+  EF_HIP(c, e);
+  return EF_OK;
+}
+
+int ef_enable_labels(ef_ctx* c, int num_classes) {
+  if (num_classes < 0 || num_classes > 256) {
+    (c ? c->err : g_create_error) = "ef_enable_labels: num_classes must lie in 0 .. 256";
+    return EF_EINVAL;
+  }
+  if (!c) { g_create_error = "ef_enable_labels: null context"; return EF_EINVAL; }
+  DeviceGuard dg_(c);
+  int r = capture_check(c, "ef_enable_labels");
+  if (r != EF_OK) return r;
+  labels_free(c);
+  if (!num_classes) return EF_OK;
+  if (!c->ids_on) {
+    r = ef_set_surfel_ids(c, 1);
+    if (r != EF_OK) return r;
+  }
+  EF_HIP(c, hipMemsetAsync(c->ids_state + 2, 0, 2 * sizeof(unsigned), c->stream));   // no previous alignment: every row starts at the prior
+  c->label_C = num_classes;
+  c->label_cur = 0;
+  c->label_ev_pending = false;
+  c->label_known = c->capacity;   // unknown: the first label call reads it
+  c->label_known_frames = c->stamps.size();
+  return EF_OK;
+}
+
+int ef_set_labels(ef_ctx* c, const float* probs, uint32_t count) {
+  int r = labels_check(c, nullptr, false, probs, count != 0, "ef_set_labels");
+  if (r != EF_OK) return r;
+  DeviceGuard dg_(c);
+  r = labels_begin(c, "ef_set_labels");
+  if (r != EF_OK) return r;
+  uint32_t n = 0;
+  r = read_count(c, &n);
+  if (r != EF_OK) return r;
+  if (count != n) { c->err = "ef_set_labels: count must equal the map count (" + std::to_string(n) + ")"; return EF_EINVAL; }
+  if (n) {
+    EF_HIP(c, hipMemcpyAsync(c->label_tab[c->label_cur], probs, (size_t)n * c->label_C * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    EF_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  return EF_OK;
+}
+
+int ef_get_labels(ef_ctx* c, uint32_t* ids, float* probs, uint32_t max_rows, uint32_t* count) {
+  if (!c || !count) { (c ? c->err : g_create_error) = c ? "ef_get_labels: null count" : "ef_get_labels: null context"; return EF_EINVAL; }
+  DeviceGuard dg_(c);
+  int r = labels_begin(c, "ef_get_labels");
+  if (r != EF_OK) return r;
+  uint32_t n = 0;
+  r = read_count(c, &n);
+  if (r != EF_OK) return r;
+  if (n > max_rows) n = max_rows;
+  *count = n;
+  if (!n) return EF_OK;
+  if (ids) EF_HIP(c, hipMemcpyAsync(ids, c->label_ids[c->label_cur], (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if (probs)
+    EF_HIP(c, hipMemcpyAsync(probs, c->label_tab[c->label_cur], (size_t)n * c->label_C * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  EF_HIP(c, hipStreamSynchronize(c->stream));
+  return EF_OK;
+}
+
+int ef_fuse_labels_dev(ef_ctx* c, const ef_render_params* view, const float* probs_dev) {
+  int r = labels_check(c, view, false, probs_dev, true, "ef_fuse_labels_dev");
+  if (r != EF_OK) return r;
+  DeviceGuard dg_(c);
+  r = labels_begin(c, "ef_fuse_labels_dev");
+  if (r != EF_OK) return r;
+  ef_render_params q;
+  r = labels_view(c, view, &q);
+  if (r != EF_OK) return r;
+  return fuse_enqueue(c, &q, probs_dev);
+}
+
+int ef_fuse_labels(ef_ctx* c, const ef_render_params* view, const float* probs_chw) {
+  int r = labels_check(c, view, false, probs_chw, true, "ef_fuse_labels");
+  if (r != EF_OK) return r;
+  DeviceGuard dg_(c);
+  r = labels_begin(c, "ef_fuse_labels");
+  if (r != EF_OK) return r;
+  ef_render_params q;
+  r = labels_view(c, view, &q);
+  if (r != EF_OK) return r;
+  const size_t bytes = (size_t)q.width * q.height * c->label_C * sizeof(float);
+  r = grow(c, &c->label_stage, &c->label_stage_bytes, bytes, "label staging");
+  if (r != EF_OK) return r;
+  EF_HIP(c, hipMemcpyAsync(c->label_stage, probs_chw, bytes, hipMemcpyHostToDevice, c->stream));
+  r = fuse_enqueue(c, &q, (const float*)c->label_stage);
+  if (r != EF_OK) return r;
+  EF_HIP(c, hipStreamSynchronize(c->stream));
+  return EF_OK;
+}
+
+int ef_render_labels_dev(ef_ctx* c, const ef_render_params* p, int32_t* label_dev, float* prob_dev) {
+  int r = labels_check(c, p, true, nullptr, false, "ef_render_labels_dev");
+  if (r != EF_OK) return r;
+  DeviceGuard dg_(c);
+  r = labels_begin(c, "ef_render_labels_dev");
+  if (r != EF_OK) return r;
+  return render_labels_enqueue(c, p, label_dev, prob_dev);
+}
+
+int ef_render_labels(ef_ctx* c, const ef_render_params* p, int32_t* label, float* prob) {
+  int r = labels_check(c, p, true, nullptr, false, "ef_render_labels");
+  if (r != EF_OK) return r;
+  DeviceGuard dg_(c);
+  r = labels_begin(c, "ef_render_labels");
+  if (r != EF_OK) return r;
+  const size_t P = (size_t)p->width * p->height;
+  r = grow(c, &c->label_stage, &c->label_stage_bytes, P * 8, "label staging");
+  if (r != EF_OK) return r;
+  int32_t* dl = label ? (int32_t*)c->label_stage : nullptr;
+  float* dp = prob ? (float*)(c->label_stage + P * 4) : nullptr;
+  r = render_labels_enqueue(c, p, dl, dp);
+  if (r != EF_OK) return r;
+  if (label) EF_HIP(c, hipMemcpyAsync(label, dl, P * 4, hipMemcpyDeviceToHost, c->stream));
+  if (prob) EF_HIP(c, hipMemcpyAsync(prob, dp, P * 4, hipMemcpyDeviceToHost, c->stream));
+  EF_HIP(c, hipStreamSynchronize(c->stream));
+  return EF_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// ef_map_upload with IDs on: the uploaded lane is kept when its shape is valid (the counter then continues above its largest ID, ids_assign);
+// any other shape is remembered and refused by the next ID-consuming call.  Labels restart from the prior.
+int ids_uploaded(ef_ctx* c, uint32_t count) {
+  EF_HIP(c, hipMemsetAsync(c->ids_state + 1, 0, sizeof(unsigned), c->stream));
+  efm::ids_check(c->maps[c->cur], count, c->ids_state + 1, c->stream);
+  EF_HIP(c, hipGetLastError());
+  unsigned flag = 0;
+  EF_HIP(c, hipMemcpyAsync(&flag, c->ids_state + 1, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+  EF_HIP(c, hipStreamSynchronize(c->stream));
+  c->ids_bad = flag != 0;
+  if (c->label_C) {
+    EF_HIP(c, hipMemsetAsync(c->ids_state + 2 + c->label_cur, 0, sizeof(unsigned), c->stream));
+    c->label_known = count;
+    c->label_known_frames = c->stamps.size();
+    c->label_ev_pending = false;
+  }
+  return EF_OK;
+}
+}  // namespace

@@ -173,4 +173,38 @@ struct RenderOut {   // row-major images; a null pointer is not written
 // zbuf: cols x rows keys, all ZBUF_EMPTY on entry and on return
 void render_model(const RenderArgs& a, SurfelSoA map, const unsigned* count_dev, unsigned long long* zbuf, RenderOut out, hipStream_t s);
 
+// ---- stable surfel IDs and label fusion (ef_labels.inc; ef_set_surfel_ids / ef_enable_labels of include/ef_hip.h) ----
+// state[0]: the next ID to hand out.  One workgroup numbers the zero suffix of the ID lane (col_time.y as uint32).
+void ids_assign(SurfelSoA map, const unsigned* count_dev, unsigned* state, hipStream_t s);
+// *flag |= 1 unless the lane of rows [0, n) is a strictly increasing non-zero prefix followed by a zero suffix
+void ids_check(SurfelSoA map, unsigned n, unsigned* flag, hipStream_t s);
+// max_rows: an upper bound of *count_dev (sizes the grid only)
+void ids_zero(SurfelSoA map, const unsigned* count_dev, unsigned max_rows, hipStream_t s);
+void ids_gather(SurfelSoA map, unsigned n, uint32_t* out, hipStream_t s);
+struct LabelAlign {
+  SurfelSoA map;
+  const unsigned* count_dev;
+  const uint32_t* ids_in;   // the previous alignment's IDs (*n_in of them, sorted) and their rows
+  const float* tab_in;
+  const unsigned* n_in;
+  uint32_t* ids_out;        // the current rows' IDs and rows; *n_out = *count_dev
+  float* tab_out;
+  unsigned* n_out;
+  int C;
+  float prior;              // 1 / C
+};
+struct LabelFuse {
+  SurfelSoA map;
+  const unsigned* count_dev;
+  Cam cam;
+  float Tcw[16];            // float T_wc^-1, row-major (pose_mats), as the render takes it
+  const uint32_t* index;    // the view's index image (render_model), row-major
+  const float* probs;       // C x rows x cols
+  float* tab;
+  int C;
+};
+void labels_align(const LabelAlign& a, unsigned max_rows, hipStream_t s);
+void labels_fuse(const LabelFuse& f, unsigned max_rows, hipStream_t s);
+void labels_gather(const uint32_t* index, int P, const float* tab, int C, int32_t* label, float* prob, hipStream_t s);
+
 }  // namespace efm

@@ -1492,5 +1492,6 @@ void sample_graph(SurfelSoA map, const unsigned* count_dev, int stride, int max_
 }
 
 #include "ef_render.inc"
+#include "ef_labels.inc"
 
 }  // namespace efm

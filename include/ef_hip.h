@@ -406,6 +406,55 @@ int ef_render_model(ef_ctx* ctx, const ef_render_params* params, uint8_t* rgba, 
 int ef_render_model_dev(ef_ctx* ctx, const ef_render_params* params, uint8_t* rgba_dev, float* depth_dev, float* vertex_dev,
                         float* normal_dev, uint32_t* index_dev);
 
+/* ---- Stable surfel IDs and per-surfel label fusion (SemanticFusion-style class probabilities, or any per-surfel distribution).  Off by
+ * default; with both switches off nothing of this runs and every output is what it is without it.  Frames never read IDs or labels.
+ *
+ * IDs: with IDs on, every surfel of model() carries a uint32 ID >= 1, stored as the RAW BIT PATTERN of the colour stream's unused lane: float 5
+ * (from 0) of the 12 per surfel that ef_map_download returns (read it as uint32, never as a float value; small IDs are denormal patterns).
+ * IDs are unique for the context's lifetime, never reused, and strictly increasing with map row (the map keeps creation order).  They are
+ * handed out lazily: every ID-consuming call (ef_get_surfel_ids, the label calls, ef_map_download while IDs are on) first numbers the rows
+ * created since the last one.  Switching on numbers the current map (1 .. N the first time); switching off zeroes the lane, so a download equals
+ * that of a context that never had IDs, and switches labels off.  ef_map_upload while IDs are on keeps the uploaded lane when it is a strictly
+ * increasing non-zero prefix followed by a zero suffix (a map downloaded with IDs; an all-zero lane, numbered by the next call); the counter
+ * continues above its largest ID.  Any other lane makes every later ID-consuming call fail with EF_ESTATE until the next valid upload or
+ * switch-on.  With ef_set_reference_download on, the downloaded buffer is the pre-clean copy (quirk Q14) and its lane is whatever that buffer
+ * holds: IDs as of the last frame's update pass, zero for surfels created after it.
+ *
+ * Labels: a float32 table [rows][C] in map row order on the device.  Every label call first re-aligns it to the current rows: a row whose ID was
+ * present at the previous label call keeps its C floats bit for bit, a new row gets the prior 1 / C.  ef_map_upload while labels are on resets
+ * every row to the prior.
+ *
+ * Fusion (ef_fuse_labels): probs_chw is C x height x width float32 for the view (a network's NCHW output without N; a network at a lower
+ * resolution passes scaled intrinsics).  I is the view's index image exactly as ef_render_model returns it for the same parameters.  Surfel
+ * row s is OBSERVED when, with p = T_cw p_world (the float T_cw the render uses) and z > 0, u = floor(fx x / z + cx), v = floor(fy y / z + cy)
+ * (f32, no contraction) lie in the image and I[v width + u] == s.  For an observed row, with o the C values at (u, v): q_c = p_c o_c,
+ * Z = sum of q_c in ascending c, p_c <- q_c / Z when Z is finite and > 0 (otherwise the row stays).  Inputs are used as given, not
+ * renormalised.  One observation per surfel per call: no atomics, deterministic.
+ *
+ * All label calls are refused with EF_ESTATE while the context's stream is being captured and while labels are off; bad parameters are refused
+ * with EF_EINVAL before anything is enqueued (with a NULL context, ef_last_error(NULL) has the message).  The _dev variants enqueue on the
+ * context's stream; they wait for the device only when the table has to grow (the count bound outgrows it) or for a NULL view (the pose). */
+int ef_set_surfel_ids(ef_ctx* ctx, int on);
+/* the ID of every row of model(), at most max_ids of them; *count = rows written.  EF_ESTATE when IDs are off.  Synchronises. */
+int ef_get_surfel_ids(ef_ctx* ctx, uint32_t* ids, uint32_t max_ids, uint32_t* count);
+/* num_classes 1 .. 256 (implies IDs on; every row starts at 1 / C); 0 switches labels off and frees the table.  EF_EINVAL outside 0 .. 256. */
+int ef_enable_labels(ef_ctx* ctx, int num_classes);
+/* the whole table from HOST memory: count rows (must equal the current map count, else EF_EINVAL) of C floats, in ef_get_surfel_ids order.
+ * Restores a checkpoint.  Synchronises. */
+int ef_set_labels(ef_ctx* ctx, const float* probs, uint32_t count);
+/* aligns, then copies up to max_rows rows: their IDs and C floats each (either pointer may be NULL); *count = rows.  Synchronises. */
+int ef_get_labels(ef_ctx* ctx, uint32_t* ids_or_null, float* probs_or_null, uint32_t max_rows, uint32_t* count);
+/* one observation.  view NULL = ef_default_render_params with draw_unstable = 1; color_type, draw_window, time and time_delta are ignored.
+ * HOST probs_chw: staged and synchronised.  EF_EINVAL for a NULL image or view parameters ef_render_model refuses. */
+int ef_fuse_labels(ef_ctx* ctx, const ef_render_params* view_or_null, const float* probs_chw);
+/* the same with a DEVICE image, enqueued on the context's stream */
+int ef_fuse_labels_dev(ef_ctx* ctx, const ef_render_params* view_or_null, const float* probs_chw_dev);
+/* per pixel of the view's index image: label = argmax of the surfel's row (ties to the lowest class), prob = that maximum; -1 and 0 where
+ * nothing is drawn.  width x height each, row-major, HOST pointers (either may be NULL); synchronises. */
+int ef_render_labels(ef_ctx* ctx, const ef_render_params* params, int32_t* label, float* prob);
+/* the same with DEVICE pointers, enqueued on the context's stream */
+int ef_render_labels_dev(ef_ctx* ctx, const ef_render_params* params, int32_t* label_dev, float* prob_dev);
+
 /* named internal images, copied to HOST (synchronises); for tests and for a front-end's drawing code */
 enum ef_image {
   EF_IMG_DEPTH_FILTERED = 0,      /* u16  */
