@@ -840,6 +840,62 @@ class ElasticFusion:
         args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (label, prob)]
         _chk(lib().ef_render_labels_dev(self.h, C.byref(params), *args), self.h)
 
+    # --- spatial index and nearest-surfel / kNN queries (ef_query_nearest / ef_query_knn) ---
+    QUERY_DEFAULT_CELL = 0.02   # EF_QUERY_DEFAULT_CELL of include/ef_hip.h
+
+    def setQueryCell(self, cell_m: float):
+        """the index grid's cell edge in metres; results never depend on it"""
+        _chk(lib().ef_set_query_cell(self.h, c_f(cell_m)), self.h)
+
+    def debugQueryLanes(self, lanes: int):
+        _chk(lib().ef_debug_query_lanes(self.h, c_i(lanes)), self.h)
+
+    def queryNearest(self, points, max_dist: float, min_conf: float = -1.0, ids: bool = False):
+        """per point (n x 3) the nearest surfel with confidence > min_conf within max_dist, ties to the lower row: (rows uint32, dist = sqrt(d2),
+        plane distance along the surfel's normal[, ids]); a miss is row 0xFFFFFFFF, dist inf, plane 0, id 0.  min_conf < 0: every surfel."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = len(pts)
+        row = np.zeros(max(n, 1), np.uint32)
+        d2 = np.zeros(max(n, 1), np.float32)
+        plane = np.zeros(max(n, 1), np.float32)
+        sid = np.zeros(max(n, 1), np.uint32) if ids else None
+        _chk(lib().ef_query_nearest(self.h, _ptr(pts), c_u32(n), c_f(max_dist), c_f(min_conf), _ptr(row), None if sid is None else _ptr(sid),
+                                    _ptr(d2), _ptr(plane)), self.h)
+        out = (row[:n], np.sqrt(d2[:n]), plane[:n])
+        return out + (sid[:n],) if ids else out
+
+    def queryNearestRaw(self, points, max_dist: float, min_conf: float = -1.0):
+        """(rows, dist2, plane) exactly as ef_query_nearest writes them (dist2 not rooted)"""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = len(pts)
+        row = np.zeros(max(n, 1), np.uint32)
+        d2 = np.zeros(max(n, 1), np.float32)
+        plane = np.zeros(max(n, 1), np.float32)
+        _chk(lib().ef_query_nearest(self.h, _ptr(pts), c_u32(n), c_f(max_dist), c_f(min_conf), _ptr(row), None, _ptr(d2), _ptr(plane)), self.h)
+        return row[:n], d2[:n], plane[:n]
+
+    def queryKnn(self, points, k: int, max_dist: float, min_conf: float = -1.0):
+        """per point the first min(k, eligible) surfels in (d2, row) order: (rows n x k uint32, dist2 n x k float32, count n uint32); unused slots
+        are misses (0xFFFFFFFF, inf); count is the number of ALL surfels within max_dist and may exceed k"""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n, k = len(pts), int(k)
+        kk = min(max(k, 1), 16)
+        rows = np.zeros((max(n, 1), kk), np.uint32)
+        d2 = np.zeros((max(n, 1), kk), np.float32)
+        cnt = np.zeros(max(n, 1), np.uint32)
+        _chk(lib().ef_query_knn(self.h, _ptr(pts), c_u32(n), c_i(k), c_f(max_dist), c_f(min_conf), _ptr(rows), _ptr(d2), _ptr(cnt)), self.h)
+        return rows[:n], d2[:n], cnt[:n]
+
+    def queryNearestDevice(self, points_dev, n: int, max_dist: float, min_conf: float = -1.0, row=None, ids=None, dist2=None, plane=None):
+        """ef_query_nearest_dev: raw device pointers (int, c_void_p or None), enqueued on the context's stream"""
+        args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (points_dev, row, ids, dist2, plane)]
+        _chk(lib().ef_query_nearest_dev(self.h, args[0], c_u32(n), c_f(max_dist), c_f(min_conf), *args[1:]), self.h)
+
+    def queryKnnDevice(self, points_dev, n: int, k: int, max_dist: float, min_conf: float = -1.0, rows=None, dist2=None, count=None):
+        """ef_query_knn_dev: raw device pointers (int, c_void_p or None), enqueued on the context's stream"""
+        args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (points_dev, rows, dist2, count)]
+        _chk(lib().ef_query_knn_dev(self.h, args[0], c_u32(n), c_i(int(k)), c_f(max_dist), c_f(min_conf), *args[1:]), self.h)
+
     def setReferenceDownload(self, on=True):
         """downloadMap / savePly read what GlobalModel::downloadMap reads (the pre-clean buffer, quirk Q14) instead of model()"""
         _chk(lib().ef_set_reference_download(self.h, c_i(int(on))), self.h)

@@ -215,6 +215,19 @@ struct ef_ctx {
   size_t label_index_n = 0;
   uint8_t* label_stage = nullptr;          // host-pointer calls: the probability image in, the label images out
   size_t label_stage_bytes = 0;
+  // spatial index and nearest / kNN queries (ef_query_nearest / ef_query_knn; kernels in ef_query.inc).  map_gen counts the calls that can
+  // change the map's rows or positions; the index is rebuilt when it or the cell size differs from what the index was built for.
+  uint64_t map_gen = 1, query_gen = 0;
+  float query_cell = EF_QUERY_DEFAULT_CELL, query_built_cell = 0.f;
+  int query_lanes = 0;                     // lanes per query; 0 = the measured choice: 16 for nearest, 1 for kNN (ef_debug_query_lanes)
+  float4* query_sorted = nullptr;          // the cell-sorted copy {x, y, z, conf} and each record's map row
+  uint32_t* query_rows = nullptr;
+  size_t query_cap = 0;
+  uint32_t* query_cells = nullptr;         // buckets (ends after the build) followed by the scan's tile sums
+  size_t query_cells_cap = 0;
+  uint32_t query_nb = 0, query_n = 0;
+  uint8_t* query_stage = nullptr;          // host-pointer calls: the points in, the results out
+  size_t query_stage_bytes = 0;
 };
 
 namespace {
@@ -730,6 +743,7 @@ int process_frame(ef_ctx* c, const uint8_t* rgb_src, const uint16_t* depth_src, 
                   float weightMultiplier, const double* in_T_wc, hipEvent_t images_ready = nullptr) {
   hipStream_t s = c->stream;
   const int W = c->cam.cols, H = c->cam.rows;
+  ++c->map_gen;   // fusion, clean and deformations change rows and positions: a spatial index built before this frame is stale
   // a persistent tracker launch of an EARLIER frame gave up waiting after admission (a protocol failure, sticky: every later launch of that
   // instance returns at once): k_track_end has copied the flag into host-mapped memory; reported here, where the front end calls
   // (class ElasticFusion::processFrame throws), without synchronising — ef_synchronize reports the same condition for the frames in flight
@@ -1178,6 +1192,10 @@ void ctx_free(ef_ctx* c) {
   if (c->label_stage) (void)hipFree(c->label_stage);
   if (c->label_count_h) (void)hipHostFree(c->label_count_h);
   if (c->label_ev) (void)hipEventDestroy(c->label_ev);
+  if (c->query_sorted) (void)hipFree(c->query_sorted);
+  if (c->query_rows) (void)hipFree(c->query_rows);
+  if (c->query_cells) (void)hipFree(c->query_cells);
+  if (c->query_stage) (void)hipFree(c->query_stage);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
 }
 
@@ -1749,6 +1767,7 @@ int ef_map_upload(ef_ctx* c, const float* surfels, uint32_t count) {
   if (!c || (!surfels && count)) return EF_EINVAL;
   DeviceGuard dg_(c);
   if (count > c->capacity) { c->err = "ef_map_upload: count exceeds max_surfels"; return EF_ECAPACITY; }
+  ++c->map_gen;
   float* tmp = nullptr;
   if (count) {
     EF_HIP(c, hipMalloc((void**)&tmp, (size_t)count * 48));
@@ -1778,6 +1797,7 @@ int ef_get_pose_qt(ef_ctx* c, double* q4_t3) {
 int ef_restore_state(ef_ctx* c, int tick, const double* q4_t3, const uint8_t* rgb_prev, const uint16_t* depth_prev) {
   if (!c || !q4_t3 || !rgb_prev || !depth_prev || tick < 2) return EF_EINVAL;
   DeviceGuard dg_(c);
+  ++c->map_gen;
   hipStream_t s = c->stream;
   const int W = c->cam.cols, H = c->cam.rows;
   if (c->closure) {
@@ -3073,3 +3093,183 @@ int ids_uploaded(ef_ctx* c, uint32_t count) {
   return EF_OK;
 }
 }  // namespace
+
+// ================================================================================================
+// Spatial index and nearest-surfel / kNN queries (include/ef_hip.h; kernels in ef_query.inc)
+// ================================================================================================
+namespace {
+struct QueryCall {
+  const char* fn;
+  const float* points;
+  uint32_t n;
+  int k;
+  float max_dist, min_conf;
+  uint32_t* row;
+  uint32_t* id;
+  float* dist2;
+  float* plane;
+  uint32_t* count;
+};
+// refusals before any GPU work
+int query_check(ef_ctx* c, const QueryCall& q) {
+  std::string& err = c ? c->err : g_create_error;
+  const std::string fn = q.fn;
+  if (q.k < 1 || q.k > 16) { err = fn + ": k must lie in 1 .. 16"; return EF_EINVAL; }
+  if (!(q.max_dist > 0.f) || !std::isfinite(q.max_dist)) { err = fn + ": max_dist must be finite and positive"; return EF_EINVAL; }
+  if (std::isnan(q.min_conf)) { err = fn + ": min_conf is NaN"; return EF_EINVAL; }
+  if (q.n && !q.points) { err = fn + ": null points"; return EF_EINVAL; }
+  if (!q.row) { err = fn + ": null row output"; return EF_EINVAL; }
+  if (!c) { err = fn + ": null context"; return EF_EINVAL; }
+  if (!(q.max_dist / c->query_cell <= (float)EF_QUERY_MAX_RATIO)) {
+    err = fn + ": max_dist / cell must not exceed " + std::to_string(EF_QUERY_MAX_RATIO) + " (ef_set_query_cell)";
+    return EF_EINVAL;
+  }
+  return EF_OK;
+}
+// the index for the current map and cell size: reused while neither has changed, else rebuilt (waits for the device once: the count sizes it)
+int query_index(ef_ctx* c) {
+  if (c->query_gen == c->map_gen && c->query_built_cell == c->query_cell) return EF_OK;
+  uint32_t n = 0;
+  int r = read_count(c, &n);
+  if (r != EF_OK) return r;
+  const uint32_t nb = efm::query_buckets(n);
+  const size_t words = (size_t)nb + 2 * ((size_t)nb / 1024 + 1);
+  if (words > c->query_cells_cap) {
+    if (c->query_cells) { (void)hipFree(c->query_cells); c->query_cells = nullptr; c->query_cells_cap = 0; }
+    EF_HIP(c, hipMalloc((void**)&c->query_cells, words * sizeof(uint32_t)));
+    c->query_cells_cap = words;
+  }
+  if (n > c->query_cap) {
+    if (c->query_sorted) { (void)hipFree(c->query_sorted); c->query_sorted = nullptr; }
+    if (c->query_rows) { (void)hipFree(c->query_rows); c->query_rows = nullptr; }
+    c->query_cap = 0;
+    const size_t cap = std::min((size_t)c->capacity, (size_t)n + (size_t)n / 4 + 1024);
+    EF_HIP(c, hipMalloc((void**)&c->query_sorted, cap * sizeof(float4)));
+    EF_HIP(c, hipMalloc((void**)&c->query_rows, cap * sizeof(uint32_t)));
+    c->query_cap = cap;
+  }
+  c->query_gen = 0;   // nothing valid until the build below is enqueued
+  EF_HIP(c, hipMemsetAsync(c->query_cells, 0, (size_t)nb * sizeof(uint32_t), c->stream));
+  efm::query_build(c->maps[c->cur], n, 1.0f / c->query_cell, nb, c->query_cells, c->query_cells + nb, c->query_sorted, c->query_rows, c->stream);
+  EF_HIP(c, hipGetLastError());
+  c->query_nb = nb;
+  c->query_n = n;
+  c->query_built_cell = c->query_cell;
+  c->query_gen = c->map_gen;
+  return EF_OK;
+}
+// device pointers in q; enqueues only (but for a rebuild)
+int query_enqueue(ef_ctx* c, const QueryCall& q) {
+  int r = capture_check(c, q.fn);
+  if (r != EF_OK) return r;
+  if (q.id) {
+    if (!c->ids_on) { c->err = std::string(q.fn) + ": surfel IDs are off (ef_set_surfel_ids)"; return EF_ESTATE; }
+    r = ids_prepare(c, q.fn);
+    if (r != EF_OK) return r;
+  }
+  if (!q.n) return EF_OK;
+  r = query_index(c);
+  if (r != EF_OK) return r;
+  efm::QueryArgs a{};
+  a.map = c->maps[c->cur];
+  a.sorted = c->query_sorted;
+  a.rows = c->query_rows;
+  a.cells = c->query_cells;
+  a.mask = c->query_nb - 1;
+  a.n_sorted = c->query_n;
+  a.inv_cell = 1.0f / c->query_built_cell;
+  a.points = q.points;
+  a.n = q.n;
+  a.k = q.k;
+  a.max_dist = q.max_dist;
+  a.r2 = q.max_dist * q.max_dist;
+  a.min_conf = q.min_conf;
+  a.row = q.row;
+  a.dist2 = q.dist2;
+  a.id = q.id;
+  a.plane = q.plane;
+  a.count = q.count;
+  efm::query_run(a, q.k, c->query_lanes, c->stream);
+  EF_HIP(c, hipGetLastError());
+  return EF_OK;
+}
+// host pointers in q: staged through query_stage, synchronised
+int query_host(ef_ctx* c, const QueryCall& q) {
+  int r = capture_check(c, q.fn);
+  if (r != EF_OK) return r;
+  const size_t n = q.n, nk = n * (size_t)q.k;
+  const size_t o_pts = 0, o_row = o_pts + n * 12, o_d2 = o_row + nk * 4, o_id = o_d2 + nk * 4, o_pl = o_id + n * 4, o_cnt = o_pl + n * 4;
+  r = grow(c, &c->query_stage, &c->query_stage_bytes, o_cnt + n * 4 + 16, "query staging");
+  if (r != EF_OK) return r;
+  uint8_t* st = c->query_stage;
+  QueryCall d = q;
+  d.points = (const float*)(st + o_pts);
+  d.row = (uint32_t*)(st + o_row);
+  d.dist2 = q.dist2 ? (float*)(st + o_d2) : nullptr;
+  d.id = q.id ? (uint32_t*)(st + o_id) : nullptr;
+  d.plane = q.plane ? (float*)(st + o_pl) : nullptr;
+  d.count = q.count ? (uint32_t*)(st + o_cnt) : nullptr;
+  if (n) EF_HIP(c, hipMemcpyAsync(st + o_pts, q.points, n * 12, hipMemcpyHostToDevice, c->stream));
+  r = query_enqueue(c, d);
+  if (r != EF_OK) return r;
+  if (n) {
+    EF_HIP(c, hipMemcpyAsync(q.row, d.row, nk * 4, hipMemcpyDeviceToHost, c->stream));
+    if (q.dist2) EF_HIP(c, hipMemcpyAsync(q.dist2, d.dist2, nk * 4, hipMemcpyDeviceToHost, c->stream));
+    if (q.id) EF_HIP(c, hipMemcpyAsync(q.id, d.id, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (q.plane) EF_HIP(c, hipMemcpyAsync(q.plane, d.plane, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (q.count) EF_HIP(c, hipMemcpyAsync(q.count, d.count, n * 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  EF_HIP(c, hipStreamSynchronize(c->stream));
+  return EF_OK;
+}
+}  // namespace
+extern "C" {
+
+int ef_set_query_cell(ef_ctx* c, float cell_m) {
+  if (!(cell_m > 0.f) || !std::isfinite(cell_m) || !std::isfinite(1.0f / cell_m)) {
+    (c ? c->err : g_create_error) = "ef_set_query_cell: cell_m must be finite and positive";
+    return EF_EINVAL;
+  }
+  if (!c) { g_create_error = "ef_set_query_cell: null context"; return EF_EINVAL; }
+  c->query_cell = cell_m;
+  return EF_OK;
+}
+int ef_debug_query_lanes(ef_ctx* c, int lanes) {
+  if (!c || (lanes != 0 && lanes != 1 && lanes != 8 && lanes != 16 && lanes != 64)) return EF_EINVAL;
+  c->query_lanes = lanes;
+  return EF_OK;
+}
+int ef_query_nearest_dev(ef_ctx* c, const float* points3, uint32_t n, float max_dist, float min_conf, uint32_t* row, uint32_t* id, float* dist2,
+                         float* plane) {
+  const QueryCall q{"ef_query_nearest_dev", points3, n, 1, max_dist, min_conf, row, id, dist2, plane, nullptr};
+  const int r = query_check(c, q);
+  if (r != EF_OK) return r;
+  DeviceGuard dg_(c);
+  return query_enqueue(c, q);
+}
+int ef_query_nearest(ef_ctx* c, const float* points3, uint32_t n, float max_dist, float min_conf, uint32_t* row, uint32_t* id, float* dist2,
+                     float* plane) {
+  const QueryCall q{"ef_query_nearest", points3, n, 1, max_dist, min_conf, row, id, dist2, plane, nullptr};
+  const int r = query_check(c, q);
+  if (r != EF_OK) return r;
+  DeviceGuard dg_(c);
+  return query_host(c, q);
+}
+int ef_query_knn_dev(ef_ctx* c, const float* points3, uint32_t n, int k, float max_dist, float min_conf, uint32_t* rows, float* dist2,
+                     uint32_t* count) {
+  const QueryCall q{"ef_query_knn_dev", points3, n, k, max_dist, min_conf, rows, nullptr, dist2, nullptr, count};
+  const int r = query_check(c, q);
+  if (r != EF_OK) return r;
+  DeviceGuard dg_(c);
+  return query_enqueue(c, q);
+}
+int ef_query_knn(ef_ctx* c, const float* points3, uint32_t n, int k, float max_dist, float min_conf, uint32_t* rows, float* dist2,
+                 uint32_t* count) {
+  const QueryCall q{"ef_query_knn", points3, n, k, max_dist, min_conf, rows, nullptr, dist2, nullptr, count};
+  const int r = query_check(c, q);
+  if (r != EF_OK) return r;
+  DeviceGuard dg_(c);
+  return query_host(c, q);
+}
+
+}  // extern "C"

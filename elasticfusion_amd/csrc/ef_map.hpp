@@ -207,4 +207,30 @@ void labels_align(const LabelAlign& a, unsigned max_rows, hipStream_t s);
 void labels_fuse(const LabelFuse& f, unsigned max_rows, hipStream_t s);
 void labels_gather(const uint32_t* index, int P, const float* tab, int C, int32_t* label, float* prob, hipStream_t s);
 
+// ---- spatial index and nearest / kNN queries (ef_query.inc; ef_query_nearest / ef_query_knn of include/ef_hip.h) ----
+struct QueryArgs {
+  SurfelSoA map;            // the live map: normal and ID of a winner
+  const float4* sorted;     // the index: {x, y, z, conf} sorted by bucket, rows[] the map row of each record
+  const uint32_t* rows;
+  const uint32_t* cells;    // cells[b]: the END of bucket b in sorted[] (its start is cells[b - 1], 0 for b = 0)
+  unsigned mask;            // buckets - 1 (a power of two)
+  unsigned n_sorted;        // records in the index (0: every query misses)
+  float inv_cell;           // 1 / cell, the float the build used
+  const float* points;      // n x 3
+  unsigned n;
+  int k;                    // slots per query in row / dist2
+  float max_dist, r2, min_conf;
+  uint32_t* row;            // n x k
+  float* dist2;             // n x k or null
+  uint32_t* id;             // n or null (k = 1 only)
+  float* plane;             // n or null (k = 1 only)
+  uint32_t* count;          // n or null
+};
+constexpr int QUERY_MAX_RATIO = 16;   // max_dist / cell the query accepts: its box is at most (2 ratio + 3)^3 cells
+unsigned query_buckets(unsigned n);   // a power of two >= 1024
+void query_build(SurfelSoA map, unsigned n, float inv_cell, unsigned nb, uint32_t* cells, uint32_t* tile_sum, float4* sorted, uint32_t* rows,
+                 hipStream_t s);
+// k 1 .. 16; lanes per query 1, 8 (k = 1: also 16, 64), 0 = the default (16 for k = 1, else 1)
+void query_run(const QueryArgs& a, int k, int lanes, hipStream_t s);
+
 }  // namespace efm

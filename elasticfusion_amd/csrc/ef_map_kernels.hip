@@ -1493,5 +1493,6 @@ void sample_graph(SurfelSoA map, const unsigned* count_dev, int stride, int max_
 
 #include "ef_render.inc"
 #include "ef_labels.inc"
+#include "ef_query.inc"
 
 }  // namespace efm

@@ -455,6 +455,47 @@ int ef_render_labels(ef_ctx* ctx, const ef_render_params* params, int32_t* label
 /* the same with DEVICE pointers, enqueued on the context's stream */
 int ef_render_labels_dev(ef_ctx* ctx, const ef_render_params* params, int32_t* label_dev, float* prob_dev);
 
+/* ---- Spatial index and nearest-surfel / kNN queries: what is near this point?  Off until first used: no query call, nothing allocated,
+ * nothing run, and no frame kernel knows of it.
+ *
+ * Semantics.  All arithmetic is f32, one rounding per operation, no contraction.  For a query point q and the surfel in map row s with
+ * position p, stored normal n (not renormalised) and confidence c:
+ *   d2(q, s)    = ((qx-px)*(qx-px) + (qy-py)*(qy-py)) + (qz-pz)*(qz-pz)
+ *   plane(q, s) = ((qx-px)*nx + (qy-py)*ny) + (qz-pz)*nz
+ *   s is ELIGIBLE iff c > min_conf and d2 <= r2, r2 = max_dist * max_dist computed once in f32 on the host.  Comparisons with NaN are
+ *   false: a surfel with a non-finite position and a query with a non-finite coordinate never match.
+ * Eligible surfels are ordered by (d2, row) ascending: ties go to the lower row.  "Row" is the map row at the time of the call: the row space
+ * of ef_map_download (reference download off), ef_get_surfel_ids and the index image of ef_render_model.  The answer is, bit for bit, that of
+ * an exhaustive scan over all rows, for any cell size: the grid only selects candidates.
+ *
+ * min_conf: a negative value for every surfel, the context's confidence threshold for stable surfels only; NaN is refused.
+ * A miss is row 0xFFFFFFFF, id 0, dist2 +inf, plane 0.  n = 0 and an empty map are valid (all misses).
+ * EF_EINVAL, before any GPU work: a NULL context or required pointer, n > 0 with NULL points3, k outside 1 .. 16, max_dist or cell_m not finite
+ * and positive (or cell_m so small that 1 / cell_m is not finite), NaN min_conf, max_dist / cell above EF_QUERY_MAX_RATIO (a query visits
+ * the cells its ball's bounding box overlaps, about (2 max_dist / cell + 1)^3).
+ * EF_ESTATE: the context's stream is being captured; id asked for while surfel IDs are off.
+ *
+ * The index is built on demand, on the context's stream behind earlier frames, and reused until a call that can change the map
+ * (ef_process_frame*, ef_map_upload, ef_restore_state) or another cell size makes it stale.  Host variants stage their arrays and synchronise.
+ * The _dev variants take DEVICE pointers and only enqueue, except that a call which has to rebuild the index first waits for the device once
+ * (the map count sizes the index). */
+#define EF_QUERY_MAX_RATIO 16
+#define EF_QUERY_DEFAULT_CELL 0.02f
+/* the grid's cell edge in metres (> 0, finite; default EF_QUERY_DEFAULT_CELL, chosen by measurement: profiles/r12_query_kernel_times.txt) */
+int ef_set_query_cell(ef_ctx* ctx, float cell_m);
+/* per point (points3: n x 3 floats) the first eligible surfel: row[n]; id (needs ef_set_surfel_ids on; new rows are numbered first), dist2 and
+ * plane may be NULL */
+int ef_query_nearest(ef_ctx* ctx, const float* points3, uint32_t n, float max_dist, float min_conf, uint32_t* row, uint32_t* id_or_null,
+                     float* dist2_or_null, float* plane_or_null);
+/* per point the first min(k, eligible) surfels in (d2, row) order: rows[n * k], dist2[n * k] (unused slots filled as a miss); count[n] is the
+ * number of ALL eligible surfels, which may exceed k (the radius count of density / outlier filters) */
+int ef_query_knn(ef_ctx* ctx, const float* points3, uint32_t n, int k, float max_dist, float min_conf, uint32_t* rows, float* dist2_or_null,
+                 uint32_t* count_or_null);
+int ef_query_nearest_dev(ef_ctx* ctx, const float* points3_dev, uint32_t n, float max_dist, float min_conf, uint32_t* row_dev,
+                         uint32_t* id_dev_or_null, float* dist2_dev_or_null, float* plane_dev_or_null);
+int ef_query_knn_dev(ef_ctx* ctx, const float* points3_dev, uint32_t n, int k, float max_dist, float min_conf, uint32_t* rows_dev,
+                     float* dist2_dev_or_null, uint32_t* count_dev_or_null);
+
 /* named internal images, copied to HOST (synchronises); for tests and for a front-end's drawing code */
 enum ef_image {
   EF_IMG_DEPTH_FILTERED = 0,      /* u16  */
@@ -515,6 +556,9 @@ int ef_get_tracker_timing(ef_ctx* ctx, ef_kernel_time* out);
 int ef_get_tracker_fallbacks(ef_ctx* ctx, int* count);
 /* developer instrumentation for the test of that path: `workgroups` workgroups that each fill one CU spin for `microseconds` on a stream of their own */
 int ef_debug_occupy(ef_ctx* ctx, int workgroups, int microseconds);
+/* developer instrumentation: lanes that share one query of ef_query_nearest / ef_query_knn (1, 8; nearest also 16, 64; 0 = the default: 16 for nearest, 1 for kNN).  Results do not
+ * depend on it; tools/query_times.py measures the choices */
+int ef_debug_query_lanes(ef_ctx* ctx, int lanes);
 /* test hook: raises the sticky "a persistent tracker launch gave up waiting" flag of the frame tracker, as a wait that timed out after admission
  * would.  From then on every persistent launch of the context returns at once; the frame whose tracker saw the flag hands it to the host, the
  * NEXT ef_process_frame[_dev] (class ElasticFusion::processFrame: throws) returns EF_EHIP without having enqueued anything, and so does
