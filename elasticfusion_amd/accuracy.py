@@ -7,7 +7,10 @@ host from the two rows' own floats.
 
 Each side reports, over the points that found a partner within max_dist: mean, median and RMS of the distance and of the absolute distance
 along the partner's normal (point to plane), and the share of points that found none.  The ground truth lives in a second context
-(ef_map_upload); neither the oracle nor any reference checkout is read."""
+(ef_map_upload); neither the oracle nor any reference checkout is read.
+
+A ground truth that is not in the map's world frame (another dataset's model, a second session, a scan) is first placed there by
+point-to-plane ICP against the map (register_to_map over ef_register_cloud; map_accuracy(align=True))."""
 from __future__ import annotations
 
 import numpy as np
@@ -33,11 +36,55 @@ def _figures(points: np.ndarray, rows: np.ndarray, target: np.ndarray) -> dict:
     return out
 
 
-def map_accuracy(ef: "api.ElasticFusion", gt_surfels: np.ndarray, max_dist: float = 0.05, map_rows=None, gt_rows=None, device: int = 0) -> dict:
-    """ef: a context with a map; gt_surfels: [m, 12] float32 in the map's world frame, laid out as downloadMap() gives them (synth.sample_surfels).
-    map_rows / gt_rows: optional row subsets to ask from (map rows that are not stable are dropped); partners are always sought in the whole
-    other side.  Returns {"accuracy": {...}, "completeness": {...}, "max_dist", "stable", "map_count"}."""
+REGISTER_SCHEDULE = (0.10, 0.05, 0.025)   # max_dist per stage, coarse to fine; each at most EF_QUERY_MAX_RATIO cells of the index
+
+
+def move_surfels(surfels: np.ndarray, T: np.ndarray) -> np.ndarray:
+    """[m, 12] surfels moved by the rigid 4 x 4 T: positions by T, normals by its rotation block (float64, rounded to float32 once)"""
+    out = np.array(surfels, np.float32).reshape(-1, 12)
+    T = np.asarray(T, np.float64)
+    out[:, :3] = out[:, :3].astype(np.float64) @ T[:3, :3].T + T[:3, 3]
+    out[:, 8:11] = out[:, 8:11].astype(np.float64) @ T[:3, :3].T
+    return out
+
+
+def register_to_map(ef: "api.ElasticFusion", surfels_or_points: np.ndarray, T_init=None, schedule=REGISTER_SCHEDULE, min_conf: float | None = None,
+                    use_normals: bool = True, **params) -> tuple:
+    """Point-to-plane ICP (ef_register_cloud) of a cloud against ef's map on a coarse-to-fine schedule of max_dist, each stage starting from
+    the last stage's pose.  surfels_or_points: [m, 12] surfels (positions, and normals unless use_normals is off) or [m, 3] points, in their
+    own frame.  min_conf None = the context's confidence threshold (stable surfels only); other keywords are ef_register_params fields.
+    Returns (T 4 x 4 float64 cloud -> map, [per-stage result dicts with "max_dist" added]).  A stage that ends TOO_FEW_PAIRS or DEGENERATE
+    leaves the pose where it was and the later, finer stages are not run."""
+    a = np.asarray(surfels_or_points, np.float32)
+    assert a.ndim == 2 and a.shape[1] in (3, 12), a.shape
+    pts = np.ascontiguousarray(a[:, :3])
+    nrm = np.ascontiguousarray(a[:, 8:11]) if a.shape[1] == 12 and use_normals else None
+    T = np.eye(4) if T_init is None else np.array(T_init, np.float64).reshape(4, 4)
+    if min_conf is None:
+        min_conf = float(ef.cfg.confidence)
+    stages = []
+    for md in schedule:
+        T, res = ef.registerCloud(pts, nrm, T_init=T, max_dist=float(md), min_conf=float(min_conf), **params)
+        res["max_dist"] = float(md)
+        stages.append(res)
+        if res["status"] in (api.REG_TOO_FEW_PAIRS, api.REG_DEGENERATE):
+            break
+    return T, stages
+
+
+def map_accuracy(ef: "api.ElasticFusion", gt_surfels: np.ndarray, max_dist: float = 0.05, map_rows=None, gt_rows=None, device: int = 0,
+                 align: bool = False, align_schedule=REGISTER_SCHEDULE) -> dict:
+    """ef: a context with a map; gt_surfels: [m, 12] float32, laid out as downloadMap() gives them (synth.sample_surfels), in the map's world
+    frame unless align is set.  map_rows / gt_rows: optional row subsets to ask from (map rows that are not stable are dropped); partners are
+    always sought in the whole other side.  align: the ground truth is first registered to the map's stable surfels (register_to_map with its
+    positions and normals, the established protocol for a model made elsewhere) and moved by the result; the figures are then taken as
+    without it.  Returns {"accuracy": {...}, "completeness": {...}, "max_dist", "stable", "map_count"[, "align": {"T", "stages"}]}."""
     gt = np.ascontiguousarray(gt_surfels, np.float32).reshape(-1, 12)
+    aligned = None
+    if align:
+        T, stages = register_to_map(ef, gt, schedule=align_schedule)
+        gt = move_surfels(gt, T)
+        aligned = {"T": T.tolist(), "stages": [{k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in st.items()} for st in stages]}
     surfels = ef.downloadMap()
     thresh = float(ef.cfg.confidence)
     rows = np.arange(len(surfels)) if map_rows is None else np.asarray(map_rows, np.int64)
@@ -51,8 +98,11 @@ def map_accuracy(ef: "api.ElasticFusion", gt_surfels: np.ndarray, max_dist: floa
         truth.close()
     gt_pts = np.ascontiguousarray(gt[:, :3] if gt_rows is None else gt[np.asarray(gt_rows, np.int64), :3])
     com_rows = ef.queryNearest(gt_pts, max_dist, thresh)[0]
-    return {"accuracy": _figures(map_pts, acc_rows, gt), "completeness": _figures(gt_pts, com_rows, surfels), "max_dist": float(max_dist),
-            "stable": int((surfels[:, 3] > np.float32(thresh)).sum()), "map_count": int(len(surfels))}
+    rep = {"accuracy": _figures(map_pts, acc_rows, gt), "completeness": _figures(gt_pts, com_rows, surfels), "max_dist": float(max_dist),
+           "stable": int((surfels[:, 3] > np.float32(thresh)).sum()), "map_count": int(len(surfels))}
+    if aligned is not None:
+        rep["align"] = aligned
+    return rep
 
 
 def format_report(r: dict) -> str:
@@ -62,4 +112,10 @@ def format_report(r: dict) -> str:
         lines.append(f"{side:12s} points {f['points']} hits {f['hits']} miss share {f['miss_share']:.4f}  "
                      f"dist mean {f['dist_mean'] * 1e3:.3f} median {f['dist_median'] * 1e3:.3f} rms {f['dist_rms'] * 1e3:.3f} mm  "
                      f"|plane| mean {f['plane_mean'] * 1e3:.3f} median {f['plane_median'] * 1e3:.3f} rms {f['plane_rms'] * 1e3:.3f} mm")
+    if "align" in r:
+        T = np.asarray(r["align"]["T"], np.float64)
+        ang = float(np.arccos(np.clip((np.trace(T[:3, :3]) - 1) / 2, -1, 1)))
+        lines.append(f"aligned first: translation {np.linalg.norm(T[:3, 3]) * 1e3:.3f} mm, rotation {np.degrees(ang):.4f} deg; stages " +
+                     ", ".join(f"{st['max_dist']:.3f} m: {st['status_name']} after {st['iterations']} ({st['pairs']} pairs, rms "
+                               f"{st['rms_first'] * 1e3:.3f} -> {st['rms_last'] * 1e3:.3f} mm)" for st in r["align"]["stages"]))
     return "\n".join(lines)

@@ -52,6 +52,61 @@ class ef_render_params(C.Structure):
                 ("time", c_i), ("time_delta", c_i)]
 
 
+class ef_register_params(C.Structure):
+    _fields_ = [("max_dist", c_f), ("min_conf", c_f), ("min_normal_cos", c_f), ("max_iterations", c_i), ("min_pairs", c_i),
+                ("stop_translation", C.c_double), ("stop_rotation", C.c_double)]
+
+
+class ef_register_sums(C.Structure):
+    _fields_ = [("A", C.c_double * 36), ("b", C.c_double * 6), ("e", C.c_double), ("pairs", c_u32), ("points", c_u32)]
+
+
+class ef_register_result(C.Structure):
+    _fields_ = [("status", c_i), ("iterations", c_i), ("pairs", c_u32), ("rms_first", C.c_double), ("rms_last", C.c_double),
+                ("A", C.c_double * 36)]
+
+
+REG_CONVERGED, REG_MAX_ITERATIONS, REG_TOO_FEW_PAIRS, REG_DEGENERATE = 0, 1, 2, 3   # EF_REG_* of include/ef_hip.h
+REG_STATUS = {REG_CONVERGED: "CONVERGED", REG_MAX_ITERATIONS: "MAX_ITERATIONS", REG_TOO_FEW_PAIRS: "TOO_FEW_PAIRS", REG_DEGENERATE: "DEGENERATE"}
+
+
+def _sums_dict(s: ef_register_sums) -> dict:
+    return {"A": np.array(s.A, np.float64).reshape(6, 6), "b": np.array(s.b, np.float64), "e": float(s.e), "pairs": int(s.pairs),
+            "points": int(s.points)}
+
+
+def _sums_struct(sums) -> ef_register_sums:
+    if isinstance(sums, ef_register_sums):
+        return sums
+    s = ef_register_sums()
+    s.A[:] = np.ascontiguousarray(sums["A"], np.float64).reshape(36).tolist()
+    s.b[:] = np.ascontiguousarray(sums["b"], np.float64).reshape(6).tolist()
+    s.e = float(sums.get("e", 0.0))
+    s.pairs = int(sums.get("pairs", 0))
+    s.points = int(sums.get("points", 0))
+    return s
+
+
+def _pose16(T):
+    if T is None:
+        return None, None
+    a = np.ascontiguousarray(T, np.float64).reshape(16)
+    return a, _ptr(a)
+
+
+def register_update(sums, T=None):
+    """ef_register_update (plain double on the host: needs neither a context nor a GPU): solves A xi = b and returns
+    (exp(xi) T as 4 x 4 float64, xi, degenerate); sums is what registerStep returns (or any dict with "A" 6 x 6 and "b" 6)."""
+    s = _sums_struct(sums)
+    keep, pT = _pose16(T)
+    out = np.zeros(16, np.float64)
+    xi = np.zeros(6, np.float64)
+    rc = lib().ef_register_update(C.byref(s), pT, _ptr(out), _ptr(xi))
+    if rc not in (0, REG_DEGENERATE):
+        _chk(rc)
+    return out.reshape(4, 4), xi, rc == REG_DEGENERATE
+
+
 DATATERM = np.dtype([("zero", np.int16, 2), ("one", np.int16, 2), ("diff", np.float32), ("valid", np.uint8),
                      ("pad", np.uint8, 3)])
 
@@ -895,6 +950,88 @@ class ElasticFusion:
         """ef_query_knn_dev: raw device pointers (int, c_void_p or None), enqueued on the context's stream"""
         args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (points_dev, rows, dist2, count)]
         _chk(lib().ef_query_knn_dev(self.h, args[0], c_u32(n), c_i(int(k)), c_f(max_dist), c_f(min_conf), *args[1:]), self.h)
+
+    # --- rigid registration of a point set against the map (ef_register_step / ef_register_cloud) ---
+    def registerParams(self, **kw) -> ef_register_params:
+        """ef_default_register_params with fields replaced by keyword"""
+        p = ef_register_params()
+        _chk(lib().ef_default_register_params(self.h, C.byref(p)), self.h)
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise TypeError(f"unknown registration parameter {k}")
+            setattr(p, k, v)
+        return p
+
+    def _registerArgs(self, points, normals, params, kw):
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        assert nrm is None or len(nrm) == len(pts), (len(pts), len(nrm))
+        if params is None:
+            params = self.registerParams(**kw)
+        else:
+            assert not kw, "give params or keywords, not both"
+        return pts, nrm, params
+
+    def registerStep(self, points, normals=None, T=None, params: ef_register_params | None = None, pairs: bool = False, **kw):
+        """one point-to-plane step of the cloud (n x 3, optional normals n x 3) at pose T (4 x 4, cloud -> world; None = identity):
+        {"A" 6 x 6, "b", "e", "pairs", "points"[, "row" uint32 n, "plane" float32 n with pairs=True]}, all float64 sums of the device"""
+        pts, nrm, params = self._registerArgs(points, normals, params, kw)
+        n = len(pts)
+        keep, pT = _pose16(T)
+        s = ef_register_sums()
+        row = np.zeros(max(n, 1), np.uint32) if pairs else None
+        plane = np.zeros(max(n, 1), np.float32) if pairs else None
+        _chk(lib().ef_register_step(self.h, _ptr(pts), None if nrm is None else _ptr(nrm), c_u32(n), C.byref(params), pT, C.byref(s),
+                                    None if row is None else _ptr(row), None if plane is None else _ptr(plane)), self.h)
+        out = _sums_dict(s)
+        if pairs:
+            out["row"], out["plane"] = row[:n], plane[:n]
+        return out
+
+    @staticmethod
+    def _registerResult(r: ef_register_result) -> dict:
+        return {"status": int(r.status), "status_name": REG_STATUS.get(int(r.status), "?"), "iterations": int(r.iterations),
+                "pairs": int(r.pairs), "rms_first": float(r.rms_first), "rms_last": float(r.rms_last),
+                "A": np.array(r.A, np.float64).reshape(6, 6)}
+
+    def registerCloud(self, points, normals=None, T_init=None, params: ef_register_params | None = None, pairs: bool = False, **kw):
+        """point-to-plane ICP of the cloud against the map from T_init (None = identity): (T 4 x 4 float64, result dict with "status",
+        "iterations", "pairs", "rms_first", "rms_last", "A"[, "row", "plane" at the returned pose with pairs=True])"""
+        pts, nrm, params = self._registerArgs(points, normals, params, kw)
+        n = len(pts)
+        keep, pT = _pose16(T_init)
+        T = np.zeros(16, np.float64)
+        res = ef_register_result()
+        row = np.zeros(max(n, 1), np.uint32) if pairs else None
+        plane = np.zeros(max(n, 1), np.float32) if pairs else None
+        _chk(lib().ef_register_cloud(self.h, _ptr(pts), None if nrm is None else _ptr(nrm), c_u32(n), C.byref(params), pT, _ptr(T),
+                                     C.byref(res), None if row is None else _ptr(row), None if plane is None else _ptr(plane)), self.h)
+        out = self._registerResult(res)
+        if pairs:
+            out["row"], out["plane"] = row[:n], plane[:n]
+        return T.reshape(4, 4), out
+
+    def registerStepDevice(self, points_dev, n: int, normals_dev=None, T=None, params: ef_register_params | None = None, row=None, plane=None,
+                           **kw):
+        """ef_register_step_dev: raw device pointers (int, c_void_p or None) for points / normals / row / plane; waits for the sums"""
+        params = params if params is not None else self.registerParams(**kw)
+        args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (points_dev, normals_dev, row, plane)]
+        keep, pT = _pose16(T)
+        s = ef_register_sums()
+        _chk(lib().ef_register_step_dev(self.h, args[0], args[1], c_u32(n), C.byref(params), pT, C.byref(s), args[2], args[3]), self.h)
+        return _sums_dict(s)
+
+    def registerCloudDevice(self, points_dev, n: int, normals_dev=None, T_init=None, params: ef_register_params | None = None, row=None,
+                            plane=None, **kw):
+        """ef_register_cloud_dev: raw device pointers (int, c_void_p or None) for points / normals / row / plane"""
+        params = params if params is not None else self.registerParams(**kw)
+        args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (points_dev, normals_dev, row, plane)]
+        keep, pT = _pose16(T_init)
+        T = np.zeros(16, np.float64)
+        res = ef_register_result()
+        _chk(lib().ef_register_cloud_dev(self.h, args[0], args[1], c_u32(n), C.byref(params), pT, _ptr(T), C.byref(res), args[2], args[3]),
+             self.h)
+        return T.reshape(4, 4), self._registerResult(res)
 
     def setReferenceDownload(self, on=True):
         """downloadMap / savePly read what GlobalModel::downloadMap reads (the pre-clean buffer, quirk Q14) instead of model()"""

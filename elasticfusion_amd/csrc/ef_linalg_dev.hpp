@@ -173,6 +173,39 @@ EFL_HD void ldlt_solve(const T* A_in, const T* b_in, T* x) {
   }
 }
 
+// The N pivots ldlt_solve<T, N> divides by for the same A (the same operations in the same order, so the same bits), in elimination order.
+// For callers that must refuse a matrix that is not positive definite; plain loops: it is not on any kernel's hot path.
+template <typename T, int N>
+EFL_HD void ldlt_pivots(const T* A_in, T* d_out) {
+  T A[N][N];
+  for (int i = 0; i < N; ++i)
+    for (int j = 0; j < N; ++j) A[i][j] = A_in[i * N + j];
+  for (int k = 0; k < N; ++k) {
+    int p = k;
+    T best = fabs(A[k][k]);
+    for (int i = k + 1; i < N; ++i) {
+      const T v = fabs(A[i][i]);
+      if (v > best) { best = v; p = i; }
+    }
+    if (p != k) {
+      for (int j = 0; j < N; ++j) { const T x = A[k][j]; A[k][j] = A[p][j]; A[p][j] = x; }
+      for (int r = 0; r < N; ++r) { const T x = A[r][k]; A[r][k] = A[r][p]; A[r][p] = x; }
+    }
+    const T d = A[k][k];
+    d_out[k] = d;
+    if (d == T(0)) continue;
+    T colk[N];
+    for (int i = k + 1; i < N; ++i) colk[i] = A[i][k];
+    for (int i = k + 1; i < N; ++i) {
+      const T l = colk[i] / d;
+      for (int j = k + 1; j <= i; ++j) {
+        A[i][j] = A[i][j] - l * colk[j];
+        A[j][i] = A[i][j];
+      }
+    }
+  }
+}
+
 // OdometryProvider::rodrigues
 EFL_HD void rodrigues(const double* src, double* dst) {
   m3_identity(dst);

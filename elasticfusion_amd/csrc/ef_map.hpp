@@ -233,4 +233,23 @@ void query_build(SurfelSoA map, unsigned n, float inv_cell, unsigned nb, uint32_
 // k 1 .. 16; lanes per query 1, 8 (k = 1: also 16, 64), 0 = the default (16 for k = 1, else 1)
 void query_run(const QueryArgs& a, int k, int lanes, hipStream_t s);
 
+// ---- point-to-plane registration of a point set against the map (ef_register.inc; ef_register_step / ef_register_cloud of include/ef_hip.h) ----
+constexpr int REGISTER_SLOTS = 32;          // doubles per slab: 21 upper-triangle entries of A (row-major), 6 of b, e, pairs, 3 unused
+// Slabs (= workgroups) of one step at most: 6 per CU, so that every wave of the launch is resident at once (the kernel fits 7 waves per SIMD).
+// A group's points are assigned statically (the order of the sums must not depend on timing), so workgroups that have to wait for a slot run
+// behind a chip that is already draining: 2048 took 1.29 times as long as 1536 at 1 M points, 1792 1.37, 1024 1.18 times
+// (profiles/r13_register_kernel_times.txt).
+constexpr int REGISTER_MAX_BLOCKS = 1536;
+struct RegisterArgs {
+  QueryArgs q;              // the index, the radius and min_conf; q.points = the cloud (n x 3), q.row / q.plane = per-point outputs or null
+  const float* normals;     // n x 3 or null
+  float R[9], t[3];         // the pose rounded to f32 once (row-major rotation block, translation)
+  float min_normal_cos;
+  int gate;                 // the normal gate is on (normals given and min_normal_cos > -1)
+  double* slabs;            // REGISTER_MAX_BLOCKS x REGISTER_SLOTS
+  double* sums;             // REGISTER_SLOTS: the fixed-order sum of the slabs
+};
+unsigned register_blocks(unsigned n);   // workgroups (= slabs) of a step over n points: a function of n alone
+void register_step(const RegisterArgs& a, hipStream_t s);
+
 }  // namespace efm

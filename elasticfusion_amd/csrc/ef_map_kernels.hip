@@ -1494,5 +1494,6 @@ void sample_graph(SurfelSoA map, const unsigned* count_dev, int stride, int max_
 #include "ef_render.inc"
 #include "ef_labels.inc"
 #include "ef_query.inc"
+#include "ef_register.inc"
 
 }  // namespace efm

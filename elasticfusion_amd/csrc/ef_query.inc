@@ -67,27 +67,13 @@ __global__ void __launch_bounds__(BLK) k_query_scatter(const float4* __restrict_
 
 __device__ __forceinline__ bool query_less(float da, unsigned ra, float db, unsigned rb) { return da < db || (da == db && ra < rb); }
 
-// L lanes share a query: lane l of the group visits cells l, l + L, ... of the query's box (flattened z fastest) and keeps its own K best as
-// sorted (d2, row) keys in registers (K is a template parameter: every index below is a compile-time constant, nothing spills).  The group's
-// lists are then merged K times by a butterfly minimum on the key; the lane that owns the winner pops it.  Rows are unique across the group
-// because a surfel is only ever accepted in the visit of its own cell.
+// The cell walk of one lane: lane `sub` of the L that share the query q visits cells sub, sub + L, ... of the query's box (flattened z fastest)
+// and keeps its own K best as sorted (d2, row) keys in bd / br (initialised by the caller), counting every eligible surfel in cnt.  Shared by
+// k_query and k_register (ef_register.inc): the argument below is the only proof that no eligible surfel is missed.
 template <int L, int K>
-__global__ void __launch_bounds__(BLK) k_query(const QueryArgs A) {
-  const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
-  const unsigned qi = t / L, sub = t % L;
-  const bool live = qi < A.n;
-  float qx = 0.f, qy = 0.f, qz = 0.f;
-  if (live) {
-    qx = A.points[(size_t)qi * 3];
-    qy = A.points[(size_t)qi * 3 + 1];
-    qz = A.points[(size_t)qi * 3 + 2];
-  }
-  float bd[K];
-  unsigned br[K];
-#pragma unroll
-  for (int j = 0; j < K; ++j) { bd[j] = __builtin_inff(); br[j] = QUERY_NONE; }
-  unsigned cnt = 0;
-  if (live && A.n_sorted && query_finite3(qx, qy, qz)) {
+__device__ __forceinline__ void query_walk(const QueryArgs& A, float qx, float qy, float qz, unsigned sub, float (&bd)[K], unsigned (&br)[K],
+                                           unsigned& cnt) {
+  if (A.n_sorted && query_finite3(qx, qy, qz)) {
     // The box: the cells of q -+ rw, rw = max_dist widened by 2^-21 of (max_dist + |q|) per axis.  It cannot miss an eligible surfel p:
     //   d2 <= r2 is decided in f32.  Adding non-negative terms never rounds below a term, so fl(fl(qx-px)^2) <= d2 <= r2 <= max_dist^2 (1+u),
     //   u = 2^-24, hence |qx - px| <= max_dist (1 + 2.1 u) in exact arithmetic (products that underflow: |qx - px| < 1e-18, the last term of rw);
@@ -130,6 +116,29 @@ __global__ void __launch_bounds__(BLK) k_query(const QueryArgs A) {
       }
     }
   }
+}
+
+// L lanes share a query: every lane walks its share of the box (query_walk) and keeps its own K best in registers (K is a template parameter:
+// every index is a compile-time constant, nothing spills).  The group's
+// lists are then merged K times by a butterfly minimum on the key; the lane that owns the winner pops it.  Rows are unique across the group
+// because a surfel is only ever accepted in the visit of its own cell.
+template <int L, int K>
+__global__ void __launch_bounds__(BLK) k_query(const QueryArgs A) {
+  const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned qi = t / L, sub = t % L;
+  const bool live = qi < A.n;
+  float qx = 0.f, qy = 0.f, qz = 0.f;
+  if (live) {
+    qx = A.points[(size_t)qi * 3];
+    qy = A.points[(size_t)qi * 3 + 1];
+    qz = A.points[(size_t)qi * 3 + 2];
+  }
+  float bd[K];
+  unsigned br[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) { bd[j] = __builtin_inff(); br[j] = QUERY_NONE; }
+  unsigned cnt = 0;
+  if (live) query_walk<L, K>(A, qx, qy, qz, sub, bd, br, cnt);
   // merge the group's lists (every lane of the wave takes part in the shuffles, live or not)
   if (L > 1) {
 #pragma unroll

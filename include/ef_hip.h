@@ -496,6 +496,97 @@ int ef_query_nearest_dev(ef_ctx* ctx, const float* points3_dev, uint32_t n, floa
 int ef_query_knn_dev(ef_ctx* ctx, const float* points3_dev, uint32_t n, int k, float max_dist, float min_conf, uint32_t* rows_dev,
                      float* dist2_dev_or_null, uint32_t* count_dev_or_null);
 
+/* ---- Rigid registration of a point set against the map: point-to-plane ICP on the spatial index above.  Off until first used: no register
+ * call, nothing allocated, nothing run, and no frame kernel knows of it.
+ *
+ * T (row-major 4 x 4 double like every other pose here; NULL where allowed = identity) maps the cloud's frame into the map's world frame.
+ *
+ * ONE STEP (ef_register_step).  Rf, tf are T's rotation block and translation rounded to f32 once.  All per-point arithmetic is f32, one
+ * rounding per operation, no contraction, in the written order.  For a point (x, y, z) with optional normal m:
+ *   p'x = ((Rf00*x + Rf01*y) + Rf02*z) + tfx, likewise y, z;   m'x = (Rf00*mx + Rf01*my) + Rf02*mz, likewise y, z
+ *   s   = the surfel ef_query_nearest returns for p' with max_dist, min_conf: the same eligibility, the same (d2, row) order, the same
+ *         treatment of non-finite input.  A miss contributes nothing.
+ *   normal gate, only with normals and min_normal_cos > -1: the pair is kept iff ((m'x*nx + m'y*ny) + m'z*nz) >= min_normal_cos, n the
+ *         stored normal, not renormalised; a NaN fails the comparison and drops the pair.
+ *   r   = plane(p', s) as the query defines it;   J = (nx, ny, nz, p'y*nz - p'z*ny, p'z*nx - p'x*nz, p'x*ny - p'y*nx) in f32
+ *   the seven numbers are widened to double;  A += J^T J,  b -= J^T r,  e += r*r,  pairs += 1  in double.  Every product of two widened f32
+ *   values is exact in double; the order of the sums is fixed by n alone (never by the index's cell size, never by timing: no
+ *   floating-point atomics), so a step is reproducible bit for bit.  A is returned full and symmetric bit for bit.  points = n.
+ *   row / plane (optional, n each) receive the pair that was used, or a miss as the query writes it (row 0xFFFFFFFF, plane 0); a pair the
+ *   normal gate dropped is reported as a miss.
+ *
+ * UPDATE (ef_register_update; plain double on the host, needs neither a context nor a GPU; ef_register_cloud calls this very function).
+ * Solves A xi = b by the library's 6 x 6 LDL^T with diagonal pivoting; xi = (translation, rotation) is a twist applied in the world frame.
+ * T_out = exp(xi) * T (left multiplication), exp the SE(3) exponential: with th = |xi_w|, W = [xi_w]x,
+ *   R = I + a W + b W^2,  V = I + b W + c W^2,  exp(xi) = [R, V xi_t; 0, 1],  a = sin th / th,  b = (1 - cos th) / th^2,  c = (1 - a) / th^2,
+ *   and below th = EF_REGISTER_SMALL_ANGLE the series a = 1 - th^2/6, b = 1/2 - th^2/24, c = 1/6 - th^2/120 (their error there is under 1e-18).
+ * The rotation block of the product is left as computed: it is not re-orthonormalised (its drift over EF_REGISTER_MAX_ITERATIONS updates is
+ * of the order of 1e-14).  T_out's last row is 0 0 0 1.  Returns EF_OK, or EF_REG_DEGENERATE (T_out = T, xi = 0) when a pivot of the
+ * factorisation is not finite and positive or xi is not finite, or EF_EINVAL for a NULL pointer or a non-finite entry of T.
+ * A solution xi = 0 (b = 0 with a positive definite A) returns T itself, every entry bit for bit, without forming the product.
+ *
+ * THE LOOP (ef_register_cloud) is step, stop tests, update, in that order:
+ *   pairs < min_pairs -> EF_REG_TOO_FEW_PAIRS with the pose reached so far;  a degenerate update -> EF_REG_DEGENERATE likewise;
+ *   after an update whose |xi_t| < stop_translation and |xi_w| < stop_rotation -> one more step at the new pose for pairs / rms_last / A
+ *   -> EF_REG_CONVERGED;  max_iterations updates -> the same closing step -> EF_REG_MAX_ITERATIONS.
+ * status is information: the return value stays EF_OK.  rms = sqrt(e / pairs), 0 without pairs.  row / plane are those of the last step, which
+ * is always taken at the returned pose.  Each iteration reads 29 doubles back (profiles/r13_register_kernel_times.txt).
+ *
+ * Defaults (ef_default_register_params): max_dist 0.05 m, min_conf = the context's confidence threshold (stable surfels; negative = every
+ * surfel), min_normal_cos 0.5, max_iterations 30, min_pairs 32, stop_translation 1e-6 m, stop_rotation 1e-6 rad.  The stop bounds sit an order
+ * of magnitude above the floor the f32 transform of the points sets on a room-sized cloud (updates of the order of 1e-7 m / 1e-7 rad once
+ * converged, profiles/r13_register_accuracy.txt): lower bounds would never report EF_REG_CONVERGED.
+ *
+ * EF_EINVAL, before any GPU work: a NULL context, params, T_out / result / out, n > 0 with NULL points3; max_dist, min_conf and the ratio to
+ * the cell as ef_query_nearest refuses them; NaN min_normal_cos; max_iterations outside 1 .. EF_REGISTER_MAX_ITERATIONS; min_pairs < 6; a
+ * stop bound that is negative or not finite; a non-finite entry of T.  EF_ESTATE while the context's stream is captured.  n = 0 and an empty
+ * map are valid (EF_REG_TOO_FEW_PAIRS, T_out = T_init).  The index is the query's own: built on demand, reused, made stale by the same
+ * calls.  Host variants stage their arrays and synchronise; the _dev variants take DEVICE pointers for points / normals / row / plane
+ * (out, T_out and result stay HOST pointers) and synchronise too, because the sums are read back. */
+#define EF_REGISTER_MAX_ITERATIONS 100
+#define EF_REGISTER_SMALL_ANGLE 1e-4
+#define EF_REG_CONVERGED 0
+#define EF_REG_MAX_ITERATIONS 1
+#define EF_REG_TOO_FEW_PAIRS 2
+#define EF_REG_DEGENERATE 3
+typedef struct ef_register_params {
+  float max_dist;          /* correspondence radius in metres */
+  float min_conf;          /* as ef_query_nearest */
+  float min_normal_cos;    /* used only when normals are given; <= -1 switches the gate off */
+  int max_iterations;      /* 1 .. EF_REGISTER_MAX_ITERATIONS */
+  int min_pairs;           /* >= 6 */
+  double stop_translation; /* metres */
+  double stop_rotation;    /* radians */
+} ef_register_params;
+typedef struct ef_register_sums {
+  double A[36];            /* row-major, symmetric */
+  double b[6];
+  double e;
+  uint32_t pairs;
+  uint32_t points;
+} ef_register_sums;
+typedef struct ef_register_result {
+  int status;              /* EF_REG_* */
+  int iterations;          /* updates applied */
+  uint32_t pairs;          /* at the returned pose */
+  double rms_first;        /* sqrt(e / pairs) at T_init */
+  double rms_last;         /* ... and at the returned pose */
+  double A[36];            /* the normal matrix at the returned pose: how well each direction of motion is held */
+} ef_register_result;
+int ef_default_register_params(ef_ctx* ctx, ef_register_params* params);
+int ef_register_step(ef_ctx* ctx, const float* points3, const float* normals3_or_null, uint32_t n, const ef_register_params* params,
+                     const double* T16_or_null, ef_register_sums* out, uint32_t* row_or_null, float* plane_or_null);
+int ef_register_update(const ef_register_sums* sums, const double* T16_or_null, double* T16_out, double* xi6_or_null);
+int ef_register_cloud(ef_ctx* ctx, const float* points3, const float* normals3_or_null, uint32_t n, const ef_register_params* params,
+                      const double* T_init16_or_null, double* T_out16, ef_register_result* result, uint32_t* row_or_null,
+                      float* plane_or_null);
+int ef_register_step_dev(ef_ctx* ctx, const float* points3_dev, const float* normals3_dev_or_null, uint32_t n,
+                         const ef_register_params* params, const double* T16_or_null, ef_register_sums* out, uint32_t* row_dev_or_null,
+                         float* plane_dev_or_null);
+int ef_register_cloud_dev(ef_ctx* ctx, const float* points3_dev, const float* normals3_dev_or_null, uint32_t n,
+                          const ef_register_params* params, const double* T_init16_or_null, double* T_out16, ef_register_result* result,
+                          uint32_t* row_dev_or_null, float* plane_dev_or_null);
+
 /* named internal images, copied to HOST (synchronises); for tests and for a front-end's drawing code */
 enum ef_image {
   EF_IMG_DEPTH_FILTERED = 0,      /* u16  */
