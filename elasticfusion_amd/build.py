@@ -64,6 +64,7 @@ VARIANTS = {   # python -m elasticfusion_amd.build --variant <name>: libefusion_
     "pipepoll": ["-DEF_FT_PIPELINED_POLL"],                    # A/B: the exchanges of the persistent launch keep two polls in flight instead of one (measured 6 % slower: off)
     "pipepoll_clocks": ["-DEF_FT_PIPELINED_POLL", "-DEF_STAGE_CLOCKS"],
     "alltaps": ["-DEF_CLEAN_ALL_TAPS"],                        # A/B: clean()'s keep-test asks for the taps of elements the time rules decide anyway (rounds 1-5)
+    "resolve": ["-DEF_KEEP_INDEX_RESOLVE"],                    # A/B: both predictIndices of a fusing frame resolved into the four index maps (rounds 1-8: two more launches) instead of their consumers tapping the z-buffer keys
     "r6m": ["-DEF_SEPARATE_SCAN", "-DEF_END_ONE_WAVE"],        # A/B: both of the above = the launches of commit 7b89629
 }
 SHIM_LIB = os.path.join(HERE, "libefusion.so")          # class ElasticFusion (include/ElasticFusion.h) over the C ABI

@@ -83,6 +83,16 @@ struct ef_ctx {
   efm::PredictMaps pm{};
   efm::FillMaps fm{};
   unsigned long long* zbuf = nullptr;
+  // Round 9: a frame that fuses does not resolve its two predictIndices into `im` — the association and the keep-test of clean() tap the keys
+  // (efm::KeyedIndex), each predictIndices on a z-buffer of its own: zbuf_assoc is cleared by the frame's clean(), zbuf_clean keeps the second
+  // splat's keys until the NEXT fusing frame's association clears it.  Until then `im` can be had from them (im_materialise, on the first
+  // ef_get_image of one of the four): im_pending says `im` is stale, im_map which of maps[] the keys' ids name (the buffer clean() read, left
+  // alone until the next clean() writes it) and im_T16 (device) holds the frame's T_cw.
+  unsigned long long* zbuf_assoc = nullptr;
+  unsigned long long* zbuf_clean = nullptr;
+  float* im_T16 = nullptr;
+  bool im_pending = false;
+  int im_map = 0;
   // global model
   efm::SurfelSoA maps[2]{};
   int cur = 0;
@@ -956,8 +966,17 @@ int process_frame(ef_ctx* c, const uint8_t* rgb_src, const uint16_t* depth_src, 
 #ifndef EF_RESOLVE_ALL_MAPS   // (A/B build "resolveall")
       im_assoc.color_time = nullptr;
 #endif
-      efm::predict_indices(c->cam, c->st->T_cw, c->tick, c->maps[c->cur], &c->st->map_counts[c->cur], c->maxDepthProcessed, c->cfg.time_delta, c->zbuf,
-                           im_assoc, s, sample_splat ? &c->probe_splat : nullptr);
+      // Round 9: neither predictIndices is resolved — their consumers tap the keys (ef_ctx::zbuf_assoc).  Not with stage timers (the update pass is
+      // a launch of its own between the two), the reference's download buffer, or a context that closes loops (a deformation's clean(), the
+      // predictions that share c->zbuf): those run the resolve launches as before.
+#ifdef EF_KEEP_INDEX_RESOLVE   // (A/B build "resolve": rounds 1-8's two resolve launches per frame)
+      const bool keyed = false;
+#else
+      const bool keyed = !c->timing && !c->reference_download && !c->cfg.close_loops;
+#endif
+      const efm::KeyedIndex key_assoc{c->zbuf_assoc, c->st->T_cw, c->maps[c->cur]}, key_clean{c->zbuf_clean, c->st->T_cw, c->maps[c->cur]};
+      efm::predict_indices(c->cam, c->st->T_cw, c->tick, c->maps[c->cur], &c->st->map_counts[c->cur], c->maxDepthProcessed, c->cfg.time_delta,
+                           keyed ? c->zbuf_assoc : c->zbuf, im_assoc, s, sample_splat ? &c->probe_splat : nullptr, nullptr, nullptr, !keyed);
       timer_end(c, "indexMap");
       timer_begin(c, "Fuse::Data+Update");
       // (the update pass — k_merge — rides on the splat of the second predictIndices: one launch less; with stage timers on it stays a launch of
@@ -968,12 +987,16 @@ int process_frame(ef_ctx* c, const uint8_t* rgb_src, const uint16_t* depth_src, 
       const bool defer_merge = !c->timing;
 #endif
       efm::fuse(c->cam, c->st->pose_f, c->tick, c->rgb, c->depth_metric, c->depth_metric_filtered, c->im, c->maxDepthProcessed,
-                &c->st->weighting, c->maps[c->cur], &c->st->map_counts[c->cur], c->cand, c->winner, s, defer_merge);
+                &c->st->weighting, c->maps[c->cur], &c->st->map_counts[c->cur], c->cand, c->winner, s, defer_merge,
+                keyed ? &key_assoc : nullptr, keyed ? c->zbuf_clean : nullptr);
       if (c->reference_download && !defer_merge) efm::copy_map(c->maps[c->cur], &c->st->map_counts[c->cur], c->shadow, s);
       timer_end(c, "Fuse::Data+Update");
       timer_begin(c, "indexMap2");
-      efm::predict_indices(c->cam, c->st->T_cw, c->tick, c->maps[c->cur], &c->st->map_counts[c->cur], c->maxDepthProcessed, c->cfg.time_delta, c->zbuf,
-                           c->im, s, nullptr, defer_merge ? &c->cand : nullptr, c->winner);
+      efm::predict_indices(c->cam, c->st->T_cw, c->tick, c->maps[c->cur], &c->st->map_counts[c->cur], c->maxDepthProcessed, c->cfg.time_delta,
+                           keyed ? c->zbuf_clean : c->zbuf, c->im, s, nullptr, defer_merge ? &c->cand : nullptr, c->winner, !keyed);
+      // (`im` now is what this frame's second predictIndices wrote, or — keyed — is still to be resolved from zbuf_clean when somebody asks)
+      c->im_pending = keyed;
+      c->im_map = c->cur;
       if (c->reference_download && defer_merge) efm::copy_map(c->maps[c->cur], &c->st->map_counts[c->cur], c->shadow, s);
       timer_end(c, "indexMap2");
       // a pending deformation (ElasticFusion.cpp:558-585): re-predict the depth of the surfels outside the time window, then let
@@ -986,7 +1009,7 @@ int process_frame(ef_ctx* c, const uint8_t* rgb_src, const uint16_t* depth_src, 
       c->cs.flip ^= 1;   // (CompactScratch::group_sum: this call's half was cleared by the call before it)
       efm::clean(c->cam, c->st->T_cw, c->tick, c->im, c->cfg.confidence, c->cfg.time_delta, c->maps[c->cur], &c->st->map_counts[c->cur], c->cand,
                  c->winner, c->maps[c->cur ^ 1], &c->st->map_counts[c->cur ^ 1], c->capacity, c->cs, c->overflow, s,
-                 c->graph_nodes > 0 ? &def : nullptr);
+                 c->graph_nodes > 0 ? &def : nullptr, keyed ? &key_clean : nullptr, keyed ? c->zbuf_assoc : nullptr, keyed ? c->im_T16 : nullptr);
       c->graph_nodes = 0;
       c->cur ^= 1;
       timer_end(c, "Fuse::Copy");
@@ -1081,6 +1104,9 @@ int ctx_init(ef_ctx* c) {
   EF_ALLOC(c, c->fm.vertex, P);
   EF_ALLOC(c, c->fm.normal, P);
   EF_ALLOC(c, c->zbuf, P, 0xFF);
+  EF_ALLOC(c, c->zbuf_assoc, P, 0xFF);
+  EF_ALLOC(c, c->zbuf_clean, P, 0xFF);
+  EF_ALLOC(c, c->im_T16, 16);
   EF_ALLOC(c, c->graph_dev, 1024 * 16);     // GlobalModel::MAX_NODES x 16 (GlobalModel.cpp:24)
   EF_ALLOC(c, c->synth_depth, P);
   EF_ALLOC(c, c->rays, P * 4);
@@ -1911,10 +1937,17 @@ int ef_set_frame_to_frame_rgb(ef_ctx* c, int v) { if (!c) return EF_EINVAL; c->c
 int ef_set_confidence_threshold(ef_ctx* c, float v) { if (!c) return EF_EINVAL; c->cfg.confidence = v; return EF_OK; }
 int ef_set_depth_cutoff(ef_ctx* c, float v) { if (!c) return EF_EINVAL; c->cfg.depth_cut = v; return EF_OK; }
 
+// the four index maps of the last fusing frame, resolved now from the keys its second predictIndices left (ef_ctx::zbuf_clean)
+static void im_materialise(ef_ctx* c) {
+  if (!c->im_pending) return;
+  efm::resolve_indices(c->cam, c->im_T16, c->maps[c->im_map], c->zbuf_clean, c->im, c->stream);
+  c->im_pending = false;
+}
 int ef_get_image(ef_ctx* c, int which, void* dst, size_t bytes) {
   if (!c || !dst) return EF_EINVAL;
   DeviceGuard dg_(c);
   const size_t P = (size_t)c->cam.cols * c->cam.rows;
+  if (which >= EF_IMG_INDEX && which <= EF_IMG_NORM_RAD) im_materialise(c);
   const void* src = nullptr;
   size_t need = 0;
   switch (which) {

@@ -42,6 +42,16 @@ struct IndexMaps {   // IndexMap::predictIndices outputs (IndexMap.h:74-88)
 __host__ __device__ inline int im_texel(const IndexMaps& im, const Cam& cam, int px, int py) {
   return im.colmajor ? px * cam.rows + py : py * cam.cols + px;
 }
+// The z-buffer of a predict_indices(..., resolve = false) standing in for the four images it was not resolved into (round 9).  A texel's key
+// holds the winner's id and the exact float of its depth (= vert_conf.z); fuse() and clean() test the depth first, so they read 8 bytes per
+// texel, and for the texels behind that gate gather the winner's two surfel rows and redo the resolve's arithmetic (index_texel_* in
+// ef_map_kernels.hip: the expressions k_index_resolve evaluates, on the same inputs).  Nobody returns these keys to ZBUF_EMPTY on reading
+// them (a consumer's neighbours read the texel too): the buffer is cleared by a later launch that is given it as `zclear` (fuse, clean).
+struct KeyedIndex {
+  const unsigned long long* keys;   // same storage order as IndexMaps::colmajor says
+  const float* T_cw16_dev;          // the pose the splat projected with
+  SurfelSoA map;                    // the rows the keys' ids name, as they stood when the splat ran (or as the splat's merge left them)
+};
 struct PredictMaps { // IndexMap::combinedPredict outputs (IndexMap.h:98-112)
   uchar4* image;
   float4* vertex;
@@ -109,7 +119,12 @@ void seed_map(const Cam& cam, const uint8_t* rgb3, const float* depth_metric, co
 void predict_indices(const Cam& cam, const float* T_cw16_dev, int time, SurfelSoA map, const unsigned* count_dev, float maxDepth,
                      int timeDelta, unsigned long long* zbuf, IndexMaps out, hipStream_t s, eft::KernelProbe* probe = nullptr,
                      // merge_cand / merge_winner given (behind fuse(..., defer_merge = true)): the update pass of the fusion rides on this splat
-                     const struct Candidates* merge_cand = nullptr, const uint32_t* merge_winner = nullptr);
+                     const struct Candidates* merge_cand = nullptr, const uint32_t* merge_winner = nullptr,
+                     // resolve false: only the splat — `out` is not written (its colmajor still names the z-buffer's order) and the keys stay in
+                     // zbuf for a KeyedIndex consumer; the caller has the buffer cleared by a later launch
+                     bool resolve = true);
+// the resolve launch of predict_indices on its own, from keys a splat left behind; the z-buffer is left as it is
+void resolve_indices(const Cam& cam, const float* T_cw16_dev, SurfelSoA map, const unsigned long long* zbuf, IndexMaps out, hipStream_t s);
 void combined_predict(const Cam& cam, const float* T_cw16_dev, SurfelSoA map, const unsigned* count_dev, float maxDepth,
                       float confThreshold, int time, int maxTime, int timeDelta, unsigned long long* zbuf, PredictMaps out,
                       // optional fused fill-in + denseEnough sampling (null fill.image => skipped)
@@ -137,7 +152,10 @@ void dense_count(const Cam& cam, const uchar4* image, unsigned* counter, hipStre
 // pose_f16_dev: float T_wc (cast<float>().matrix()); weighting_dev: device float
 void fuse(const Cam& cam, const float* pose_f16_dev, int time, const uint8_t* rgb3, const float* depth_metric,
           const float* depth_metric_filtered, IndexMaps im, float maxDepth, const float* weighting_dev, SurfelSoA map,
-          const unsigned* count_dev, Candidates cand, uint32_t* winner, hipStream_t s, bool defer_merge = false);
+          const unsigned* count_dev, Candidates cand, uint32_t* winner, hipStream_t s, bool defer_merge = false,
+          // keyed given: the association taps the z-buffer instead of im's images (im.colmajor still read); zclear (or null): cols x rows keys
+          // of ANOTHER z-buffer that the association's launch returns to ZBUF_EMPTY
+          const KeyedIndex* keyed = nullptr, unsigned long long* zclear = nullptr);
 // deformation graph handed to clean() after a loop closure (copy_unstable.vert:128-322): nodes x 16 floats sorted by time
 // {position 3, rotation 9 column-major, translation 3, time}; depth = synthesize_depth image (read unless is_fern)
 struct Deformation {
@@ -150,7 +168,10 @@ struct Deformation {
 // clean + append; writes the compacted map to `out` and the new count (clamped to capacity) to *count_out_dev
 void clean(const Cam& cam, const float* T_cw16_dev, int time, IndexMaps im, float confThreshold, int timeDelta, SurfelSoA map,
            const unsigned* count_dev, Candidates cand, uint32_t* winner, SurfelSoA out, unsigned* count_out_dev, uint32_t capacity,
-           const CompactScratch& cs, int* overflow_flag, hipStream_t s, const Deformation* deform = nullptr);
+           const CompactScratch& cs, int* overflow_flag, hipStream_t s, const Deformation* deform = nullptr,
+           // keyed given (no deformation): the keep-test taps the z-buffer instead of im's images; zclear (or null): cols x rows keys of ANOTHER
+           // z-buffer that the scatter launch returns to ZBUF_EMPTY; T_keep16_dev (or null): receives a copy of the 16 floats at T_cw16_dev
+           const KeyedIndex* keyed = nullptr, unsigned long long* zclear = nullptr, float* T_keep16_dev = nullptr);
 // Deformation::sampleGraphModel: nodes {x, y, z, initTime} = every `stride`-th surfel (5000 in the reference); *n_out = node count
 void sample_graph(SurfelSoA map, const unsigned* count_dev, int stride, int max_nodes, float* out4, unsigned* n_out, hipStream_t s);
 // candidates -> AoS "newUnstable" list in draw order (operator tier / tests)

@@ -9,6 +9,7 @@
 #include <mutex>
 #include <hip/hip_ext.h>
 #include "ef_map.hpp"
+#include "ef_zkey.hpp"
 
 using namespace ef;
 
@@ -23,10 +24,7 @@ constexpr int CLEAN_GRID = 4096;     // grid-stride workgroups of the clean pass
 static_assert(CLEAN_ROW == BLK, "clean kernels run one element per thread");
 static_assert(CLEAN_GRID % 8 == 0, "xcd_row");
 
-__device__ __forceinline__ uint32_t depth_key(float z) {  // order-preserving float -> uint
-  const uint32_t b = __float_as_uint(z);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
+// (depth_key / depth_of_key: ef_zkey.hpp)
 __device__ __forceinline__ unsigned long long zkey(float z, uint32_t id) { return ((unsigned long long)depth_key(z) << 32) | id; }
 // XCD-aware work order (round 6).  Workgroup b of a launch runs on XCD b % 8 and every XCD has its own L2.  The per-surfel and per-pixel passes
 // that read a NEIGHBOURHOOD of the index maps (clean's and fuse's taps) walk surfels / pixels in column-major order, so consecutive workgroups read
@@ -356,6 +354,20 @@ __global__ void __launch_bounds__(BLK) k_index_splat(const Cam cam, const float*
     atomicMin(&zbuf[colmajor ? px * cam.rows + py : py * cam.cols + px], zkey(p.z, id));   // N2
   }
 }
+// What a texel won by a surfel holds besides its index and its colour / time row — ONE definition, evaluated by the resolve launch and by the
+// consumers that tap the z-buffer itself (KeyedIndex: k_associate<true>, clean_test<true>), so the two cannot drift apart:
+//   vertex + confidence = {T * position, confidence}; its .z is the float the splat put into the key (the same xform of the same row)
+//   normal + radius     = {normalize(R * normal), radius}
+__device__ __forceinline__ float4 index_texel_vert_conf(const rt34& T, float4 pc) {
+  const f3 p = xform(T, f3{pc.x, pc.y, pc.z});
+  return make_float4(p.x, p.y, p.z, pc.w);
+}
+__device__ __forceinline__ float4 index_texel_norm_rad(const rt34& T, float4 nr) {
+  const f3 n = normalized(mul(T.R, f3{nr.x, nr.y, nr.z}));
+  return make_float4(n.x, n.y, n.z, nr.w);
+}
+// CLEAR false: the keys are left in place (resolve_indices: the images asked for after a frame whose consumers tapped the keys)
+template <bool CLEAR>
 __global__ void __launch_bounds__(BLK) k_index_resolve(const Cam cam, const float* __restrict__ T16, SurfelSoA map,
                                                         unsigned long long* zbuf, IndexMaps out) {
   const int pi = blockIdx.x * blockDim.x + threadIdx.x;
@@ -370,17 +382,15 @@ __global__ void __launch_bounds__(BLK) k_index_resolve(const Cam cam, const floa
     out.norm_rad[pi] = make_float4(0, 0, 0, 0);
     return;
   }
-  zbuf[pi] = ZBUF_EMPTY;  // leave the buffer clean for the next splat: no separate clear pass
+  if (CLEAR) zbuf[pi] = ZBUF_EMPTY;  // leave the buffer clean for the next splat: no separate clear pass
   const uint32_t id = (uint32_t)key;
   const rt34 T = rt34_load16(T16);
   const float4 pc = map.pos_conf[id];
   const float4 nr = map.nrm_rad[id];
-  const f3 p = xform(T, f3{pc.x, pc.y, pc.z});
-  const f3 n = normalized(mul(T.R, f3{nr.x, nr.y, nr.z}));
   out.index[pi] = id;
-  out.vert_conf[pi] = make_float4(p.x, p.y, p.z, pc.w);
+  out.vert_conf[pi] = index_texel_vert_conf(T, pc);
   if (out.color_time) out.color_time[pi] = map.col_time[id];
-  out.norm_rad[pi] = make_float4(n.x, n.y, n.z, nr.w);
+  out.norm_rad[pi] = index_texel_norm_rad(T, nr);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -681,7 +691,6 @@ __global__ void __launch_bounds__(BLK) k_surface_resolve(const Cam cam, const fl
   }
 }
 // IndexMap::synthesizeDepth (G6): depth_splat.frag's only output is the intersection depth the z-buffer key already holds
-__device__ __forceinline__ float depth_of_key(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 __global__ void __launch_bounds__(BLK) k_depth_resolve(int cols, int rows, unsigned long long* zbuf, float* __restrict__ depth) {
   const int pi = blockIdx.x * blockDim.x + threadIdx.x;
   if (pi >= cols * rows) return;
@@ -723,13 +732,23 @@ struct FuseArgs {
   IndexMaps im;
   float maxDepth;
   const float* weighting;
+  KeyedIndex key;               // k_associate<true>: the z-buffer it taps in place of im's images
+  unsigned long long* zclear;   // ... and cols x rows keys of another one it returns to ZBUF_EMPTY (or null)
 };
 // data.vert:76-193.  One thread per fused pixel (W/2 x H/2, parity-selected: quirk Q12), threads walk rows
 // (coalesced taps); the candidate lands in slot r = column-major rank == the reference's draw order.
+// KEYED (round 9): the frame's first predictIndices is not resolved into images — a texel is the 8-byte key the splat left (FuseArgs::key).  The
+// key gives the winner's id and vc.z, which is all the first two tests of a tap look at; only the texels behind them ask for the winner's
+// position and normal rows, and vc / nr are what the resolve would have stored (index_texel_*).  An empty texel and one won by surfel 0 fail
+// `current > 0U` as they do on the images.  The launch also clears FuseArgs::zclear (the z-buffer of the PREVIOUS frame's second
+// predictIndices, whose readers are long done and whose next splat comes behind this launch).
+template <bool KEYED>
 __global__ void __launch_bounds__(BLK) k_associate(const FuseArgs A, Candidates cand, uint32_t* winner, int colwalk) {
   const Cam cam = A.cam;
   const int qc = cam.cols / 2, qr = cam.rows / 2;
   const int q = (int)(xcd_block() * blockDim.x + threadIdx.x);
+  if (KEYED && A.zclear)
+    for (int i = q, P = cam.cols * cam.rows, step = (int)(gridDim.x * blockDim.x); i < P; i += step) A.zclear[i] = ZBUF_EMPTY;
   if (q >= qc * qr) return;
   // colwalk: consecutive lanes go down a column (the order of the candidate slots and of a column-major index map);
   // otherwise along a row (the order of the depth and colour images)
@@ -756,7 +775,8 @@ __global__ void __launch_bounds__(BLK) k_associate(const FuseArgs A, Candidates 
     const uint8_t c0 = c[0], c1 = c[1], c2 = c[2];
     const float weighting = *A.weighting;
     uint32_t idx9[3][3];
-    float4 vc9[3][3], nr9[3][3];
+    float4 vc9[3][3], nr9[3][3];   // KEYED: the winners' position + confidence and normal + radius ROWS until the taps turn them into texels
+    uint2 key9[3][3];   // {id, depth_key}: the two halves of a 64-bit key
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       const int tx = clampi(i + a - 1, 0, cam.cols - 1);
@@ -764,9 +784,13 @@ __global__ void __launch_bounds__(BLK) k_associate(const FuseArgs A, Candidates 
       for (int b = 0; b < 3; ++b) {
         const int ty = clampi(j + b - 1, 0, cam.rows - 1);
         const int ti = im_texel(A.im, cam, tx, ty);
-        idx9[a][b] = A.im.index[ti];
-        vc9[a][b] = A.im.vert_conf[ti];
-        nr9[a][b] = A.im.norm_rad[ti];
+        if (KEYED) {
+          key9[a][b] = reinterpret_cast<const uint2*>(A.key.keys)[ti];
+        } else {
+          idx9[a][b] = A.im.index[ti];
+          vc9[a][b] = A.im.vert_conf[ti];
+          nr9[a][b] = A.im.norm_rad[ti];
+        }
       }
     }
     const rt34 pose = rt34_load16(A.pose16);
@@ -808,6 +832,7 @@ __global__ void __launch_bounds__(BLK) k_associate(const FuseArgs A, Candidates 
 #ifdef EF_ASSOC_LATE_LOADS
       uint32_t idx9[3][3];
       float4 vc9[3][3], nr9[3][3];
+      uint2 key9[3][3];   // {id, depth_key}: the two halves of a 64-bit key
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
         const int tx = clampi(i + a - 1, 0, cam.cols - 1);
@@ -815,12 +840,39 @@ __global__ void __launch_bounds__(BLK) k_associate(const FuseArgs A, Candidates 
         for (int b = 0; b < 3; ++b) {
           const int ty = clampi(j + b - 1, 0, cam.rows - 1);
           const int ti = im_texel(A.im, cam, tx, ty);
-          idx9[a][b] = A.im.index[ti];
-          vc9[a][b] = A.im.vert_conf[ti];
-          nr9[a][b] = A.im.norm_rad[ti];
+          if (KEYED) {
+            key9[a][b] = reinterpret_cast<const uint2*>(A.key.keys)[ti];
+          } else {
+            idx9[a][b] = A.im.index[ti];
+            vc9[a][b] = A.im.vert_conf[ti];
+            nr9[a][b] = A.im.norm_rad[ti];
+          }
         }
       }
 #endif
+      // KEYED: the second round of loads, again all of them before the first use and none behind a branch — a texel that fails the first two
+      // tests of its taps (empty, won by surfel 0, or too far from the pixel in depth: decided on the key) asks for row 0 and is marked 0,
+      // which is what `current > 0U` sends away
+      const rt34 Tcw = rt34_load16(KEYED ? A.key.T_cw16_dev : A.pose16);   // (not KEYED: unused)
+      if (KEYED) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+          for (int b = 0; b < 3; ++b) {
+            const uint32_t id = key9[a][b].x;
+            float vcz = depth_of_key(key9[a][b].y);
+            asm volatile("" : "+v"(vcz));   // (opaque: with the decode visible to this comparison, hipcc 7.2's instruction selection crashes on the kernel)
+            const bool tap = (id & key9[a][b].y) != 0xFFFFFFFFu /* ZBUF_EMPTY */ && id > 0U && fabsf((vcz * lambda) - (vPosLocal.z * lambda)) < 0.05f;
+            idx9[a][b] = tap ? id : 0U;
+          }
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+          for (int b = 0; b < 3; ++b) {
+            vc9[a][b] = A.key.map.pos_conf[idx9[a][b]];
+            nr9[a][b] = A.key.map.nrm_rad[idx9[a][b]];
+          }
+      }
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
         const int a3 = a == 0 ? 0 : (a == 3 ? 2 : 1);
@@ -829,11 +881,11 @@ __global__ void __launch_bounds__(BLK) k_associate(const FuseArgs A, Candidates 
           const int b3 = b == 0 ? 0 : (b == 3 ? 2 : 1);
           const uint32_t current = idx9[a3][b3];
           if (current > 0U) {
-            const float4 vc = vc9[a3][b3];
+            const float4 vc = KEYED ? index_texel_vert_conf(Tcw, vc9[a3][b3]) : vc9[a3][b3];
             if (fabsf((vc.z * lambda) - (vPosLocal.z * lambda)) < 0.05f) {
               const f3 cr = cross(ray, f3{vc.x, vc.y, vc.z});
               const float dist = sqrtf(dot(cr, cr)) / lenRay;
-              const float4 nr = nr9[a3][b3];
+              const float4 nr = KEYED ? index_texel_norm_rad(Tcw, nr9[a3][b3]) : nr9[a3][b3];
               const f3 nn{nr.x, nr.y, nr.z};
               const float cang = dot(nn, vNormLocal) / (sqrtf(dot(nn, nn)) * lenN);
               const bool angOk = (cang > 0.87758255f && cang <= 1.0f);  // abs(acos(c)) < 0.5, NaN-false
@@ -908,6 +960,7 @@ struct CleanArgs {
   IndexMaps im;
   float confThreshold;
   int timeDelta;
+  KeyedIndex key;   // clean_test<true>: the z-buffer it taps in place of im's images
 };
 // The 4 taps of one axis (N4: pixel offsets {-1,-.5,0,+.5} -> texel floor(x+off), clamped) hit at most 3 distinct
 // texels (the offsets span 1.5, so the floors span <= 2, and clamping is monotone).  The keep-test only counts taps,
@@ -928,6 +981,11 @@ __device__ __forceinline__ Taps3 dedupe_taps(float x, int hi) {
   return r;
 }
 // copy_unstable.vert:49-130 (nodes == 0); returns keep flag; ct.w tag -2 is rewritten to time by the caller
+// KEYED (round 9): the frame's second predictIndices is not resolved into images — a texel is the 8-byte key its splat left (CleanArgs::key).  Both
+// counting rules ask for `vc.z > localPos.z`, and vc.z is in the key: only the texels behind that test (and `idx > 0U`, and at least one
+// tap) ask for the winner's position + confidence and colour + time rows; vc is what the resolve would have stored (index_texel_vert_conf)
+// and c2 is the colour + time row itself.  The rows are those of the map this launch compacts: the splat merged them before it projected them.
+template <bool KEYED>
 __device__ __forceinline__ bool clean_test(const CleanArgs& A, const rt34& T, float4 pc, float4 ct, float4 nr) {
   const Cam& cam = A.cam;
   const float ftime = (float)A.time, ftd = (float)A.timeDelta;
@@ -949,23 +1007,46 @@ __device__ __forceinline__ bool clean_test(const CleanArgs& A, const rt34& T, fl
   if (!decided && ftime - ct.w < ftd && localPos.z > 0 && x > 0 && y > 0 && x < (float)cam.cols && y < (float)cam.rows) {
     const Taps3 tx = dedupe_taps(x, cam.cols - 1), ty = dedupe_taps(y, cam.rows - 1);
     uint32_t idx[9];
-    float4 vcs[9], c2s[9];
+    float4 vcs[9], c2s[9];   // KEYED: vcs = the winners' position + confidence ROWS until the taps turn them into texels
+    if (KEYED) {
+      unsigned long long keys[9];
 #pragma unroll
-    for (int a = 0; a < 3; ++a)
+      for (int a = 0; a < 3; ++a)
 #pragma unroll
-      for (int b = 0; b < 3; ++b) {
-        const int ti = im_texel(A.im, cam, tx.u[a], ty.u[b]);
-        idx[a * 3 + b] = A.im.index[ti];
-        vcs[a * 3 + b] = A.im.vert_conf[ti];
-        c2s[a * 3 + b] = A.im.color_time[ti];
+        for (int b = 0; b < 3; ++b) keys[a * 3 + b] = A.key.keys[im_texel(A.im, cam, tx.u[a], ty.u[b])];
+      // (a texel no rule can count — no tap on it, empty, won by surfel 0, or not behind the element — asks for row 0 and is marked 0)
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+          const unsigned long long key = keys[a * 3 + b];
+          const uint32_t id = (uint32_t)key;
+          const bool tap = tx.m[a] * ty.m[b] > 0 && key != ZBUF_EMPTY && id > 0U && depth_of_key((uint32_t)(key >> 32)) > localPos.z;
+          idx[a * 3 + b] = tap ? id : 0U;
+        }
+#pragma unroll
+      for (int k = 0; k < 9; ++k) {
+        vcs[k] = A.key.map.pos_conf[idx[k]];
+        c2s[k] = A.key.map.col_time[idx[k]];
       }
+    } else {
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+          const int ti = im_texel(A.im, cam, tx.u[a], ty.u[b]);
+          idx[a * 3 + b] = A.im.index[ti];
+          vcs[a * 3 + b] = A.im.vert_conf[ti];
+          c2s[a * 3 + b] = A.im.color_time[ti];
+        }
+    }
     const bool steep = fabsf(localNorm.z) > 0.85f;
 #pragma unroll
     for (int a = 0; a < 3; ++a)
 #pragma unroll
       for (int b = 0; b < 3; ++b) {
         const int w = tx.m[a] * ty.m[b];   // how many of the 16 taps land on this texel
-        const float4 vc = vcs[a * 3 + b], c2 = c2s[a * 3 + b];
+        const float4 vc = KEYED ? index_texel_vert_conf(T, vcs[a * 3 + b]) : vcs[a * 3 + b], c2 = c2s[a * 3 + b];
         if (w > 0 && idx[a * 3 + b] > 0U) {
           const float dx = vc.x - localPos.x, dy = vc.y - localPos.y;
           if (c2.z < ct.z && vc.w > A.confThreshold && vc.z > localPos.z && vc.z - localPos.z < 0.01f &&
@@ -1134,6 +1215,7 @@ __global__ void __launch_bounds__(BLK) k_clean_deform(const CleanArgs A, const D
 // one element per thread, one CLEAN_ROW-element compaction chunk per workgroup iteration: everything a row needs
 // is in flight at once (the element count is device-resident, hence the grid-stride over rows)
 // gsum_now / gsum_zero (CompactScratch::group_sum, or null): the row's count is also added to its group's sum, and the other half is cleared
+template <bool KEYED>
 __global__ void __launch_bounds__(BLK) k_clean_flags(const CleanArgs A, SurfelSoA map, const unsigned* __restrict__ count_dev,
                                                       Candidates cand, uint32_t* winner, uint8_t* __restrict__ flags,
                                                       uint32_t* __restrict__ chunk_count, uint32_t* gsum_now, uint32_t* __restrict__ gsum_zero,
@@ -1151,7 +1233,7 @@ __global__ void __launch_bounds__(BLK) k_clean_flags(const CleanArgs A, SurfelSo
     bool f = false;
     if (e < n) {
       float4 pc, ct, nr;
-      if (load_element(map, cand, count, e, pc, ct, nr)) f = clean_test(A, T, pc, ct, nr);
+      if (load_element(map, cand, count, e, pc, ct, nr)) f = clean_test<KEYED>(A, T, pc, ct, nr);
       if (e < count) winner[e] = WINNER_EMPTY;  // re-arm the association winners for the next frame
       flags[e] = f ? 1 : 0;
     }
@@ -1196,12 +1278,19 @@ __device__ __forceinline__ unsigned block_excl_scan_and_sum(unsigned v, unsigned
 // gsum given (CompactScratch::group_sum): no scan launch in front of this one — the workgroup adds up the groups and the rows in front of its row
 // itself (<= max_groups + CLEAN_GROUP - 1 words, one or two loads per thread, in flight with the row's elements), and the workgroup of the
 // LAST row leaves the totals k_scan_chunks left (total_out, the clamped count_out, the overflow flag)
+// zclear (or null): zclear_n keys of a z-buffer whose readers ran before this launch are returned to ZBUF_EMPTY (round 9: the frame's first
+// predictIndices, tapped by k_associate<true>); T_keep (or null) receives the 16 floats at T_src (the pose of the keys clean_test<true> tapped:
+// resolve_indices may be asked for their images after the tracker has moved on)
 __global__ void __launch_bounds__(BLK) k_clean_scatter(SurfelSoA map, const unsigned* __restrict__ count_dev, Candidates cand,
                                                         const uint8_t* __restrict__ flags, const uint32_t* __restrict__ chunk_offset,
                                                         int time, SurfelSoA out, uint32_t capacity, const uint32_t* __restrict__ gsum,
                                                         const uint32_t* __restrict__ chunk_count, uint32_t* total_out, unsigned* count_out,
-                                                        int* overflow_flag) {
+                                                        int* overflow_flag, unsigned long long* __restrict__ zclear, int zclear_n,
+                                                        const float* __restrict__ T_src, float* __restrict__ T_keep) {
   __shared__ unsigned lds[2 * BLK / 64];
+  if (zclear)
+    for (int i = blockIdx.x * BLK + threadIdx.x; i < zclear_n; i += gridDim.x * BLK) zclear[i] = ZBUF_EMPTY;
+  if (T_keep && blockIdx.x == 0 && threadIdx.x < 16) T_keep[threadIdx.x] = T_src[threadIdx.x];
   const unsigned count = *count_dev;
   const unsigned n = count + (unsigned)cand.n;
   const unsigned nrows = (n + CLEAN_ROW - 1) / CLEAN_ROW;
@@ -1367,11 +1456,11 @@ void seed_map(const Cam& cam, const uint8_t* rgb3, const float* dm, const float*
 
 void predict_indices(const Cam& cam, const float* T_cw16_dev, int time, SurfelSoA map, const unsigned* count_dev, float maxDepth,
                      int timeDelta, unsigned long long* zbuf, IndexMaps out, hipStream_t s, eft::KernelProbe* probe, const Candidates* merge_cand,
-                     const uint32_t* merge_winner) {
+                     const uint32_t* merge_winner, bool resolve) {
   if (merge_cand) {   // fuse(..., defer_merge = true) in front of this call: the update pass rides on the splat
     hipLaunchKernelGGL(k_index_splat<true>, dim3(SURFEL_GRID), dim3(BLK), 0, s, cam, T_cw16_dev, time, map, count_dev, maxDepth, timeDelta, zbuf,
                        out.colmajor, *merge_cand, merge_winner);
-    hipLaunchKernelGGL(k_index_resolve, dim3(ceil_div(cam.cols * cam.rows, BLK)), dim3(BLK), 0, s, cam, T_cw16_dev, map, zbuf, out);
+    if (resolve) hipLaunchKernelGGL(k_index_resolve<true>, dim3(ceil_div(cam.cols * cam.rows, BLK)), dim3(BLK), 0, s, cam, T_cw16_dev, map, zbuf, out);
     return;
   }
   // the probe's events receive the kernel's own begin / end timestamps (what rocprofv3 --kernel-trace reports as its duration)
@@ -1380,7 +1469,11 @@ void predict_indices(const Cam& cam, const float* T_cw16_dev, int time, SurfelSo
   if (sample) probe->used++;
   hipExtLaunchKernelGGL(k_index_splat<false>, dim3(SURFEL_GRID), dim3(BLK), 0, s, e0, e1, 0, cam, T_cw16_dev, time, map, count_dev, maxDepth, timeDelta,
                         zbuf, out.colmajor, Candidates{}, (const uint32_t*)nullptr);
-  hipLaunchKernelGGL(k_index_resolve, dim3(ceil_div(cam.cols * cam.rows, BLK)), dim3(BLK), 0, s, cam, T_cw16_dev, map, zbuf, out);
+  if (resolve) hipLaunchKernelGGL(k_index_resolve<true>, dim3(ceil_div(cam.cols * cam.rows, BLK)), dim3(BLK), 0, s, cam, T_cw16_dev, map, zbuf, out);
+}
+void resolve_indices(const Cam& cam, const float* T_cw16_dev, SurfelSoA map, const unsigned long long* zbuf, IndexMaps out, hipStream_t s) {
+  hipLaunchKernelGGL(k_index_resolve<false>, dim3(ceil_div(cam.cols * cam.rows, BLK)), dim3(BLK), 0, s, cam, T_cw16_dev, map,
+                     const_cast<unsigned long long*>(zbuf), out);
 }
 
 void combined_predict(const Cam& cam, const float* T_cw16_dev, SurfelSoA map, const unsigned* count_dev, float maxDepth,
@@ -1430,19 +1523,23 @@ void dense_count(const Cam& cam, const uchar4* image, unsigned* counter, hipStre
 
 void fuse(const Cam& cam, const float* pose_f16_dev, int time, const uint8_t* rgb3, const float* dm, const float* dmf, IndexMaps im,
           float maxDepth, const float* weighting_dev, SurfelSoA map, const unsigned* count_dev, Candidates cand, uint32_t* winner,
-          hipStream_t s, bool defer_merge) {
+          hipStream_t s, bool defer_merge, const KeyedIndex* keyed, unsigned long long* zclear) {
   (void)count_dev;
-  FuseArgs A{cam, pose_f16_dev, time, rgb3, dm, dmf, im, maxDepth, weighting_dev};
+  FuseArgs A{cam, pose_f16_dev, time, rgb3, dm, dmf, im, maxDepth, weighting_dev, keyed ? *keyed : KeyedIndex{}, zclear};
   // column-major index maps: walking columns measured 24.7 us vs 34.8 us for walking rows (profiles/, round 1)
-  hipLaunchKernelGGL(k_associate, dim3(ceil_div(cand.n, BLK)), dim3(BLK), 0, s, A, cand, winner, im.colmajor ? 1 : 0);
+  if (keyed)
+    hipLaunchKernelGGL(k_associate<true>, dim3(ceil_div(cand.n, BLK)), dim3(BLK), 0, s, A, cand, winner, im.colmajor ? 1 : 0);
+  else
+    hipLaunchKernelGGL(k_associate<false>, dim3(ceil_div(cand.n, BLK)), dim3(BLK), 0, s, A, cand, winner, im.colmajor ? 1 : 0);
   // (defer_merge: the caller's next launch is predict_indices(..., &cand, winner), whose splat merges every surfel before it projects it)
   if (!defer_merge) hipLaunchKernelGGL(k_merge, dim3(ceil_div(cand.n, BLK)), dim3(BLK), 0, s, cand, (const uint32_t*)winner, map, time);
 }
 
 void clean(const Cam& cam, const float* T_cw16_dev, int time, IndexMaps im, float confThreshold, int timeDelta, SurfelSoA map,
            const unsigned* count_dev, Candidates cand, uint32_t* winner, SurfelSoA out, unsigned* count_out_dev, uint32_t capacity,
-           const CompactScratch& cs, int* overflow_flag, hipStream_t s, const Deformation* deform) {
-  CleanArgs A{cam, T_cw16_dev, time, im, confThreshold, timeDelta};
+           const CompactScratch& cs, int* overflow_flag, hipStream_t s, const Deformation* deform, const KeyedIndex* keyed,
+           unsigned long long* zclear, float* T_keep16_dev) {
+  CleanArgs A{cam, T_cw16_dev, time, im, confThreshold, timeDelta, keyed ? *keyed : KeyedIndex{}};
 #ifdef EF_SEPARATE_SCAN   // (A/B build "sepscan": rounds 1-5's three launches)
   const bool fold = false;
 #else
@@ -1450,8 +1547,12 @@ void clean(const Cam& cam, const float* T_cw16_dev, int time, IndexMaps im, floa
 #endif
   uint32_t* const gnow = fold ? cs.group_sum + (size_t)(cs.flip & 1) * cs.max_groups * CLEAN_GSTRIDE : nullptr;
   uint32_t* const gzero = fold ? cs.group_sum + (size_t)((cs.flip & 1) ^ 1) * cs.max_groups * CLEAN_GSTRIDE : nullptr;
-  hipLaunchKernelGGL(k_clean_flags, dim3(CLEAN_GRID), dim3(BLK), 0, s, A, map, count_dev, cand, winner, cs.flags,
-                     cs.chunk_count, gnow, gzero, cs.max_groups);
+  if (keyed)
+    hipLaunchKernelGGL(k_clean_flags<true>, dim3(CLEAN_GRID), dim3(BLK), 0, s, A, map, count_dev, cand, winner, cs.flags,
+                       cs.chunk_count, gnow, gzero, cs.max_groups);
+  else
+    hipLaunchKernelGGL(k_clean_flags<false>, dim3(CLEAN_GRID), dim3(BLK), 0, s, A, map, count_dev, cand, winner, cs.flags,
+                       cs.chunk_count, gnow, gzero, cs.max_groups);
   if (deform && deform->nodes > 0) {
     const DeformArgs D{deform->graph_dev, deform->nodes, deform->depth_dev, deform->is_fern, deform->max_depth};
     hipLaunchKernelGGL(k_clean_deform, dim3(CLEAN_GRID), dim3(BLK), 0, s, A, D, map, count_dev, cand, (const uint8_t*)cs.flags);
@@ -1463,7 +1564,7 @@ void clean(const Cam& cam, const float* T_cw16_dev, int time, IndexMaps im, floa
                        cs.chunk_offset, cs.totals, count_out_dev, capacity, overflow_flag, (unsigned)CLEAN_ROW);
   hipLaunchKernelGGL(k_clean_scatter, dim3(CLEAN_GRID), dim3(BLK), 0, s, map, count_dev, cand, (const uint8_t*)cs.flags,
                      (const uint32_t*)cs.chunk_offset, time, out, capacity, (const uint32_t*)gnow, (const uint32_t*)cs.chunk_count, cs.totals,
-                     count_out_dev, overflow_flag);
+                     count_out_dev, overflow_flag, zclear, cam.cols * cam.rows, T_cw16_dev, T_keep16_dev);
 }
 
 void candidates_to_aos(Candidates cand, float* aos, unsigned* count_dev, const CompactScratch& cs, hipStream_t s) {
