@@ -31,41 +31,7 @@ VARIANTS = {   # python -m elasticfusion_amd.build --variant <name>: libefusion_
     "nofma_fast": ["-DEF_FORCE_FAST_ORDER"],                   # no fused multiply-adds + the fast order (parity factorial)
     "clocks": ["-DEF_STAGE_CLOCKS"],                           # phase clocks of the default build's tracker (tools/small_clocks.py)
     "fast_clocks": ["-DEF_FAST_BUILD", "-DEF_STAGE_CLOCKS"],   # phase clocks of the fast build's persistent tracker (tools/fast_clocks.py)
-    "ldlt_wave": ["-DEF_LDLT_WAVE"],                           # A/B: rounds 2-4's 6x6 factorisation, one matrix element per lane (ef_solve_dev.hpp)
-    "ldlt_wave_clocks": ["-DEF_LDLT_WAVE", "-DEF_STAGE_CLOCKS"],
-    "nopairs": ["-DEF_NO_VISIT_PAIRS"],                        # A/B: one visit per lane in the normal-equation rows (rounds 1-5; round 6 evaluates two, packed)
-    "nopairs_clocks": ["-DEF_NO_VISIT_PAIRS", "-DEF_STAGE_CLOCKS"],
-    "p_icp": ["-DEF_RT_WITH_PAIRS_ICP"],                       # A/B: the level-resident parts of the persistent launch with two visits per lane (default: one)
-    "p_search": ["-DEF_RT_WITH_PAIRS_SEARCH"],
-    "p_rgb": ["-DEF_RT_WITH_PAIRS_RGB"],
-    "p_all": ["-DEF_RT_WITH_PAIRS_ICP", "-DEF_RT_WITH_PAIRS_SEARCH", "-DEF_RT_WITH_PAIRS_RGB"],
-    "shfl": ["-DEF_RT_SHFL_REDUCE"],                           # A/B: the wave-level sums of the persistent launch through ds_bpermute (rounds 1-5) instead of DPP / permlane moves
-    "sepsc": ["-DEF_SEPARATE_SIN_COS"],                        # A/B: cos(theta) and sin(theta) of the update step as two calls (rounds 1-5) instead of one sincos
-    "pyrstages": ["-DEF_PYR_STAGES"],                          # A/B: one launch per pyramid stage (step l -> l + 1 with the maps + Sobel of level l) instead of two steps + one maps / Sobel launch (measured no faster: off)
-    "deep": ["-DEF_DEEP_PIPE"],                                # A/B: k_se3_accum's multi-round path (1280x960) two rounds deep instead of one (measured slower: off)
-    "sepinputs": ["-DEF_SEPARATE_INPUTS"],                     # A/B: depth pre-processing and the tracker's model maps as two launches instead of one (k_frame_inputs)
-    "sepmerge": ["-DEF_SEPARATE_MERGE"],                       # A/B: the fusion's update pass as its own launch (k_merge) instead of riding on the second index splat
-    "pre_vpair": ["-DEF_PRE_VPAIR"],                           # A/B: the bilateral filter's two pixels per lane four rows apart (round 5) instead of side by side
-    "prep_late": ["-DEF_RT_PREPARE_LATE"],                     # A/B: the sigma-independent half of the photometric rows behind exchange A (rounds 1-5) instead of beside it
-    "p_nostream": ["-DEF_RT_NO_PAIRS_STREAM"],                 # ... and the streaming path with one
-    "sepscan": ["-DEF_SEPARATE_SCAN"],                         # A/B: clean()'s scan of the rows' counts as its own launch (rounds 1-5) instead of inside the scatter's workgroups
-    "endwave": ["-DEF_END_ONE_WAVE"],                          # A/B: k_track_ref_end's two tails behind resultRt on one wavefront (round 5) instead of two
-    "pre_pertap": ["-DEF_PRE_SCALE_PER_TAP"],                  # A/B: the bilateral filter scales the tile value back at every tap instead of once behind the loop
-    "assoc_late": ["-DEF_ASSOC_LATE_LOADS"],                   # A/B: k_associate asks for the filtered depth, the colour and the index-map texels behind its test on the raw depth (rounds 1-5)
-    "resolveall": ["-DEF_RESOLVE_ALL_MAPS"],                   # A/B: the frame's first predictIndices resolves all four index maps (rounds 1-5) instead of the three the association taps
-    "splat_early": ["-DEF_SPLAT_EARLY_LOADS"],                 # A/B: the surface splat asks for all three streams of a surfel at once (default: colour / time and normal only for stable surfels)
-    "resolvetally": ["-DEF_RESOLVE_TALLY"],                    # A/B: denseEnough()'s tally by one atomicAdd per sample from the prediction's resolve pass (rounds 1-5) instead of by the next frame's model-map workgroups
-    "modeone": ["-DEF_FT_MODE_ONE"],                           # A/B: the admission verdict of the persistent launch polled on one word (rounds 4-5) instead of 64 copies
-    "modeone_clocks": ["-DEF_FT_MODE_ONE", "-DEF_STAGE_CLOCKS"],
-    "norepl": ["-DEF_FT_REPL=1", "-DEF_FT_REPL_A=1"],          # A/B: one copy of the all-to-all exchange areas of the persistent launch (rounds 4-5) instead of 64 (totals) / 2 (records)
-    "norepl_clocks": ["-DEF_FT_REPL=1", "-DEF_FT_REPL_A=1", "-DEF_STAGE_CLOCKS"],
-    "lanesweep": ["-DEF_FT_LANE_SWEEP"],                       # A/B: the sweeps of the exchanges with every lane on its own four granules (rounds 4-5) instead of every load instruction on 64 consecutive ones
-    "lanesweep_clocks": ["-DEF_FT_LANE_SWEEP", "-DEF_STAGE_CLOCKS"],
-    "pipepoll": ["-DEF_FT_PIPELINED_POLL"],                    # A/B: the exchanges of the persistent launch keep two polls in flight instead of one (measured 6 % slower: off)
-    "pipepoll_clocks": ["-DEF_FT_PIPELINED_POLL", "-DEF_STAGE_CLOCKS"],
-    "alltaps": ["-DEF_CLEAN_ALL_TAPS"],                        # A/B: clean()'s keep-test asks for the taps of elements the time rules decide anyway (rounds 1-5)
     "resolve": ["-DEF_KEEP_INDEX_RESOLVE"],                    # A/B: both predictIndices of a fusing frame resolved into the four index maps (rounds 1-8: two more launches) instead of their consumers tapping the z-buffer keys
-    "r6m": ["-DEF_SEPARATE_SCAN", "-DEF_END_ONE_WAVE"],        # A/B: both of the above = the launches of commit 7b89629
 }
 SHIM_LIB = os.path.join(HERE, "libefusion.so")          # class ElasticFusion (include/ElasticFusion.h) over the C ABI
 SOURCES = ["ef_track_kernels.hip", "ef_map_kernels.hip", "ef_context.hip", "ef_ferns.hip"]

@@ -54,7 +54,7 @@ struct ef_ctx {
   float* depth_metric_alt = nullptr;
   float* depth_metric_filtered_alt = nullptr;
   hipStream_t in_stream = nullptr;
-  hipEvent_t ev_input_done = nullptr, ev_track_done = nullptr, ev_staged = nullptr;
+  hipEvent_t ev_input_done = nullptr, ev_track_done = nullptr;
   hipEvent_t ev_frame_done[2] = {nullptr, nullptr};   // end of the frame that last used each set of frame images
   int frame_parity = 0;
   int overlap_mode = 1;          // ef_set_input_overlap: 1 = whole input stage after the previous tracker; 2 = copy + bilateral filter already during it
@@ -115,7 +115,7 @@ struct ef_ctx {
   // (eft::ModelMapsArgs::tally_image) instead of one atomic per sample from the prediction's resolve pass
   // (set at ef_create: up to 1 024 samples — 640 x 480 has 768: the resolve pass 13.5 -> 10.3 us, 2072 -> 2091 frames/s; at 1280 x 960, 3 072
   // samples, every model-map workgroup reading them all costs more than the atomics, which hide behind that size's 139 MB: 1029 against 1034,
-  // profiles/r08o_*, r08p_*.  -DEF_RESOLVE_TALLY, the A/B build "resolvetally": never)
+  // profiles/r08o_*, r08p_*)
   bool tally_by_consumer = false;
   bool tally_pending = false;
   // timing
@@ -808,11 +808,7 @@ int process_frame(ef_ctx* c, const uint8_t* rgb_src, const uint16_t* depth_src, 
   const uint8_t* rgb_in = fold_copies ? rgb_src : c->rgb;
   // Round 6: in the single-stream script of a tracked frame the pre-processing and the tracker's model-side maps are ONE launch (k_frame_inputs,
   // at init_icp_model below): two independent kernels, one bound by LDS look-ups, the other by HBM.
-#ifdef EF_SEPARATE_INPUTS   // (A/B build "sepinputs")
-  const bool joint_inputs = false;
-#else
   const bool joint_inputs = track_this && !overlap && !c->timing;
-#endif
   if (!joint_inputs && !efm::preprocess_depth(depth_in, W, H, c->cfg.depth_cut, c->depth_filtered, c->depth_metric, c->depth_metric_filtered, sb, 0u,
                              track_this ? rgb_in : nullptr, c->pyr.nextImage[0], fold_copies ? c->rgb : nullptr, c->bil_table)) {
     c->err = "bilateral weight table missing on this device";
@@ -963,9 +959,7 @@ int process_frame(ef_ctx* c, const uint8_t* rgb_src, const uint16_t* depth_src, 
       timer_begin(c, "indexMap");
       const bool sample_splat = c->ktime_every > 0 && (c->tick % c->ktime_every) == 0 && c->probe_splat.start;
       efm::IndexMaps im_assoc = c->im;   // what the association taps: no colour / time stream (the second predictIndices below writes all four maps)
-#ifndef EF_RESOLVE_ALL_MAPS   // (A/B build "resolveall")
       im_assoc.color_time = nullptr;
-#endif
       // Round 9: neither predictIndices is resolved — their consumers tap the keys (ef_ctx::zbuf_assoc).  Not with stage timers (the update pass is
       // a launch of its own between the two), the reference's download buffer, or a context that closes loops (a deformation's clean(), the
       // predictions that share c->zbuf): those run the resolve launches as before.
@@ -981,11 +975,7 @@ int process_frame(ef_ctx* c, const uint8_t* rgb_src, const uint16_t* depth_src, 
       timer_begin(c, "Fuse::Data+Update");
       // (the update pass — k_merge — rides on the splat of the second predictIndices: one launch less; with stage timers on it stays a launch of
       // its own so that the reference's TICK / TOCK stages keep their meaning)
-#ifdef EF_SEPARATE_MERGE   // (A/B build "sepmerge")
-      const bool defer_merge = false;
-#else
       const bool defer_merge = !c->timing;
-#endif
       efm::fuse(c->cam, c->st->pose_f, c->tick, c->rgb, c->depth_metric, c->depth_metric_filtered, c->im, c->maxDepthProcessed,
                 &c->st->weighting, c->maps[c->cur], &c->st->map_counts[c->cur], c->cand, c->winner, s, defer_merge,
                 keyed ? &key_assoc : nullptr, keyed ? c->zbuf_clean : nullptr);
@@ -1006,7 +996,6 @@ int process_frame(ef_ctx* c, const uint8_t* rgb_src, const uint16_t* depth_src, 
         efm::synthesize_depth(c->cam, c->st->T_cw, c->maps[c->cur], &c->st->map_counts[c->cur], c->maxDepthProcessed, c->cfg.confidence, c->tick,
                               c->tick - c->cfg.time_delta, 65535, c->zbuf, c->synth_depth, s, c->rays);
       timer_begin(c, "Fuse::Copy");
-      c->cs.flip ^= 1;   // (CompactScratch::group_sum: this call's half was cleared by the call before it)
       efm::clean(c->cam, c->st->T_cw, c->tick, c->im, c->cfg.confidence, c->cfg.time_delta, c->maps[c->cur], &c->st->map_counts[c->cur], c->cand,
                  c->winner, c->maps[c->cur ^ 1], &c->st->map_counts[c->cur ^ 1], c->capacity, c->cs, c->overflow, s,
                  c->graph_nodes > 0 ? &def : nullptr, keyed ? &key_clean : nullptr, keyed ? c->zbuf_assoc : nullptr, keyed ? c->im_T16 : nullptr);
@@ -1053,7 +1042,6 @@ int ctx_init(ef_ctx* c) {
   for (auto& e : c->ev_frame_done) EF_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
   EF_HIP(c, hipEventCreateWithFlags(&c->ev_input_done, hipEventDisableTiming));
   EF_HIP(c, hipEventCreateWithFlags(&c->ev_track_done, hipEventDisableTiming));
-  EF_HIP(c, hipEventCreateWithFlags(&c->ev_staged, hipEventDisableTiming));
   EF_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
   for (int i = 0; i < ef_ctx::RING; ++i) {
     EF_HIP(c, hipEventCreateWithFlags(&c->ev_h2d[i], hipEventDisableTiming));
@@ -1167,9 +1155,7 @@ int ctx_init(ef_ctx* c) {
   EF_ALLOC(c, c->traj, (size_t)c->traj_cap * 16);
   // T_wc = identity (ElasticFusion.h: T_wc_curr default) -> publish the float matrices
   hipLaunchKernelGGL(k_init_state, dim3(1), dim3(64), 0, s, c->st, (W / 20) * (H / 20), W * H);
-#ifndef EF_RESOLVE_TALLY
   c->tally_by_consumer = (W / 20) * (H / 20) <= 1024;
-#endif
   efm::build_ray_table(c->cam, c->rays, s);
   const double I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   eft::pose_injected(c->st, I16, false, 1.0f, false, nullptr, 0, s);
@@ -1183,7 +1169,7 @@ void ctx_free(ef_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->stream) eft::persistent_chain_forget(c->stream);   // (a borrowed stream may be destroyed by its owner right after this call)
   if (c->in_stream) (void)hipStreamDestroy(c->in_stream);
-  for (hipEvent_t e : {c->ev_input_done, c->ev_track_done, c->ev_staged, c->ev_frame_done[0], c->ev_frame_done[1]})
+  for (hipEvent_t e : {c->ev_input_done, c->ev_track_done, c->ev_frame_done[0], c->ev_frame_done[1]})
     if (e) (void)hipEventDestroy(e);
   for (void* p : c->allocs) (void)hipFree(p);
   if (c->h_abort) (void)hipHostFree(c->h_abort);

@@ -79,7 +79,7 @@ struct CompactScratch {
   int max_chunks;
   // clean() without its scan launch (round 6): kept elements per GROUP of CLEAN_GROUP rows, added up by k_clean_flags (integer atomics: exact
   // in any order) and read by k_clean_scatter, whose workgroups find their row's offset themselves.  Two halves of max_groups words: a call
-  // adds into half `flip` and zeroes the other one for the call after it (the owner flips before every clean()).  Null: the scan launch.
+  // adds into half `flip` and zeroes the other one for the call after it (clean() owns `flip`: it toggles it at entry).  Null: the scan launch.
   // One sum per 128-byte line (CLEAN_GSTRIDE words apart): with the sums side by side every row's atomic of a frame queued on one or two lines
   // (k_clean_flags 16.9 -> 20.9 us, profiles/r08a_bench_kernel_stats.csv).
   uint32_t* group_sum = nullptr;
@@ -168,7 +168,7 @@ struct Deformation {
 // clean + append; writes the compacted map to `out` and the new count (clamped to capacity) to *count_out_dev
 void clean(const Cam& cam, const float* T_cw16_dev, int time, IndexMaps im, float confThreshold, int timeDelta, SurfelSoA map,
            const unsigned* count_dev, Candidates cand, uint32_t* winner, SurfelSoA out, unsigned* count_out_dev, uint32_t capacity,
-           const CompactScratch& cs, int* overflow_flag, hipStream_t s, const Deformation* deform = nullptr,
+           CompactScratch& cs, int* overflow_flag, hipStream_t s, const Deformation* deform = nullptr,
            // keyed given (no deformation): the keep-test taps the z-buffer instead of im's images; zclear (or null): cols x rows keys of ANOTHER
            // z-buffer that the scatter launch returns to ZBUF_EMPTY; T_keep16_dev (or null): receives a copy of the 16 floats at T_cw16_dev
            const KeyedIndex* keyed = nullptr, unsigned long long* zclear = nullptr, float* T_keep16_dev = nullptr);

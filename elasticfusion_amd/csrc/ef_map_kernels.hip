@@ -464,26 +464,10 @@ __global__ void k_ray_table(const Cam cam, float4* __restrict__ rays) {
 }
 // SPLAT_LANES consecutive lanes share one surfel and take every SPLAT_LANES-th fragment of its sprite: sprite areas vary
 // from 1 to dozens of pixels, and with one surfel per lane a wave waits for its largest sprite
-#ifndef EF_SPLAT_LANES
-#define EF_SPLAT_LANES 4
-#endif
-constexpr int SPLAT_LANES = EF_SPLAT_LANES;
-// The splat sends every fragment to a 64-bit atomicMin on the z-buffer in HBM.  north_star's "LDS-tiled binning" was built in round 3
-// (-DEF_SPLAT_TILED, python -m elasticfusion_amd.build --variant splattiled -DEF_SPLAT_TILED): a workgroup takes a CONTIGUOUS range of
-// SPLAT_CHUNK surfel ids (surfels are created in column-major pixel order and move little, so a short id range falls into a small
-// window of the image), measures that window (bounding box of its sprites, LDS min / max), resolves every fragment inside it with a
-// 64-bit atomicMin on an LDS tile and sends ONE global atomicMin per touched pixel afterwards; fragments outside the tile go to HBM
-// directly.  min is associative and commutative: the z-buffer is bit-identical (the whole -m gpu suite passes on that build,
-// profiles/r03e_gpu_tests_tiled_splat.log).  MEASURED on the mature 640x480 map: 40.3 us against 33.3 us for the all-global version, 1449
-// against 1472 frames/s (profiles/r03e_ab_tiled_vs_global_splat.log, profiles/r03e_tiled_splat_bench_kernel_stats.csv): three barriers, the
-// tile's clear and sweep and the box atomics per 128 surfels cost more than the overdraw they keep out of HBM, whose 64-bit atomics on
-// neighbouring pixels already coalesce in L2.  Not the default.
-#ifndef EF_SPLAT_TILED
+constexpr int SPLAT_LANES = 4;
+// The splat sends every fragment to a 64-bit atomicMin on the z-buffer in HBM.  (An LDS-tiled binning of the fragments, round 3, was bit-identical
+// and slower — 40.3 against 33.3 us, profiles/r03e_ab_tiled_vs_global_splat.log; removed, last present in commit 2372c48.)
 constexpr int SPLAT_GRID = SURFEL_GRID * SPLAT_LANES;
-#else
-constexpr int SPLAT_ROUNDS = 2, SPLAT_CHUNK = SPLAT_ROUNDS * (BLK / SPLAT_LANES), SPLAT_TILE = 4096;
-constexpr int SPLAT_GRID = 4096;   // workgroups; each strides over chunks of SPLAT_CHUNK ids (the count lives on the device)
-#endif
 // Round 6: a fragment's ray comes from the context's table (LUT; the operator tier, which has no context, evaluates it) and dot(S.p, S.n) is
 // taken out of the fragment loop.  (Measured and dropped in the same round: an early-z load before the atomic — 28.0 against 24.5 us, plain or
 // agent-scope: the atomics return nothing, the load makes every fragment wait — and one surfel per lane for the per-surfel part with the quad
@@ -500,19 +484,12 @@ __global__ void __launch_bounds__(BLK) k_surface_splat(const Cam cam, const floa
   const rt34 T = rt34_load16(T16);
   const unsigned count = *count_dev;
   const unsigned sub = threadIdx.x % SPLAT_LANES;
-#ifndef EF_SPLAT_TILED
   const unsigned stride = gridDim.x * blockDim.x / SPLAT_LANES;
   for (unsigned id = (blockIdx.x * blockDim.x + threadIdx.x) / SPLAT_LANES; id < count; id += stride) {
     const float4 pc = map.pos_conf[id];
-#ifdef EF_SPLAT_EARLY_LOADS   // (A/B build "splat_early": all three streams of a surfel in one round trip, whatever its confidence)
-    const float4 ct = map.col_time[id];
-    const float4 nr = map.nrm_rad[id];
-    if (pc.w < confThreshold) continue;
-#else
     if (pc.w < confThreshold) continue;  // unstable surfels (the bulk of a young map) never reach the normal stream
     const float4 ct = map.col_time[id];
     const float4 nr = map.nrm_rad[id];
-#endif
     const Sprite S = make_sprite(cam, T, pc, ct, nr, maxDepth, confThreshold, (float)time, (float)maxTime, (float)timeDelta);
     if (!S.ok) continue;
     const int px0 = max(0, (int)ceilf(S.u - S.hs - 0.5f)), px1 = min(cam.cols - 1, (int)ceilf(S.u + S.hs - 0.5f) - 1);
@@ -530,81 +507,9 @@ __global__ void __launch_bounds__(BLK) k_surface_splat(const Cam cam, const floa
       if (z != z) continue;
       unsigned long long* cell = &zbuf[zi];
       const unsigned long long key = zkey(z, id);
-#if defined(EF_SPLAT_EARLYZ) && EF_SPLAT_EARLYZ == 1
-      // early z (A/B): a fragment that is not nearer than what the cell already shows cannot change it (keys only decrease: a stale value is safe)
-      if (*(volatile unsigned long long*)cell <= key) continue;
-#elif defined(EF_SPLAT_EARLYZ) && EF_SPLAT_EARLYZ == 2
-      if (__hip_atomic_load(cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= key) continue;
-#endif
       atomicMin(cell, key);
     }
   }
-#else
-  (void)rays;
-  __shared__ unsigned long long tile[SPLAT_TILE];
-  __shared__ int box[4];   // min x, min y, max x, max y of the chunk's sprites
-  const unsigned group = threadIdx.x / SPLAT_LANES;
-  for (unsigned c0 = blockIdx.x * SPLAT_CHUNK; c0 < count; c0 += gridDim.x * SPLAT_CHUNK) {
-    if (threadIdx.x == 0) { box[0] = box[1] = 0x7fffffff; box[2] = box[3] = -1; }
-    __syncthreads();
-    Sprite S[SPLAT_ROUNDS];
-    int px0[SPLAT_ROUNDS], px1[SPLAT_ROUNDS], py0[SPLAT_ROUNDS], py1[SPLAT_ROUNDS];
-#pragma unroll
-    for (int r = 0; r < SPLAT_ROUNDS; ++r) {
-      const unsigned id = c0 + r * (BLK / SPLAT_LANES) + group;
-      S[r].ok = false;
-      px0[r] = py0[r] = 0;
-      px1[r] = py1[r] = -1;
-      if (id < count) {
-        const float4 pc = map.pos_conf[id];
-        if (!(pc.w < confThreshold)) {   // unstable surfels (the bulk of a young map) never reach the normal stream
-          const float4 ct = map.col_time[id];
-          const float4 nr = map.nrm_rad[id];
-          S[r] = make_sprite(cam, T, pc, ct, nr, maxDepth, confThreshold, (float)time, (float)maxTime, (float)timeDelta);
-        }
-      }
-      if (S[r].ok) {
-        px0[r] = max(0, (int)ceilf(S[r].u - S[r].hs - 0.5f)); px1[r] = min(cam.cols - 1, (int)ceilf(S[r].u + S[r].hs - 0.5f) - 1);
-        py0[r] = max(0, (int)ceilf(S[r].v - S[r].hs - 0.5f)); py1[r] = min(cam.rows - 1, (int)ceilf(S[r].v + S[r].hs - 0.5f) - 1);
-        if (sub == 0 && px1[r] >= px0[r] && py1[r] >= py0[r]) {
-          atomicMin(&box[0], px0[r]); atomicMin(&box[1], py0[r]);
-          atomicMax(&box[2], px1[r]); atomicMax(&box[3], py1[r]);
-        }
-      }
-    }
-    __syncthreads();
-    const int bx0 = box[0], by0 = box[1];
-    const int bw = box[2] - bx0 + 1;                       // <= 0: no sprite in this chunk
-    const int th = bw > 0 ? min(box[3] - by0 + 1, SPLAT_TILE / bw) : 0;   // rows of the window that fit the tile (0: window wider than the tile)
-    const int tn = bw > 0 ? bw * th : 0;
-    for (int i = threadIdx.x; i < tn; i += BLK) tile[i] = ~0ull;
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < SPLAT_ROUNDS; ++r) {
-      if (!S[r].ok) continue;
-      const unsigned id = c0 + r * (BLK / SPLAT_LANES) + group;
-      const int w = px1[r] - px0[r] + 1, nfrag = w * (py1[r] - py0[r] + 1);
-      for (int f = (int)sub; f < nfrag; f += SPLAT_LANES) {
-        const int fy = f / w, px = px0[r] + (f - fy * w), py = py0[r] + fy;
-        float z;
-        if (!sprite_fragment(cam, S[r], px, py, z)) continue;
-        if (z != z) continue;
-        const int ly = py - by0;
-        if (ly < th) atomicMin(&tile[ly * bw + (px - bx0)], zkey(z, id));
-        else atomicMin(&zbuf[px * cam.rows + py], zkey(z, id));
-      }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < tn; i += BLK) {
-      const unsigned long long k = tile[i];
-      if (k != ~0ull) {
-        const int ly = i / bw, lx = i - ly * bw;
-        atomicMin(&zbuf[(bx0 + lx) * cam.rows + (by0 + ly)], k);
-      }
-    }
-    __syncthreads();   // the tile and the box are re-used by the next chunk
-  }
-#endif
 }
 
 // geometry.glsl:44-60 on the filtered u16 depth (integer pixel coords, forward differences; quirk Q4)
@@ -766,7 +671,6 @@ __global__ void __launch_bounds__(BLK) k_associate(const FuseArgs A, Candidates 
     const f3 vPosLocal = getVertexF(DR, i, j, x, y, cx, cy, inv_fx, inv_fy);
     const bool sel = ((int)x % 2 == (int)ftime % 2 && (int)y % 2 == (int)ftime % 2);
     const bool nb = !(DR.at(i - 1, j) == 0 || DR.at(i, j - 1) == 0 || DR.at(i + 1, j) == 0 || DR.at(i, j + 1) == 0);
-#ifndef EF_ASSOC_LATE_LOADS
     // Round 6: everything the pixel reads — the filtered depth's cross, its colour, the 27 words of its 9 index-map texels — has an address that
     // depends on (i, j) only, so it is asked for HERE, beside the raw depth, not behind the test on the raw depth (a second dependent round
     // trip for every pixel that passes; clamped addresses: a pixel that fails the test reads valid memory it does not use)
@@ -794,13 +698,8 @@ __global__ void __launch_bounds__(BLK) k_associate(const FuseArgs A, Candidates 
       }
     }
     const rt34 pose = rt34_load16(A.pose16);
-#endif
     if (sel && nb && vPosLocal.z > 0 && vPosLocal.z <= A.maxDepth) {
-#ifdef EF_ASSOC_LATE_LOADS
-      const rt34 pose = rt34_load16(A.pose16);
-#endif
       const f3 vPos = xform(pose, vPosLocal);
-#ifndef EF_ASSOC_LATE_LOADS
       // getVertexF / getNormalF (geometry.glsl:21-40) on the values loaded above: the same expressions
       auto vtx = [&](float z, float xx, float yy) { return f3{(xx - cx) * z * inv_fx, (yy - cy) * z * inv_fy, z}; };
       const f3 vPosition_f = vtx(zf_c, x, y);
@@ -809,13 +708,6 @@ __global__ void __launch_bounds__(BLK) k_associate(const FuseArgs A, Candidates 
       const f3 del_x = half_sum(xb, vPosition_f) - half_sum(xf, vPosition_f);
       const f3 del_y = half_sum(yb, vPosition_f) - half_sum(yf, vPosition_f);
       const f3 vNormLocal = normalized(cross(del_x, del_y));
-#else
-      const f3 vPosition_f = getVertexF(DF, i, j, x, y, cx, cy, inv_fx, inv_fy);
-      const uint8_t* c = A.rgb3 + (size_t)(j * cam.cols + i) * 3;
-      const f3 col{(float)c[0] / 255.0f, (float)c[1] / 255.0f, (float)c[2] / 255.0f};
-      const f3 vNormLocal = getNormalF(DF, vPosition_f, i, j, x, y, cx, cy, inv_fx, inv_fy);
-      const float weighting = *A.weighting;
-#endif
       const f3 nW = mul(pose.R, vNormLocal);
       int counter = 0;
       uint32_t best = 0;
@@ -829,27 +721,6 @@ __global__ void __launch_bounds__(BLK) k_associate(const FuseArgs A, Candidates 
       // texels) are issued up front, unconditionally — inside the conditionals of the tap loop they formed chains of up to 48 DEPENDENT
       // round trips (index -> vertex -> normal, tap after tap: the compiler cannot speculate a load across a branch); the 16 taps are then
       // evaluated on registers in the reference's order (a duplicate tap never changes `best`: dist < bestDist is strict)
-#ifdef EF_ASSOC_LATE_LOADS
-      uint32_t idx9[3][3];
-      float4 vc9[3][3], nr9[3][3];
-      uint2 key9[3][3];   // {id, depth_key}: the two halves of a 64-bit key
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const int tx = clampi(i + a - 1, 0, cam.cols - 1);
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {
-          const int ty = clampi(j + b - 1, 0, cam.rows - 1);
-          const int ti = im_texel(A.im, cam, tx, ty);
-          if (KEYED) {
-            key9[a][b] = reinterpret_cast<const uint2*>(A.key.keys)[ti];
-          } else {
-            idx9[a][b] = A.im.index[ti];
-            vc9[a][b] = A.im.vert_conf[ti];
-            nr9[a][b] = A.im.norm_rad[ti];
-          }
-        }
-      }
-#endif
       // KEYED: the second round of loads, again all of them before the first use and none behind a branch — a texel that fails the first two
       // tests of its taps (empty, won by surfel 0, or too far from the pixel in depth: decided on the key) asks for row 0 and is marked 0,
       // which is what `current > 0U` sends away
@@ -998,12 +869,7 @@ __device__ __forceinline__ bool clean_test(const CleanArgs& A, const rt34& T, fl
   // (round 6) the taps only ever turn a 1 into a 0, and the two time rules below override them: an element they send away whatever the taps say
   // — a matched candidate (tag -1: most candidate slots of a mature map), an old unstable surfel — does not ask for its 27 texels
   const float tagTime = ct.w == -2 ? ftime : ct.w;
-#ifdef EF_CLEAN_ALL_TAPS   // (A/B build "alltaps": rounds 1-5)
-  const bool decided = false;
-  (void)tagTime;
-#else
   const bool decided = tagTime == -1 || ((ftime - tagTime) > 20 && pc.w < A.confThreshold);
-#endif
   if (!decided && ftime - ct.w < ftd && localPos.z > 0 && x > 0 && y > 0 && x < (float)cam.cols && y < (float)cam.rows) {
     const Taps3 tx = dedupe_taps(x, cam.cols - 1), ty = dedupe_taps(y, cam.rows - 1);
     uint32_t idx[9];
@@ -1480,9 +1346,6 @@ void combined_predict(const Cam& cam, const float* T_cw16_dev, SurfelSoA map, co
                       float confThreshold, int time, int maxTime, int timeDelta, unsigned long long* zbuf, PredictMaps out, FillMaps fill,
                       const uint16_t* depth_filtered, const uint8_t* rgb3, bool passthroughImage, unsigned* dense_counter, hipStream_t s,
                       unsigned* nonempty_flag, unsigned nonempty_value, unsigned* consumed_mark, unsigned consumed_value, const float* rays4) {
-#ifdef EF_SPLAT_NO_LUT
-  rays4 = nullptr;   // (A/B: every fragment evaluates its ray)
-#endif
   if (rays4)
     hipLaunchKernelGGL(k_surface_splat<true>, dim3(SPLAT_GRID), dim3(BLK), 0, s, cam, T_cw16_dev, map, count_dev, maxDepth, confThreshold,
                        time, maxTime, timeDelta, zbuf, consumed_mark, consumed_value, (const float4*)rays4);
@@ -1537,14 +1400,11 @@ void fuse(const Cam& cam, const float* pose_f16_dev, int time, const uint8_t* rg
 
 void clean(const Cam& cam, const float* T_cw16_dev, int time, IndexMaps im, float confThreshold, int timeDelta, SurfelSoA map,
            const unsigned* count_dev, Candidates cand, uint32_t* winner, SurfelSoA out, unsigned* count_out_dev, uint32_t capacity,
-           const CompactScratch& cs, int* overflow_flag, hipStream_t s, const Deformation* deform, const KeyedIndex* keyed,
+           CompactScratch& cs, int* overflow_flag, hipStream_t s, const Deformation* deform, const KeyedIndex* keyed,
            unsigned long long* zclear, float* T_keep16_dev) {
   CleanArgs A{cam, T_cw16_dev, time, im, confThreshold, timeDelta, keyed ? *keyed : KeyedIndex{}};
-#ifdef EF_SEPARATE_SCAN   // (A/B build "sepscan": rounds 1-5's three launches)
-  const bool fold = false;
-#else
   const bool fold = cs.group_sum != nullptr;
-#endif
+  if (fold) cs.flip ^= 1;   // (this call's half was cleared by the call before it)
   uint32_t* const gnow = fold ? cs.group_sum + (size_t)(cs.flip & 1) * cs.max_groups * CLEAN_GSTRIDE : nullptr;
   uint32_t* const gzero = fold ? cs.group_sum + (size_t)((cs.flip & 1) ^ 1) * cs.max_groups * CLEAN_GSTRIDE : nullptr;
   if (keyed)

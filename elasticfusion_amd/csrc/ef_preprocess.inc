@@ -17,14 +17,10 @@ __device__ __forceinline__ float metric_px(unsigned value, unsigned maxv) {
 //     x + sentinel * 0 == x exactly, so the two sums see the same sequence of non-trivial additions in the same order as the clipped
 //     loops of depth_bilateral.frag:49-72.
 typedef float float2v __attribute__((ext_vector_type(2)));
-#ifdef EF_PRE_VPAIR   // (A/B build "pre_vpair": rounds 5's tile — a lane's two pixels four rows apart)
-constexpr int PRE_TW = 64, PRE_TH = 8, PRE_R = 6, PRE_LW = PRE_TW + 2 * PRE_R, PRE_LH = PRE_TH + 2 * PRE_R;
-#else
 // Round 6: a lane's two pixels are horizontal NEIGHBOURS (x = 2 lane, 2 lane + 1): the two tile values of a tap are adjacent in LDS — one
 // 8-byte read straight into the register pair the packed arithmetic wants (four rows apart they arrived in two registers of two different
 // reads and were paired with a v_mov each: 315 of the kernel's 2 300 VALU instructions) — and the outputs of a lane are adjacent too.
 constexpr int PRE_TW = 128, PRE_TH = 4, PRE_R = 6, PRE_LW = PRE_TW + 2 * PRE_R + 4 /* rows of 576 bytes: 16-byte aligned */, PRE_LH = PRE_TH + 2 * PRE_R;
-#endif
 constexpr int BIL_ROWS = 27, BIL_COLS = 400, BIL_ZERO = 396;   // columns >= BIL_ZERO hold +0 (|d| >= 396: 396^2 * 0.000555556 > 87)
 constexpr float BIL_OUTSIDE = 1.0e6f;                            // sentinel of a tap outside the image
 struct BilRows {   // (|dy|, |dx|) -> first float of the table row of dx^2 + dy^2
@@ -64,60 +60,6 @@ __device__ __forceinline__ void preprocess_tile(int bx, int by, const uint16_t* 
       if (q < BIL_ROWS * BIL_COLS / 4) dst[q] = src[q];
     }
   }
-#ifdef EF_PRE_VPAIR
-  for (int i = t; i < PRE_LH * PRE_LW; i += 256) {
-    const int ly = i / PRE_LW, lx = i - ly * PRE_LW;
-    const int gx = x0 + lx - PRE_R, gy = y0 + ly - PRE_R;
-    tile[ly][lx] = (gx >= 0 && gx < cols && gy >= 0 && gy < rows) ? (float)raw[gy * cols + gx] : BIL_OUTSIDE;
-  }
-  __syncthreads();
-  const int x = x0 + tx, ya = y0 + ty, yb = ya + 4;
-  if (x >= cols) return;
-  const bool in_a = ya < rows, in_b = yb < rows;
-  // Round 6: the frame's level-0 intensity image (bgr2IntensityKernel, cudafuncs.cu:584-596 — populateRGBDData(frame)) and the context's copy of
-  // the colour image ride along: six bytes per lane in the shadow of 169 LDS look-ups, one launch less per frame (k_intensity_both, 5 us).
-  if (rgb3) {
-    const int ys[2] = {ya, yb};
-    const bool ins[2] = {in_a, in_b};
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      if (!ins[q]) continue;
-      const size_t i = (size_t)ys[q] * cols + x;
-      const uint8_t r = rgb3[i * 3], g = rgb3[i * 3 + 1], b = rgb3[i * 3 + 2];
-      next0[i] = intensity_of((float)r, (float)g, (float)b);
-      if (rgb_keep) { rgb_keep[i * 3] = r; rgb_keep[i * 3 + 1] = g; rgb_keep[i * 3 + 2] = b; }
-    }
-  }
-  const float2v value = {tile[ty + PRE_R][tx + PRE_R], tile[ty + 4 + PRE_R][tx + PRE_R]};
-  const unsigned va = in_a ? (unsigned)value.x : 0u, vb = in_b ? (unsigned)value.y : 0u;
-  const bool gate_a = in_a && !(va > maxv || va < 300U), gate_b = in_b && !(vb > maxv || vb < 300U);
-  float2v sum1 = (float2v)(0.0f), sum2 = (float2v)(0.0f);
-  if (gate_a || gate_b) {
-#pragma unroll
-    for (int dy = -PRE_R; dy <= PRE_R; ++dy) {
-#pragma unroll
-      for (int dx = -PRE_R; dx <= PRE_R; ++dx) {
-        const float* row = tab + BIL.base[dy < 0 ? -dy : dy][dx < 0 ? -dx : dx];   // (an immediate once both loops are unrolled)
-        const float2v tmp = {tile[ty + PRE_R + dy][tx + PRE_R + dx], tile[ty + 4 + PRE_R + dy][tx + PRE_R + dx]};
-        const float2v d = value - tmp;
-        const int ia = (int)fminf(fabsf(d.x), (float)BIL_ZERO), ib = (int)fminf(fabsf(d.y), (float)BIL_ZERO);
-        const float2v w = {row[ia], row[ib]};
-        sum1 = sum1 + tmp * w;
-        sum2 = sum2 + w;
-      }
-    }
-  }
-  if (in_a) {
-    const uint16_t f = gate_a ? (uint16_t)(unsigned)roundf(sum1.x / sum2.x) : (uint16_t)0;
-    filtered[ya * cols + x] = f;
-    if (WITH_METRIC) { metric[ya * cols + x] = metric_px(va, maxv); metric_filtered[ya * cols + x] = metric_px(f, maxv); }
-  }
-  if (in_b) {
-    const uint16_t f = gate_b ? (uint16_t)(unsigned)roundf(sum1.y / sum2.y) : (uint16_t)0;
-    filtered[yb * cols + x] = f;
-    if (WITH_METRIC) { metric[yb * cols + x] = metric_px(vb, maxv); metric_filtered[yb * cols + x] = metric_px(f, maxv); }
-  }
-#else
   constexpr int LWU = PRE_TW + 2 * PRE_R;   // columns of the tile that are filled
   for (int i = t; i < PRE_LH * LWU; i += 256) {
     const int ly = i / LWU, lx = i - ly * LWU;
@@ -157,22 +99,15 @@ __device__ __forceinline__ void preprocess_tile(int bx, int by, const uint16_t* 
         const float2v d4 = value4 - tmp4;   // 4 (value - tmp), exactly
         const int ia = (int)fminf(fabsf(d4.x), 4.0f * BIL_ZERO), ib = (int)fminf(fabsf(d4.y), 4.0f * BIL_ZERO);   // byte offsets
         const float2v w = {*(const float*)((const char*)row + ia), *(const float*)((const char*)row + ib)};
-#ifdef EF_PRE_SCALE_PER_TAP   // (A/B build "pre_pertap": the tile value back to the depth at every tap, as first built)
-        const float2v tmp = tmp4 * 0.25f;
-        sum1 = sum1 + tmp * w;
-#else
         // sum1 is carried as 4 x the shader's sum: (4 tmp) * w and the additions of such products are 4 x the unscaled ones BIT FOR BIT (a power of
         // two commutes with rounding while nothing is subnormal or overflows: 300 <= tmp < 2^16, w = 0 or >= e^-87 > FLT_MIN, every term >= 0),
         // so one multiplication by 0.25 behind the loop replaces 169 inside it
         sum1 = sum1 + tmp4 * w;
-#endif
         sum2 = sum2 + w;
       }
     }
   }
-#ifndef EF_PRE_SCALE_PER_TAP
   sum1 = sum1 * 0.25f;
-#endif
   {
     const uint16_t f = gate_a ? (uint16_t)(unsigned)roundf(sum1.x / sum2.x) : (uint16_t)0;
     filtered[y * cols + xa] = f;
@@ -183,5 +118,4 @@ __device__ __forceinline__ void preprocess_tile(int bx, int by, const uint16_t* 
     filtered[y * cols + xb] = f;
     if (WITH_METRIC) { metric[y * cols + xb] = metric_px(vb, maxv); metric_filtered[y * cols + xb] = metric_px(f, maxv); }
   }
-#endif
 }

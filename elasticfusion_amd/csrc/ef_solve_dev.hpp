@@ -92,8 +92,8 @@ __device__ __forceinline__ int se3_member_of(int i, int j) {
 
 // Eigen::LDLT-style solve of the 6x6 system held one element per lane (lane e < 36 holds A[e/6][e%6], bitwise
 // symmetric); b in S.b.  Mirrors efl::ldlt_solve<double,6> operation for operation.  Result in S.x (all 6 entries).
-// (Rounds 2-4's version, kept for the A/B and the host emulation — tests/test_wave_emulation.py runs both against the scalar statement;
-// the update step runs ldlt6_every_lane below.)
+// (Rounds 2-4's version, kept for the operator tier and the host emulation — tests/test_wave_emulation.py runs both against the scalar
+// statement; the update step runs ldlt6_every_lane below.)
 __device__ __forceinline__ void ldlt6_wave(double a, SolveScratch& S) {
   const int lane = threadIdx.x & 63;
   const int e = lane < 36 ? lane : 0;
@@ -387,11 +387,7 @@ __device__ __forceinline__ void gauss_newton_update_wave(eft::TrackState* st, ef
   }
   wave_sync();
   EF_STAMP(st, 4);
-#ifdef EF_LDLT_WAVE
-  ldlt6_wave(a, S);         // rounds 2-4 (A/B: python -m elasticfusion_amd.build --variant ldlt_wave)
-#else
   ldlt6_every_lane(a, S);   // round 5: 2.14 -> 1.88 us per update step (profiles/r05l_clocks_ldlt.jsonl), 16 registers fewer in k_track_ref
-#endif
   EF_STAMP(st, 5);
   // ---- computeUpdateSE3 (OdometryProvider.h:73-96): rodrigues(result[3..5]) and the 4x4 increment ----
   {
@@ -404,7 +400,7 @@ __device__ __forceinline__ void gauss_newton_update_wave(eft::TrackState* st, ef
       const int k = r * 3 + c;
       val = (r == c) ? 1.0 : 0.0;
       if (theta >= DBL_EPSILON) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(EF_SEPARATE_SIN_COS)
+#ifdef __HIP_DEVICE_COMPILE__
         // one sincos instead of cos and sin apart (155 against 294 VALU instructions of one dependent double-precision chain on the critical path of
         // every iteration): ocml's sincos returns, bit for bit, what its sin and its cos return (tools/probe/sincos_probe.hip on MI355X: 2^24 arguments from
         // subnormal to 1e300, zero differences — profiles/r06x_sincos_probe.json)

@@ -19,14 +19,8 @@ constexpr int FT_SY_OFF = FT_GA_OFF + 4 * 256;                // FtSync
 // Round 6: the two areas EVERY workgroup polls — the 58 totals of exchange B's second hop and the 256 records of exchange A — exist FT_REPL
 // times, 8 KB apart; a publisher stores every copy, workgroup w (XCD w % 8) polls copy w % FT_REPL.  A poll goes past the L2s: with one copy,
 // 256 wavefronts hammer the same four (B) / thirty-two (A) lines, and the stores they wait for queue behind their requests (the counter-experiment,
-// twice the polls: exchange B 3.45 -> 4.96 us, profiles/r08i_*).  (k_track_ref only; -DEF_FT_REPL=1: one copy, the A/B build "norepl".)
-#ifndef EF_FT_REPL
-#define EF_FT_REPL 64
-#endif
-#ifndef EF_FT_REPL_A
-#define EF_FT_REPL_A 2
-#endif
-constexpr int FT_REPL = EF_FT_REPL, FT_REPL_A = EF_FT_REPL_A > 8 ? 8 : EF_FT_REPL_A;   // copies of the totals (B) / of the records (A)
+// twice the polls: exchange B 3.45 -> 4.96 us, profiles/r08i_*).  (k_track_ref only.)
+constexpr int FT_REPL = 64, FT_REPL_A = 2;                    // copies of the totals (B) / of the records (A)
 constexpr int FT_REPL_STRIDE = 1024;                          // u64 words between two copies
 constexpr int FT_MODE_WORD = 128;                             // word of every copy of the totals that carries the admission verdict (granule {FT_MODE_*, epoch})
 constexpr int FT_G2R_OFF = 49152;                             // u64 G2R[FT_REPL <= 64][1024] (64 used per copy)
@@ -101,26 +95,12 @@ __device__ __forceinline__ bool ft_sweep(const unsigned long long* base, int str
 #pragma unroll
   for (int i = 0; i < 4; ++i) { ok[i] = 4 * lane + i >= n; data[i] = 0u; }
   if (*dead_s) return false;
-#ifdef EF_FT_PIPELINED_POLL
-  // Two sweeps in flight (A/B build "pipepoll", round 6): a poll is a round trip past the L2s; with one at a time a granule that lands just behind a
-  // poll's request waits a whole round trip for the next one.  MEASURED: slower — exchange B 3.45 -> 4.96 us, exchange A 2.19 -> 2.74 us, the launch
-  // 333 -> 379 us, 1942 -> 1828 frames/s (profiles/r08i_*): twice the polls on the same few lines delay the very stores they wait for.  Off.
-  unsigned long long gp[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) gp[i] = ok[i] ? 0ull : ft_get(base + (size_t)stride * (4 * lane + i));
-#endif
+  // (two sweeps in flight instead of one measured slower: exchange B 3.45 -> 4.96 us, 1942 -> 1828 frames/s, profiles/r08i_*; removed, last
+  // present in commit 2372c48)
   for (int spin = 0; spin < FT_SPIN; ++spin) {
     unsigned long long g[4];
-#ifdef EF_FT_PIPELINED_POLL
-    unsigned long long gn[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) gn[i] = ok[i] ? 0ull : ft_get(base + (size_t)stride * (4 * lane + i));
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { g[i] = gp[i]; gp[i] = gn[i]; }
-#else
 #pragma unroll
     for (int i = 0; i < 4; ++i) g[i] = ok[i] ? 0ull : ft_get(base + (size_t)stride * (4 * lane + i));
-#endif
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       if (!ok[i] && (unsigned)(g[i] >> 32) == epoch) { ok[i] = true; data[i] = (unsigned)g[i]; }
@@ -139,32 +119,13 @@ __device__ __forceinline__ bool ft_sweep_pairs(const unsigned long long* GA, uns
   bool ok[4] = {false, false, false, false};
   sa = sb = 0;
   if (*dead_s) return false;
-#ifdef EF_FT_PIPELINED_POLL
-  unsigned long long pa[4], pb[4];   // (two sweeps in flight: see ft_sweep)
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    pa[i] = ft_get(GA + 2 * (4 * lane + i));
-    pb[i] = ft_get(GA + 2 * (4 * lane + i) + 1);
-  }
-#endif
   for (int spin = 0; spin < FT_SPIN; ++spin) {
     unsigned long long ga[4], gb[4];
-#ifdef EF_FT_PIPELINED_POLL
-    unsigned long long na_[4], nb_[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      na_[i] = ok[i] ? 0ull : ft_get(GA + 2 * (4 * lane + i));
-      nb_[i] = ok[i] ? 0ull : ft_get(GA + 2 * (4 * lane + i) + 1);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { ga[i] = pa[i]; gb[i] = pb[i]; pa[i] = na_[i]; pb[i] = nb_[i]; }
-#else
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       ga[i] = ok[i] ? 0ull : ft_get(GA + 2 * (4 * lane + i));
       gb[i] = ok[i] ? 0ull : ft_get(GA + 2 * (4 * lane + i) + 1);
     }
-#endif
 #pragma unroll
     for (int i = 0; i < 4; ++i)
       if (!ok[i] && (unsigned)(ga[i] >> 32) == epoch && (unsigned)(gb[i] >> 32) == epoch) { ok[i] = true; sa += (int)(unsigned)ga[i]; sb += (int)(unsigned)gb[i]; }
@@ -180,15 +141,9 @@ __device__ __forceinline__ bool ft_sweep_pairs(const unsigned long long* GA, uns
 // instead of every lane on its own four (ft_sweep: a load instruction touched 16 lines, ft_sweep_pairs: 32 — a sweep asked the memory side for
 // 64 / 256 line pieces where 16 / 32 carry everything).  The producers store column c's granule at ft_slot(c) = 64 (c % 4) + c / 4, so lane l
 // still ends up with columns 4 l .. 4 l + 3 — what the rest of the tree expects.
-#ifndef EF_FT_LANE_SWEEP   // (-DEF_FT_LANE_SWEEP: the A/B build "lanesweep", rounds 4-5's addressing)
+// (Every lane on its own four granules, rounds 4-5's addressing: removed, last present in commit 2372c48.)
 __device__ __forceinline__ int ft_slot(int col) { return 64 * (col & 3) + (col >> 2); }
-#else
-__device__ __forceinline__ int ft_slot(int col) { return col; }
-#endif
 __device__ __forceinline__ bool ft_sweep_row(const unsigned long long* row, unsigned epoch, volatile int* dead_s, FtSync* Y, unsigned (&data)[4]) {
-#ifdef EF_FT_LANE_SWEEP
-  return ft_sweep(row, 1, FT_WGS, epoch, dead_s, Y, data);
-#else
   const int lane = threadIdx.x & 63;
   bool ok[4] = {false, false, false, false};
 #pragma unroll
@@ -208,14 +163,10 @@ __device__ __forceinline__ bool ft_sweep_row(const unsigned long long* row, unsi
   __hip_atomic_store(&Y->abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   *dead_s = 1;
   return false;
-#endif
 }
 // exchange A: the 512 granules {count}{sum} of the 256 records, granule 64 i + l in lane l: an even lane only ever holds counts, an odd lane sums
 // (both integer sums are order-free; every granule carries its own tag and the sweep waits for all of them)
 __device__ __forceinline__ bool ft_sweep_records(const unsigned long long* GA, unsigned epoch, volatile int* dead_s, FtSync* Y, int& sa, int& sb) {
-#ifdef EF_FT_LANE_SWEEP
-  return ft_sweep_pairs(GA, epoch, dead_s, Y, sa, sb);
-#else
   const int lane = threadIdx.x & 63;
   bool ok[8];
 #pragma unroll
@@ -245,7 +196,6 @@ __device__ __forceinline__ bool ft_sweep_records(const unsigned long long* GA, u
   __hip_atomic_store(&Y->abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   *dead_s = 1;
   return false;
-#endif
 }
 // hop 2 of exchange B: lanes < na poll the totals G2[lane]
 __device__ __forceinline__ bool ft_poll_totals(const unsigned long long* G2, int na, unsigned epoch, volatile int* dead_s, FtSync* Y, float& value) {
@@ -253,21 +203,11 @@ __device__ __forceinline__ bool ft_poll_totals(const unsigned long long* G2, int
   bool ok = lane >= na;
   value = 0.f;
   if (*dead_s) return false;
-#ifdef EF_FT_PIPELINED_POLL
-  unsigned long long gp = ok ? 0ull : ft_get(G2 + lane);   // (two polls in flight: see ft_sweep)
-#endif
   for (int spin = 0; spin < FT_SPIN; ++spin) {
-#ifdef EF_FT_PIPELINED_POLL
-    const unsigned long long gn = ok ? 0ull : ft_get(G2 + lane);
-    const unsigned long long g = gp;
-    gp = gn;
-    if (!ok && (unsigned)(g >> 32) == epoch) { ok = true; value = __uint_as_float((unsigned)g); }
-#else
     if (!ok) {
       const unsigned long long g = ft_get(G2 + lane);
       if ((unsigned)(g >> 32) == epoch) { ok = true; value = __uint_as_float((unsigned)g); }
     }
-#endif
     if (__all(ok)) return true;
     if ((spin & 127) == 127 && (__hip_atomic_load(&Y->abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) || *dead_s)) { *dead_s = 1; return false; }
     if (spin > 8) __builtin_amdgcn_s_sleep(1);

@@ -114,9 +114,6 @@ __global__ void __launch_bounds__(FT_BLOCK) k_track_fast(const FtArgs A, TrackSt
     for (int a = 0; a < NA; ++a) P[(size_t)a * 256] = 0.f;   // the totals k_track_end's head reads (ng = 1)
     return;
   }
-#ifdef EF_FT_NO_ADMISSION   // development (A/B of the admission step's cost): every launch is taken for resident
-  if (t == 128) mode_s = FT_MODE_PERSISTENT;
-#else
   if (t == 64) ft_put(&Y->arrive[wg], 1u, A.epoch);
   if (wg == 0 && wave == 7) {
     bool ok[4] = {false, false, false, false};
@@ -153,7 +150,6 @@ __global__ void __launch_bounds__(FT_BLOCK) k_track_fast(const FtArgs A, TrackSt
     }
     mode_s = m;   // 0: no verdict within seconds (workgroup 0 never ran?): treated like a time-out below
   }
-#endif
   // ---- k_track_begin, by every workgroup for itself; workgroup 0 also leaves the global side of it ----
   if (t == 0) {
     dead_s = (int)__hip_atomic_load(&Y->abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -457,30 +457,6 @@ __global__ void k_vn_sobel_levels(const VNLevels V, const SobelLevels S) {
   else sobel_mask_px(S, z - NUM_PYRS, x, y);
 }
 
-// One STAGE of the frame's pyramids as one launch (round 6; A/B build "pyrstages", not the default: see build_pyramids): the pyramid step level
-// l -> l + 1 of up to four images AND the vertex / normal maps and the Sobel + photometric gates of level l — which read level l only, i.e. what
-// the previous stage (or, for l = 0, the input launch) wrote.  blockIdx.z: 0 .. n_pyr - 1 pyramid jobs, then the maps, then the Sobel.
-struct StageJobs {
-  PyrJobs J;
-  int n_pyr;
-  VNLevels V;
-  SobelLevels S;
-  int level;
-};
-__global__ void k_pyramid_stage(const StageJobs A) {
-  const int z = blockIdx.z, x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
-  if (z < A.n_pyr) {
-    if (x >= A.J.scols / 2 || y >= A.J.srows / 2) return;
-    if (A.J.type[z] == 0) pyr_down_u16_px((const uint16_t*)A.J.src[z], A.J.scols, A.J.srows, (uint16_t*)A.J.dst[z], x, y);
-    else if (A.J.type[z] == 1) pyr_down_gauss_f_px((const float*)A.J.src[z], A.J.scols, A.J.srows, (float*)A.J.dst[z], x, y);
-    else pyr_down_uchar_gauss_px((const uint8_t*)A.J.src[z], A.J.scols, A.J.srows, (uint8_t*)A.J.dst[z], x, y);
-  } else if (z == A.n_pyr) {
-    vmap_nmap_px(A.V, A.level, x, y);
-  } else {
-    sobel_mask_px(A.S, A.level, x, y);
-  }
-}
-
 // projectPointsKernel, cudafuncs.cu:670-688
 __device__ __forceinline__ f3 project_point(int x, int y, float z, float invFx, float invFy, float cx, float cy) {
   return {(float)((x - cx) * z * invFx), (float)((y - cy) * z * invFy), z};
@@ -1354,7 +1330,7 @@ __device__ __forceinline__ void visit_stage2b(const IcpView& IV, const RgbView& 
 // norms are compared as squares (IcpView::dist2Max / sine2Max: ef_device.hpp, sq_le_max — the same verdict on every input).  133 VALU
 // instructions per row.  Operation for operation icp_row / rgb_row: same operands, same order, same roundings; bit-identical rows.
 // ------------------------------------------------------------------------------------------
-#if defined(EF_NO_FMA) && !defined(EF_NO_VISIT_PAIRS)   // (-DEF_NO_VISIT_PAIRS: the A/B build, build.VARIANTS["nopairs"])
+#ifdef EF_NO_FMA   // (the fast build keeps one visit per lane)
 #define EF_VISIT_PAIRS 1
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 struct p3 { f32x2 x, y, z; };   // a point / vector of each of the two visits
@@ -1505,20 +1481,14 @@ __device__ __forceinline__ void accum_quads(const IcpView& IV, const RgbView& RV
 #ifdef EF_VISIT_PAIRS
   if constexpr ((ICP || PACKED) && CH % 2 == 0) {   // two visits per lane: steps 2 u, 2 u + 1 of a chunk as one packed evaluation
     constexpr int NP = CH / 2;
-    // DEEP: two rounds in flight instead of one.  Built and measured at 1280 x 960 (five rounds of CH = 4): k_se3_accum 22.9 us against 21.5 with
-    // one (profiles/r07c_1280x960_kernel_stats*.csv) — a third set of loads queues behind the others in the CU's one address pipe (the same
-    // finding as CH = 10 in round 3) and costs a register copy per value and round.  Off; the code stays for the A/B (-DEF_DEEP_PIPE).
-#ifdef EF_DEEP_PIPE
-    constexpr bool DEEP = CH <= 4;
-#else
-    constexpr bool DEEP = false;
-#endif
+    // (two rounds in flight instead of one measured slower at 1280 x 960: k_se3_accum 22.9 us against 21.5, profiles/r07c_1280x960_kernel_stats*.csv;
+    // removed, last present in commit 2372c48)
     auto pixel = [&](int s) { const int k = 4 * s + jl; return (s < S && k < K) ? k * VTHREADS + g : N; };
     float sigma = in.sigma_fixed;
     // A round = CH steps = NP packed evaluations; the next round's loads are issued before this round's outer products.
     if constexpr (ICP) {
       const IcpPose Pu = icp_pose_uniform(P);
-      IcpLoads2 L[NP], Ln[DEEP ? NP : 1];
+      IcpLoads2 L[NP];
       IcpGathers2 G[NP];
       p3 vg[NP], scp[NP];
 #pragma unroll
@@ -1529,17 +1499,9 @@ __device__ __forceinline__ void accum_quads(const IcpView& IV, const RgbView& RV
         G[u] = icp2_stage2a(IV, L[u], scp[u]);
       }
       EF_ASTAMP(1);
-      if constexpr (DEEP) {
-#pragma unroll
-        for (int u = 0; u < NP; ++u) Ln[u] = L[u];
-        if (CH < S) {   // uniform
-#pragma unroll
-          for (int u = 0; u < NP; ++u) Ln[u] = icp2_stage1(IV, pixel(CH + 2 * u), pixel(CH + 2 * u + 1), N);
-        }
-      }
 #pragma unroll 1
       for (int s0 = 0; s0 < S; s0 += CH) {
-        if (!DEEP && s0 > 0) {   // (one round deep: this round's gathers behind its loads, issued before the previous round's outer products)
+        if (s0 > 0) {   // (one round deep: this round's gathers behind its loads, issued before the previous round's outer products)
 #pragma unroll
           for (int u = 0; u < NP; ++u) {
             icp2_transform(Pu, L[u], vg[u], scp[u]);
@@ -1551,21 +1513,8 @@ __device__ __forceinline__ void accum_quads(const IcpView& IV, const RgbView& RV
         for (int u = 0; u < NP; ++u) icp2_stage2b(IV, Pu, L[u], G[u], vg[u], scp[u], rows[2 * u], rows[2 * u + 1]);
         if (s0 == 0) EF_ASTAMP(2);
         if (s0 + CH < S) {   // uniform
-          if constexpr (DEEP) {   // the next round's gathers, the round after's loads
 #pragma unroll
-            for (int u = 0; u < NP; ++u) {
-              L[u] = Ln[u];
-              icp2_transform(Pu, L[u], vg[u], scp[u]);
-              G[u] = icp2_stage2a(IV, L[u], scp[u]);
-            }
-            if (s0 + 2 * CH < S) {
-#pragma unroll
-              for (int u = 0; u < NP; ++u) Ln[u] = icp2_stage1(IV, pixel(s0 + 2 * CH + 2 * u), pixel(s0 + 2 * CH + 2 * u + 1), N);
-            }
-          } else {
-#pragma unroll
-            for (int u = 0; u < NP; ++u) L[u] = icp2_stage1(IV, pixel(s0 + CH + 2 * u), pixel(s0 + CH + 2 * u + 1), N);
-          }
+          for (int u = 0; u < NP; ++u) L[u] = icp2_stage1(IV, pixel(s0 + CH + 2 * u), pixel(s0 + CH + 2 * u + 1), N);
         }
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
@@ -1600,14 +1549,9 @@ __device__ __forceinline__ void accum_quads(const IcpView& IV, const RgbView& RV
           }
         }
       };
-      Rgb2 X[NP], Xn[DEEP ? NP : 1];
+      Rgb2 X[NP];
       load(0, X);
       gather(X);
-      if constexpr (DEEP) {
-#pragma unroll
-        for (int u = 0; u < NP; ++u) Xn[u] = X[u];
-        if (CH < S) load(CH, Xn);   // uniform
-      }
       if (with_slots) {
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
@@ -1618,20 +1562,11 @@ __device__ __forceinline__ void accum_quads(const IcpView& IV, const RgbView& RV
       }
 #pragma unroll 1
       for (int s0 = 0; s0 < S; s0 += CH) {
-        if (!DEEP && s0 > 0) gather(X);
+        if (s0 > 0) gather(X);
         float rows[CH][8];
 #pragma unroll
         for (int u = 0; u < NP; ++u) rgb2_rows(RV, sigma, X[u].corr, X[u].gx, X[u].gy, d0[u], valid[u], rows[2 * u], rows[2 * u + 1]);
-        if (s0 + CH < S) {   // uniform
-          if constexpr (DEEP) {   // the next round's gathers, the round after's loads
-#pragma unroll
-            for (int u = 0; u < NP; ++u) X[u] = Xn[u];
-            gather(X);
-            if (s0 + 2 * CH < S) load(s0 + 2 * CH, Xn);
-          } else {
-            load(s0 + CH, X);
-          }
-        }
+        if (s0 + CH < S) load(s0 + CH, X);   // uniform
 #pragma unroll
         for (int u = 0; u < CH; ++u) {
           if (s0 + u < S) quad_rows_accumulate(rows[u], s0 + u, K, c);   // uniform; phase B
@@ -3400,39 +3335,8 @@ void build_pyramids(const Pyramid& p, const uint16_t* depth_filtered, Intr k, fl
   // (both pyramid steps as ONE launch — a workgroup computing the 36 x 36 level-1 pixels its 16 x 16 level-2 tile reads, then the tile — was
   // built and measured in round 6: 25.2 us against 8.0 + 5.4 for the two launches: six dependent 25-tap trips per thread; dropped,
   // profiles/r06q_kernel_stats_fused_pyramid_steps.csv)
-  // (one launch per pyramid STAGE — the step level l -> l + 1 together with the vertex / normal maps and the Sobel of level l, which read level l
-  // only: k_pyramid_stage — was built and measured in round 6: 1934 against 1939 frames/s same box, 3 x 18.7 us against 2 x 13.5 + 25.5 at
-  // 1280 x 960, profiles/r07d_ab_pyramid_stages.log: the level-0 maps no longer wait for two launches, but the two small stages cost what the one
-  // joint launch of all levels cost; off, kept as the A/B build "pyrstages")
-#ifdef EF_PYR_STAGES
-  {
-    StageJobs A{};
-    for (int i = 0; i < NUM_PYRS; ++i) {
-      A.V.depth[i] = i == 0 ? depth_filtered : p.depth_tmp[i];
-      A.V.vmap[i] = p.vmap_curr[i]; A.V.nmap[i] = p.nmap_curr[i];
-      A.V.cols[i] = p.W(i); A.V.rows[i] = p.H(i);
-      A.V.k[i] = intr_level(k, i);
-    }
-    A.V.cutoff = cutoff;
-    A.S = sobel_levels_of(p);
-    for (int i = 0; i < NUM_PYRS; ++i) {   // stage i: level i -> i + 1 (not behind the last level), maps + Sobel of level i
-      A.level = i;
-      A.n_pyr = 0;
-      if (i + 1 < NUM_PYRS) {
-        A.J.src[0] = i == 0 ? (const void*)depth_filtered : (const void*)p.depth_tmp[i]; A.J.dst[0] = p.depth_tmp[i + 1]; A.J.type[0] = 0;
-        A.J.src[1] = p.lastDepth[i]; A.J.dst[1] = p.lastDepth[i + 1]; A.J.type[1] = 1;
-        A.J.src[2] = p.lastImage[i]; A.J.dst[2] = p.lastImage[i + 1]; A.J.type[2] = 2;
-        A.J.src[3] = p.nextImage[i]; A.J.dst[3] = p.nextImage[i + 1]; A.J.type[3] = 2;
-        A.J.scols = p.W(i); A.J.srows = p.H(i);
-        A.n_pyr = 4;
-      }
-      dim3 g = tile_grid(p.W(i), p.H(i));
-      g.z = A.n_pyr + 1 + (with_sobel ? 1 : 0);
-      hipLaunchKernelGGL(k_pyramid_stage, g, tile_block(), 0, s, A);
-    }
-    return;
-  }
-#endif
+  // (one launch per pyramid STAGE — step l -> l + 1 with the maps and the Sobel of level l — measured no faster in round 6: 1934 against 1939
+  // frames/s, profiles/r07d_ab_pyramid_stages.log; removed, last present in commit 2372c48)
   for (int i = 0; i + 1 < NUM_PYRS; ++i) {
     PyrJobs J;
     J.src[0] = i == 0 ? (const void*)depth_filtered : (const void*)p.depth_tmp[i]; J.dst[0] = p.depth_tmp[i + 1]; J.type[0] = 0;

@@ -35,11 +35,6 @@ __device__ __forceinline__ int rt_pixel(int col, int idx) { return (idx >> 6) * 
 // move per step — row / half-wave swaps and in-row DPP shifts — instead of a trip through the LDS crossbar, 6 dependent ds_bpermute ≈ 0.15 us on
 // the critical path of every exchange); lanes off that path hold other values than before, nobody reads them
 __device__ __forceinline__ float warp32_pair_tree(float x) {
-#ifdef EF_RT_SHFL_REDUCE   // (A/B build "shfl": rounds 1-5's formulation)
-#pragma unroll
-  for (int off = 16; off > 0; off >>= 1) x += __shfl_down(x, off, 32);
-  return x + __shfl(x, 32, 64);
-#endif
   x += down16(x);        // lanes 0..15 and 32..47: + lane i + 16
   x += row_down<8>(x);
   x += row_down<4>(x);
@@ -49,11 +44,6 @@ __device__ __forceinline__ float warp32_pair_tree(float x) {
 }
 // integer sum over the wavefront, in lane 0 (order-free: exact)
 __device__ __forceinline__ int wave_sum_lane0(int v) {
-#ifdef EF_RT_SHFL_REDUCE
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-#endif
   float x = __int_as_float(v);   // (moved as bits: permlane / DPP moves do not interpret them)
   auto add = [](float a, float b) { return __int_as_float(__float_as_int(a) + __float_as_int(b)); };
   x = add(x, down32(x));
@@ -211,21 +201,11 @@ struct RtNoWait { float sigma; __device__ __forceinline__ float operator()() con
 constexpr int RT_RGB_WORDS = 8;   // per visit: 5 words of the search (below) + 3 of rt_rgb_prepare
 constexpr int RT_ICP_STEP_BYTES = 4 * 6 * 64 * 4, RT_RGB_STEP_BYTES = 4 * RT_RGB_WORDS * 64 * 4;   // per step, all four wavefronts of a term
 constexpr int RT_CH = 5;    // steps whose gathers are in flight together (640 x 480 level 0: all of them)
-constexpr int RT_CH2 = 6;   // the same for the two-visits-per-lane functions: three packed evaluations of two visits each
 // Which parts of the launch evaluate two visits per lane.  Measured same-box (profiles/r06u_ab_visit_pairs_by_part.log): the level-resident paths
 // at 640 x 480 are one latency chain per iteration, not instruction issue — the packed ICP rows cost 1.5 % (1819 against 1843 frames/s), the
 // packed photometric rows 0.6 %, the packed search nothing either way; the streaming paths (1280 x 960 level 0) gain.  So the resident paths
-// keep one visit per lane (-DEF_RT_PAIRS_ICP / _SEARCH / _RGB switch them on: build.VARIANTS) and the streaming path takes two.
-#if defined(EF_VISIT_PAIRS) && defined(EF_RT_WITH_PAIRS_ICP)
-#define EF_RT_PAIRS_ICP 1
-#endif
-#if defined(EF_VISIT_PAIRS) && defined(EF_RT_WITH_PAIRS_SEARCH)
-#define EF_RT_PAIRS_SEARCH 1
-#endif
-#if defined(EF_VISIT_PAIRS) && defined(EF_RT_WITH_PAIRS_RGB)
-#define EF_RT_PAIRS_RGB 1
-#endif
-#if defined(EF_VISIT_PAIRS) && !defined(EF_RT_NO_PAIRS_STREAM)
+// keep one visit per lane (their two-visit versions: removed, last present in commit 2372c48) and the streaming path takes two.
+#ifdef EF_VISIT_PAIRS
 #define EF_RT_PAIRS_STREAM 1
 #endif
 __device__ __forceinline__ int rt_res_mode(bool has_icp, bool has_rgb, int S, unsigned budget) {
@@ -282,52 +262,6 @@ __device__ __forceinline__ void rt_fill_rgb(const PtLevel& Lv, uint32_t* slots, 
 }
 // one step's rows -> the three outer products of its (up to) four passes, in pass order (phase B)
 __device__ __forceinline__ void rt_rows_to_sums(float (&rows)[8], int s, int K, f32x4 (&c)[3]) { quad_rows_accumulate(rows, s, K, c); }
-#ifdef EF_RT_PAIRS_ICP
-// accum_quads<ICP> on level-resident pixel data, two visits per lane (icp2_*, ef_track_kernels.hip): RT_CH2 steps' gathers in flight together,
-// the current vertex / normal from LDS
-__device__ __forceinline__ void rt_icp_resident(const IcpView& IV, const RgbView& RV, const IcpPose& Pin, const float* slots, int gbase, int N, int K,
-                                                f32x4 (&c)[3]) {
-  (void)RV;
-  constexpr int NP = RT_CH2 / 2;
-  const int S = (K + 3) >> 2, lane = threadIdx.x & 63;
-  const IcpPose P = icp_pose_uniform(Pin);
-  auto load2 = [&](int s) {   // steps s, s + 1
-    IcpLoads2 L;
-    const float* pa = slots + (size_t)(s < S ? s : S - 1) * 6 * 64 + lane;
-    const float* pb = slots + (size_t)(s + 1 < S ? s + 1 : S - 1) * 6 * 64 + lane;
-    L.vcurr = p3{{pa[0], pb[0]}, {pa[64], pb[64]}, {pa[128], pb[128]}};
-    L.ncurr = p3{{pa[192], pb[192]}, {pa[256], pb[256]}, {pa[320], pb[320]}};
-    L.inb[0] = rt_visit_pixel(gbase, s, S, K, N) < N;
-    L.inb[1] = rt_visit_pixel(gbase, s + 1, S, K, N) < N;
-    return L;
-  };
-#pragma unroll 1
-  for (int s0 = 0; s0 < S; s0 += RT_CH2) {
-    // what stays in registers across the round trip: the gathered model vertex / normal and their address (vcurr_g and s_cp are recomputed from
-    // the slot: the same operations on the same values)
-    IcpGathers2 G[NP];
-#pragma unroll
-    for (int u = 0; u < NP; ++u) {
-      const IcpLoads2 L = load2(s0 + 2 * u);
-      p3 vg, scp;
-      icp2_transform(P, L, vg, scp);
-      G[u] = icp2_stage2a(IV, L, scp);
-    }
-#pragma unroll
-    for (int u = 0; u < NP; ++u) {
-      if (s0 + 2 * u < S) {   // uniform
-        const IcpLoads2 L = load2(s0 + 2 * u);
-        p3 vg, scp;
-        icp2_transform(P, L, vg, scp);
-        float ra[8], rb[8];
-        icp2_stage2b(IV, P, L, G[u], vg, scp, ra, rb);
-        rt_rows_to_sums(ra, s0 + 2 * u, K, c);
-        if (s0 + 2 * u + 1 < S) rt_rows_to_sums(rb, s0 + 2 * u + 1, K, c);   // uniform
-      }
-    }
-  }
-}
-#else
 // accum_quads<ICP> on level-resident pixel data: RT_CH steps' gathers in flight together, the current vertex / normal from LDS
 __device__ __forceinline__ void rt_icp_resident(const IcpView& IV, const RgbView& RV, const IcpPose& P, const float* slots, int gbase, int N, int K,
                                                 f32x4 (&c)[3]) {
@@ -371,72 +305,6 @@ __device__ __forceinline__ void rt_icp_resident(const IcpView& IV, const RgbView
     }
   }
 }
-#endif
-#ifdef EF_RT_PAIRS_SEARCH
-// the photometric wavefront's search over ITS OWN visits (k_track_step's body / residualKernel, reduce.cu:631-667, on the level-resident pixel
-// data), two visits per lane: packed correspondence + the model depth it gathered go into the wavefront's slots; returns this lane's
-// {count, sum diff^2}
-__device__ __forceinline__ void rt_rgb_search(const PtLevel& Lv, const m33& Km_in, const f3& kt_in, uint32_t* slots, int K, int& cnt, int& sq) {
-  constexpr int NP = RT_CH2 / 2;
-  const m33 Km = uniform_m33(Km_in);   // (the workgroup's state: the same in every lane; see icp_pose_uniform)
-  const f3 kt = uniform_f3(kt_in);
-  const int S = (K + 3) >> 2, lane = threadIdx.x & 63, cols = Lv.cols, rows = Lv.rows;
-  const bufrsrc rd = buf_of(Lv.lastDepth, (unsigned)(cols * rows) * 4u), ri = buf_of(Lv.lastImage, (unsigned)(cols * rows));
-  cnt = sq = 0;
-#pragma unroll 1
-  for (int s0 = 0; s0 < S; s0 += RT_CH2) {
-    int u0s[NP][2], v0s[NP][2], gi[NP][2], nis[NP][2], lis[NP][2];
-    float td1s[NP][2], d0s[NP][2];
-#pragma unroll
-    for (int u = 0; u < NP; ++u) {
-      const int sa = s0 + 2 * u, sb = sa + 1;
-      const uint32_t* pa = slots + (size_t)(sa < S ? sa : S - 1) * RT_RGB_WORDS * 64 + lane;
-      const uint32_t* pb = slots + (size_t)(sb < S ? sb : S - 1) * RT_RGB_WORDS * 64 + lane;
-      const f32x2 d1{__uint_as_float(pa[0]), __uint_as_float(pb[0])};
-      const uint32_t w[2] = {pa[64], pb[64]};
-      const f32x2 x{(float)(int)(w[0] & 0x7FFu), (float)(int)(w[1] & 0x7FFu)}, y{(float)(int)((w[0] >> 11) & 0x7FFu), (float)(int)((w[1] >> 11) & 0x7FFu)};
-      const bool m[2] = {sa < S && (w[0] & (1u << 30)), sb < S && (w[1] & (1u << 30))};
-      const f32x2 td1 = d1 * (both(Km.r[2].x) * x + both(Km.r[2].y) * y + both(Km.r[2].z)) + both(kt.z);
-      const f32x2 nu = (d1 * (both(Km.r[0].x) * x + both(Km.r[0].y) * y + both(Km.r[0].z)) + both(kt.x)) / td1;
-      const f32x2 nv = (d1 * (both(Km.r[1].x) * x + both(Km.r[1].y) * y + both(Km.r[1].z)) + both(kt.y)) / td1;
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        nis[u][e] = (int)((w[e] >> 22) & 0xFFu);
-        td1s[u][e] = td1[e];
-        u0s[u][e] = f2i_rn(nu[e]);
-        v0s[u][e] = f2i_rn(nv[e]);
-        const bool in = m[e] && u0s[u][e] >= 0 && v0s[u][e] >= 0 && u0s[u][e] < cols && v0s[u][e] < rows;
-        gi[u][e] = in ? v0s[u][e] * cols + u0s[u][e] : -1;
-        const unsigned g = in ? (unsigned)(v0s[u][e] * cols + u0s[u][e]) : 0u;   // (a visit without a correspondence reads texel 0 and is discarded through gi)
-        d0s[u][e] = buf_f32(rd, g * 4u, 0u);
-        lis[u][e] = (int)(uint8_t)__builtin_amdgcn_raw_buffer_load_b8(ri, (int)g, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < NP; ++u) {
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        if (s0 + 2 * u + e < S) {   // uniform
-          uint32_t packed = 0u;
-          float d0 = 0.f;
-          if (gi[u][e] >= 0) {
-            d0 = d0s[u][e];
-            if (d0 > 0 && fabsf(td1s[u][e] - d0) <= 0.07f /* maxDepthDeltaRGB, RGBDOdometry.cpp:41 */ && lis[u][e] != 0) {
-              const int idiff = nis[u][e] - lis[u][e];
-              packed = pack_corres(u0s[u][e], v0s[u][e], idiff);
-              cnt += 1;
-              sq += idiff * idiff;
-            }
-          }
-          uint32_t* p = slots + (size_t)(s0 + 2 * u + e) * RT_RGB_WORDS * 64 + lane;
-          p[192] = packed;
-          p[256] = __float_as_uint(d0);
-        }
-      }
-    }
-  }
-}
-#else
 // the photometric wavefront's search over ITS OWN visits (k_track_step's body / residualKernel, reduce.cu:631-667, on the level-resident pixel
 // data): packed correspondence + the model depth it gathered go into the wavefront's slots; returns this lane's {count, sum diff^2}
 __device__ __forceinline__ void rt_rgb_search(const PtLevel& Lv, const m33& Km, const f3& kt, uint32_t* slots, int K, int& cnt, int& sq) {
@@ -479,30 +347,6 @@ __device__ __forceinline__ void rt_rgb_search(const PtLevel& Lv, const m33& Km, 
     }
   }
 }
-#endif
-#ifdef EF_RT_PAIRS_RGB
-// accum_quads<RGB> on the wavefront's slots, two visits per lane: no memory access at all
-__device__ __forceinline__ void rt_rgb_resident(const IcpView& IV, const RgbView& RV, const IcpPose& P, float sigma, const uint32_t* slots, int K,
-                                                f32x4 (&c)[3]) {
-  (void)IV; (void)P;
-  const int S = (K + 3) >> 2, lane = threadIdx.x & 63;
-#pragma unroll 1
-  for (int s = 0; s < S; s += 2) {
-    const uint32_t* pa = slots + (size_t)s * RT_RGB_WORDS * 64 + lane;
-    const uint32_t* pb = slots + (size_t)(s + 1 < S ? s + 1 : s) * RT_RGB_WORDS * 64 + lane;
-    const uint32_t gxy[2] = {pa[128], pb[128]};
-    const uint32_t corr[2] = {pa[192], pb[192]};
-    const float d0[2] = {__uint_as_float(pa[256]), __uint_as_float(pb[256])};
-    const int gx[2] = {(int)(int16_t)(gxy[0] & 0xFFFFu), (int)(int16_t)(gxy[1] & 0xFFFFu)};
-    const int gy[2] = {(int)(int16_t)(gxy[0] >> 16), (int)(int16_t)(gxy[1] >> 16)};
-    const bool valid[2] = {(corr[0] & 0x80000000u) != 0u, s + 1 < S && (corr[1] & 0x80000000u) != 0u};
-    float ra[8], rb[8];
-    rgb2_rows(RV, sigma, corr, gx, gy, d0, valid, ra, rb);
-    rt_rows_to_sums(ra, s, K, c);
-    if (s + 1 < S) rt_rows_to_sums(rb, s + 1, K, c);   // uniform
-  }
-}
-#else
 // What the photometric rows need that does NOT depend on sigma — the model point behind the correspondence (projectPointsKernel folded in,
 // cudafuncs.cu:670-688) and 1 / z, the one double-precision division of a row (reduce.cu:447) — evaluated by every photometric wavefront for ITS
 // visits right behind its search, i.e. while the column's record of exchange A is under way: off the critical path search -> A -> rows -> B.
@@ -567,7 +411,6 @@ __device__ __forceinline__ void rt_rgb_resident(const IcpView& IV, const RgbView
   }
 }
 #define EF_RT_RGB_PREPARE 1
-#endif
 
 // The trees of one column behind its wavefronts' sums c[] (k_se3_accum's tail): call with the whole workgroup (two __syncthreads inside).
 // Wavefront = (term, virtual warp wl, half): 0-3 the launch's first term, 4-7 the second.  On return the lanes 0..3 (v = 0, j = lane) of
@@ -789,11 +632,7 @@ __global__ void __launch_bounds__(FT_BLOCK) k_track_ref(const FtArgs A, TrackSta
   if (t == 128) {
     unsigned m = 0u;
     for (int spin = 0; spin < FT_SPIN; ++spin) {
-#ifdef EF_FT_MODE_ONE   // (A/B build "modeone": every workgroup polls FtSync::mode, rounds 4-5)
-      const unsigned long long g = ft_get(&Y->mode);
-#else
       const unsigned long long g = ft_get(G2_mine + FT_MODE_WORD);
-#endif
       if ((unsigned)(g >> 32) == A.epoch) { m = (unsigned)g; break; }
       if (spin > 8) __builtin_amdgcn_s_sleep(1);
     }
@@ -1129,14 +968,11 @@ __global__ void __launch_bounds__(FT_BLOCK) k_track_ref(const FtArgs A, TrackSta
           }
         }
         __builtin_amdgcn_s_setprio(0);
-#if defined(EF_RT_RGB_PREPARE) && !defined(EF_RT_PREPARE_LATE)
+#ifdef EF_RT_RGB_PREPARE
         rt_rgb_prepare(RV, slots, K);   // (behind the column's record: what the rows need that does not wait for sigma)
 #endif
         const float sigma = wait_sigma();
         FT_CLK2(25);   // resident: publish A, sweep, sigma
-#if defined(EF_RT_RGB_PREPARE) && defined(EF_RT_PREPARE_LATE)
-        rt_rgb_prepare(RV, slots, K);   // (A/B build "prep_late": the same work where rounds 1-5 had it, behind sigma)
-#endif
         rt_rgb_resident(IV, RV, P, sigma, slots, K, c);
         FT_CLK2(26);   // resident: photometric rows
       }
@@ -1443,9 +1279,6 @@ __global__ void __launch_bounds__(FT_BLOCK) k_track_ref_end(float* partials, Tra
   if (A.has_head) {
     if (t < na) M.sums_s[(A.icp ? 0 : SE3_ACCS) + t] = total;   // (head_sums with ng = 1)
     __syncthreads();
-#ifdef EF_END_ONE_WAVE   // (A/B build "endwave": both tails behind resultRt on the solving wavefront, as in round 5)
-    if (t < 64) solve_step_wave(st, prev, next, true, M.sums_s, A, M.S, PF, true);
-#else
     // the update step's two tails on two wavefronts, as inside the persistent loop; the float pose is all the tail below waits for, so
     // wavefront 0 goes on while wavefront 1 evaluates K R K^-1 / K t (the next barrier is the one in front of the four pieces below)
     if (t < 64) solve_step_wave<true>(st, prev, next, true, M.sums_s, A, M.S, PF, true);
@@ -1454,7 +1287,6 @@ __global__ void __launch_bounds__(FT_BLOCK) k_track_ref_end(float* partials, Tra
       if (wave == 0) { efs::gn_tail_pose(M.S, next, true); efs::wave_sync(); }
       else if (wave == 1) efs::gn_tail_krk(A.knext, M.S, next, true);
     }
-#endif
   } else if (t == 0) {
     for (int i = 0; i < 9; ++i) M.S.Rcurr[i] = prev->Rcurr[i];
     for (int i = 0; i < 3; ++i) M.S.tcurr[i] = prev->tcurr[i];
