@@ -640,22 +640,56 @@ struct FuseArgs {
   KeyedIndex key;               // k_associate<true>: the z-buffer it taps in place of im's images
   unsigned long long* zclear;   // ... and cols x rows keys of another one it returns to ZBUF_EMPTY (or null)
 };
-// data.vert:76-193.  One thread per fused pixel (W/2 x H/2, parity-selected: quirk Q12), threads walk rows
+// data.vert:76-193.  ASSOC_LANES consecutive lanes per fused pixel (W/2 x H/2, parity-selected: quirk Q12), pixels walk a column or a row
 // (coalesced taps); the candidate lands in slot r = column-major rank == the reference's draw order.
 // KEYED (round 9): the frame's first predictIndices is not resolved into images — a texel is the 8-byte key the splat left (FuseArgs::key).  The
 // key gives the winner's id and vc.z, which is all the first two tests of a tap look at; only the texels behind them ask for the winner's
 // position and normal rows, and vc / nr are what the resolve would have stored (index_texel_*).  An empty texel and one won by surfel 0 fail
 // `current > 0U` as they do on the images.  The launch also clears FuseArgs::zclear (the z-buffer of the PREVIOUS frame's second
 // predictIndices, whose readers are long done and whose next splat comes behind this launch).
+// Round 10: the 16 taps {-1, 0, 0, +1}^2 (N4) touch 9 distinct texels, rank a3 * 3 + b3 in order of first appearance.  Each texel is EVALUATED
+// once ({qualifies, dist, id}: the tap body's expressions on the same values) and the reference's selection — strict `dist < bestDist` from 1000,
+// so the earliest minimum wins and a repeated tap never changes it — runs over the 9 ranks.  The ranks are dealt to the ASSOC_LANES lanes of the
+// pixel in contiguous segments (4 lanes: 3 + 2 + 2 + 2); a lane loads and evaluates its own texels only, selects over its segment, and the
+// segments' results are combined in rank order with the same strict `<` (DPP, no LDS): the earliest global minimum below 1000, which is what the
+// sequential scan returns.  Lane 0 of the group alone computes and stores the candidate.
+// ASSOC_LANES: 1, 2, 4 and 8 all build and are bit-identical by construction; by static counts (profiles/r10a_associate_instr_counts.txt) 1 / 2 / 4 / 8
+// lanes give 2189 / 1566 / 1216 / 1033 VALU instructions per wavefront at 112 / 70 / 56 / 48 VGPRs and 1.2 / 2.3 / 4.7 / 9.4 workgroups per CU at
+// 640 x 480; 4 is the first that fills every SIMD with several wavefronts (8: twice the wavefronts for 15 % fewer instructions each).  None of
+// them has been timed on the GPU yet.
+constexpr int ASSOC_LANES = 4;
+constexpr int ASSOC_SLOTS = (9 + ASSOC_LANES - 1) / ASSOC_LANES;   // texels of the longest segment
+static_assert(ASSOC_LANES == 1 || ASSOC_LANES == 2 || ASSOC_LANES == 4 || ASSOC_LANES == 8, "a wavefront holds whole pixels; the combine knows offsets 1, 2, 4");
+// the value lane + OFF of the same row of 16 holds (OFF 1, 2: inside the quad)
+template <int OFF>
+__device__ __forceinline__ uint32_t assoc_lane_down(uint32_t v) {
+  static_assert(OFF == 1 || OFF == 2 || OFF == 4, "");
+  constexpr int ctrl = OFF == 1 ? 0xF5 /* quad_perm:[1,1,3,3] */ : OFF == 2 ? 0xEE /* quad_perm:[2,3,2,3] */ : 0x104 /* row_shl:4 */;
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, 0xF, 0xF, true);
+}
+// the selection's step between a segment (this lane's: the earlier ranks) and the one OFF lanes on: replaced only by a strictly smaller dist
+template <int OFF>
+__device__ __forceinline__ void assoc_combine(float& bestDist, uint32_t& best) {
+  const float d = __uint_as_float(assoc_lane_down<OFF>(__float_as_uint(bestDist)));
+  const uint32_t id = assoc_lane_down<OFF>(best);
+  if (d < bestDist) {
+    bestDist = d;
+    best = id;
+  }
+}
 template <bool KEYED>
 __global__ void __launch_bounds__(BLK) k_associate(const FuseArgs A, Candidates cand, uint32_t* winner, int colwalk) {
   const Cam cam = A.cam;
   const int qc = cam.cols / 2, qr = cam.rows / 2;
-  const int q = (int)(xcd_block() * blockDim.x + threadIdx.x);
+  const int t = (int)(xcd_block() * blockDim.x + threadIdx.x);
   if (KEYED && A.zclear)
-    for (int i = q, P = cam.cols * cam.rows, step = (int)(gridDim.x * blockDim.x); i < P; i += step) A.zclear[i] = ZBUF_EMPTY;
+    for (int i = t, P = cam.cols * cam.rows, step = (int)(gridDim.x * blockDim.x); i < P; i += step) A.zclear[i] = ZBUF_EMPTY;
+  const int q = t / ASSOC_LANES, sub = t % ASSOC_LANES;   // fused pixel, lane of its group (the whole group takes every branch on q below together)
   if (q >= qc * qr) return;
-  // colwalk: consecutive lanes go down a column (the order of the candidate slots and of a column-major index map);
+  // this lane's segment of the 9 ranks: 9 / ASSOC_LANES of them, the first 9 % ASSOC_LANES lanes one more
+  const int seg_len = 9 / ASSOC_LANES + (sub < 9 % ASSOC_LANES ? 1 : 0);
+  const int seg_first = sub * (9 / ASSOC_LANES) + (sub < 9 % ASSOC_LANES ? sub : 9 % ASSOC_LANES);
+  // colwalk: consecutive pixels go down a column (the order of the candidate slots and of a column-major index map);
   // otherwise along a row (the order of the depth and colour images)
   const int qy = colwalk ? q % qr : q / qc, qx = colwalk ? q / qr : q - (q / qc) * qc;
   const int par = A.time % 2;
@@ -671,45 +705,41 @@ __global__ void __launch_bounds__(BLK) k_associate(const FuseArgs A, Candidates 
     const f3 vPosLocal = getVertexF(DR, i, j, x, y, cx, cy, inv_fx, inv_fy);
     const bool sel = ((int)x % 2 == (int)ftime % 2 && (int)y % 2 == (int)ftime % 2);
     const bool nb = !(DR.at(i - 1, j) == 0 || DR.at(i, j - 1) == 0 || DR.at(i + 1, j) == 0 || DR.at(i, j + 1) == 0);
-    // Round 6: everything the pixel reads — the filtered depth's cross, its colour, the 27 words of its 9 index-map texels — has an address that
+    // Round 6: everything the pixel reads — the filtered depth's cross, its colour, the words of its index-map texels — has an address that
     // depends on (i, j) only, so it is asked for HERE, beside the raw depth, not behind the test on the raw depth (a second dependent round
     // trip for every pixel that passes; clamped addresses: a pixel that fails the test reads valid memory it does not use)
     const float zf_c = DF.at(i, j), zf_xf = DF.at(i + 1, j), zf_xb = DF.at(i - 1, j), zf_yf = DF.at(i, j + 1), zf_yb = DF.at(i, j - 1);
     const uint8_t* c = A.rgb3 + (size_t)(j * cam.cols + i) * 3;
     const uint8_t c0 = c[0], c1 = c[1], c2 = c[2];
     const float weighting = *A.weighting;
-    uint32_t idx9[3][3];
-    float4 vc9[3][3], nr9[3][3];   // KEYED: the winners' position + confidence and normal + radius ROWS until the taps turn them into texels
-    uint2 key9[3][3];   // {id, depth_key}: the two halves of a 64-bit key
+    // slot m of this lane: rank seg_first + m while m < seg_len; a slot past the segment reads rank 8's texel and is marked 0 like a failing one
+    uint32_t idxs[ASSOC_SLOTS];
+    float4 vcs[ASSOC_SLOTS], nrs[ASSOC_SLOTS];   // KEYED: the winners' position + confidence and normal + radius ROWS until the evaluation turns them into texels
+    uint2 keys[ASSOC_SLOTS];   // {id, depth_key}: the two halves of a 64-bit key
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const int tx = clampi(i + a - 1, 0, cam.cols - 1);
-#pragma unroll
-      for (int b = 0; b < 3; ++b) {
-        const int ty = clampi(j + b - 1, 0, cam.rows - 1);
-        const int ti = im_texel(A.im, cam, tx, ty);
-        if (KEYED) {
-          key9[a][b] = reinterpret_cast<const uint2*>(A.key.keys)[ti];
-        } else {
-          idx9[a][b] = A.im.index[ti];
-          vc9[a][b] = A.im.vert_conf[ti];
-          nr9[a][b] = A.im.norm_rad[ti];
-        }
+    for (int m = 0; m < ASSOC_SLOTS; ++m) {
+      const int k = m < seg_len ? seg_first + m : 8;
+      const int a3 = (k >= 3) + (k >= 6), b3 = k - 3 * a3;
+      const int tx = clampi(i + a3 - 1, 0, cam.cols - 1), ty = clampi(j + b3 - 1, 0, cam.rows - 1);
+      const int ti = im_texel(A.im, cam, tx, ty);
+      if (KEYED) {
+        keys[m] = reinterpret_cast<const uint2*>(A.key.keys)[ti];
+      } else {
+        const uint32_t id = A.im.index[ti];
+        idxs[m] = m < seg_len ? id : 0U;
+        vcs[m] = A.im.vert_conf[ti];
+        nrs[m] = A.im.norm_rad[ti];
       }
     }
     const rt34 pose = rt34_load16(A.pose16);
     if (sel && nb && vPosLocal.z > 0 && vPosLocal.z <= A.maxDepth) {
-      const f3 vPos = xform(pose, vPosLocal);
       // getVertexF / getNormalF (geometry.glsl:21-40) on the values loaded above: the same expressions
       auto vtx = [&](float z, float xx, float yy) { return f3{(xx - cx) * z * inv_fx, (yy - cy) * z * inv_fy, z}; };
       const f3 vPosition_f = vtx(zf_c, x, y);
-      const f3 col{(float)c0 / 255.0f, (float)c1 / 255.0f, (float)c2 / 255.0f};
       const f3 xf = vtx(zf_xf, x + 1, y), xb = vtx(zf_xb, x - 1, y), yf = vtx(zf_yf, x, y + 1), yb = vtx(zf_yb, x, y - 1);
       const f3 del_x = half_sum(xb, vPosition_f) - half_sum(xf, vPosition_f);
       const f3 del_y = half_sum(yb, vPosition_f) - half_sum(yf, vPosition_f);
       const f3 vNormLocal = normalized(cross(del_x, del_y));
-      const f3 nW = mul(pose.R, vNormLocal);
-      int counter = 0;
       uint32_t best = 0;
       float bestDist = 1000;
       const float xl = (x - cx) * inv_fx, yl = (y - cy) * inv_fy;
@@ -717,67 +747,68 @@ __global__ void __launch_bounds__(BLK) k_associate(const FuseArgs A, Candidates 
       const f3 ray{xl, yl, 1};
       const float lenRay = sqrtf(dot(ray, ray));
       const float lenN = sqrtf(dot(vNormLocal, vNormLocal));
-      // N4: the 16 taps {-1, 0, 0, +1}^2 touch 9 distinct texels.  Round 5: all 27 loads (index, vertex + confidence, normal + radius of the 9
-      // texels) are issued up front, unconditionally — inside the conditionals of the tap loop they formed chains of up to 48 DEPENDENT
-      // round trips (index -> vertex -> normal, tap after tap: the compiler cannot speculate a load across a branch); the 16 taps are then
-      // evaluated on registers in the reference's order (a duplicate tap never changes `best`: dist < bestDist is strict)
+      // Round 5: the loads of the texels (index, vertex + confidence, normal + radius) are issued up front, unconditionally — inside the
+      // conditionals of the evaluation they formed chains of DEPENDENT round trips (index -> vertex -> normal, texel after texel: the compiler
+      // cannot speculate a load across a branch); the texels are then evaluated on registers
       // KEYED: the second round of loads, again all of them before the first use and none behind a branch — a texel that fails the first two
       // tests of its taps (empty, won by surfel 0, or too far from the pixel in depth: decided on the key) asks for row 0 and is marked 0,
       // which is what `current > 0U` sends away
       const rt34 Tcw = rt34_load16(KEYED ? A.key.T_cw16_dev : A.pose16);   // (not KEYED: unused)
       if (KEYED) {
 #pragma unroll
-        for (int a = 0; a < 3; ++a)
+        for (int m = 0; m < ASSOC_SLOTS; ++m) {
+          const uint32_t id = keys[m].x;
+          float vcz = depth_of_key(keys[m].y);
+          asm volatile("" : "+v"(vcz));   // (opaque: with the decode visible to this comparison, hipcc 7.2's instruction selection crashes on the kernel)
+          const bool tap = m < seg_len && (id & keys[m].y) != 0xFFFFFFFFu /* ZBUF_EMPTY */ && id > 0U && fabsf((vcz * lambda) - (vPosLocal.z * lambda)) < 0.05f;
+          idxs[m] = tap ? id : 0U;
+        }
 #pragma unroll
-          for (int b = 0; b < 3; ++b) {
-            const uint32_t id = key9[a][b].x;
-            float vcz = depth_of_key(key9[a][b].y);
-            asm volatile("" : "+v"(vcz));   // (opaque: with the decode visible to this comparison, hipcc 7.2's instruction selection crashes on the kernel)
-            const bool tap = (id & key9[a][b].y) != 0xFFFFFFFFu /* ZBUF_EMPTY */ && id > 0U && fabsf((vcz * lambda) - (vPosLocal.z * lambda)) < 0.05f;
-            idx9[a][b] = tap ? id : 0U;
-          }
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-          for (int b = 0; b < 3; ++b) {
-            vc9[a][b] = A.key.map.pos_conf[idx9[a][b]];
-            nr9[a][b] = A.key.map.nrm_rad[idx9[a][b]];
-          }
+        for (int m = 0; m < ASSOC_SLOTS; ++m) {
+          vcs[m] = A.key.map.pos_conf[idxs[m]];
+          nrs[m] = A.key.map.nrm_rad[idxs[m]];
+        }
       }
+      // the selection over this lane's segment, in rank order
 #pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        const int a3 = a == 0 ? 0 : (a == 3 ? 2 : 1);
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-          const int b3 = b == 0 ? 0 : (b == 3 ? 2 : 1);
-          const uint32_t current = idx9[a3][b3];
-          if (current > 0U) {
-            const float4 vc = KEYED ? index_texel_vert_conf(Tcw, vc9[a3][b3]) : vc9[a3][b3];
-            if (fabsf((vc.z * lambda) - (vPosLocal.z * lambda)) < 0.05f) {
-              const f3 cr = cross(ray, f3{vc.x, vc.y, vc.z});
-              const float dist = sqrtf(dot(cr, cr)) / lenRay;
-              const float4 nr = KEYED ? index_texel_norm_rad(Tcw, nr9[a3][b3]) : nr9[a3][b3];
-              const f3 nn{nr.x, nr.y, nr.z};
-              const float cang = dot(nn, vNormLocal) / (sqrtf(dot(nn, nn)) * lenN);
-              const bool angOk = (cang > 0.87758255f && cang <= 1.0f);  // abs(acos(c)) < 0.5, NaN-false
-              if (dist < bestDist && (fabsf(nr.z) < 0.75f || angOk)) {
-                counter++;
-                bestDist = dist;
-                best = current;
-              }
+      for (int m = 0; m < ASSOC_SLOTS; ++m) {
+        const uint32_t current = idxs[m];
+        if (current > 0U) {
+          const float4 vc = KEYED ? index_texel_vert_conf(Tcw, vcs[m]) : vcs[m];
+          if (fabsf((vc.z * lambda) - (vPosLocal.z * lambda)) < 0.05f) {
+            const f3 cr = cross(ray, f3{vc.x, vc.y, vc.z});
+            const float dist = sqrtf(dot(cr, cr)) / lenRay;
+            const float4 nr = KEYED ? index_texel_norm_rad(Tcw, nrs[m]) : nrs[m];
+            const f3 nn{nr.x, nr.y, nr.z};
+            const float cang = dot(nn, vNormLocal) / (sqrtf(dot(nn, nn)) * lenN);
+            const bool angOk = (cang > 0.87758255f && cang <= 1.0f);  // abs(acos(c)) < 0.5, NaN-false
+            if (dist < bestDist && (fabsf(nr.z) < 0.75f || angOk)) {
+              bestDist = dist;
+              best = current;
             }
           }
         }
       }
-      const float tag = counter > 0 ? -1.0f : -2.0f;
-      cand.pos_conf[r] = make_float4(vPos.x, vPos.y, vPos.z, confidence(x, y, cx, cy, weighting));
-      cand.nrm_rad[r] = make_float4(nW.x, nW.y, nW.z, getRadius(vPosition_f.z, vNormLocal.z, inv_fx, inv_fy));
-      c_col = make_float4(encodeColor(col), 0.f, ftime, tag);
-      cand.best[r] = best;
-      if (counter > 0) atomicMin(&winner[best], (uint32_t)r);  // N5: first pixel in draw order owns the update texel
+      // ... and over the group's segments: lane s takes in lane s + 1's, then s + 2's, then s + 4's (every lane of the group is here: the
+      // conditions above depend on the pixel only)
+      if (ASSOC_LANES > 1) assoc_combine<1>(bestDist, best);
+      if (ASSOC_LANES > 2) assoc_combine<2>(bestDist, best);
+      if (ASSOC_LANES > 4) assoc_combine<4>(bestDist, best);
+      if (sub == 0) {
+        const bool found = bestDist < 1000;   // something replaced the initial 1000 (the reference's counter > 0)
+        const f3 vPos = xform(pose, vPosLocal);
+        const f3 nW = mul(pose.R, vNormLocal);
+        const f3 col{(float)c0 / 255.0f, (float)c1 / 255.0f, (float)c2 / 255.0f};
+        const float tag = found ? -1.0f : -2.0f;
+        cand.pos_conf[r] = make_float4(vPos.x, vPos.y, vPos.z, confidence(x, y, cx, cy, weighting));
+        cand.nrm_rad[r] = make_float4(nW.x, nW.y, nW.z, getRadius(vPosition_f.z, vNormLocal.z, inv_fx, inv_fy));
+        c_col = make_float4(encodeColor(col), 0.f, ftime, tag);
+        cand.best[r] = best;
+        if (found) atomicMin(&winner[best], (uint32_t)r);  // N5: first pixel in draw order owns the update texel
+      }
     }
   }
-  cand.col_time[r] = c_col;
+  if (sub == 0) cand.col_time[r] = c_col;
 }
 // update.vert:37-92, in place, only for the surfels that won an association
 // update.vert:37-92 for ONE surfel: candidate r (which won the association) merged into surfel id, in place; s / sc: the surfel's position +
@@ -1390,10 +1421,13 @@ void fuse(const Cam& cam, const float* pose_f16_dev, int time, const uint8_t* rg
   (void)count_dev;
   FuseArgs A{cam, pose_f16_dev, time, rgb3, dm, dmf, im, maxDepth, weighting_dev, keyed ? *keyed : KeyedIndex{}, zclear};
   // column-major index maps: walking columns measured 24.7 us vs 34.8 us for walking rows (profiles/, round 1)
+  // the launch is sized from the work, ASSOC_LANES lanes per fused pixel: 640 x 480 = 76 800 pixels x 4 lanes = 1 200 workgroups, 4.7 per CU on
+  // 256 CUs (one lane per pixel: 300 workgroups, 1.17 per CU — 44 CUs with two, every SIMD of the others with a single wavefront)
+  const int groups = ceil_div(cand.n * ASSOC_LANES, BLK);
   if (keyed)
-    hipLaunchKernelGGL(k_associate<true>, dim3(ceil_div(cand.n, BLK)), dim3(BLK), 0, s, A, cand, winner, im.colmajor ? 1 : 0);
+    hipLaunchKernelGGL(k_associate<true>, dim3(groups), dim3(BLK), 0, s, A, cand, winner, im.colmajor ? 1 : 0);
   else
-    hipLaunchKernelGGL(k_associate<false>, dim3(ceil_div(cand.n, BLK)), dim3(BLK), 0, s, A, cand, winner, im.colmajor ? 1 : 0);
+    hipLaunchKernelGGL(k_associate<false>, dim3(groups), dim3(BLK), 0, s, A, cand, winner, im.colmajor ? 1 : 0);
   // (defer_merge: the caller's next launch is predict_indices(..., &cand, winner), whose splat merges every surfel before it projects it)
   if (!defer_merge) hipLaunchKernelGGL(k_merge, dim3(ceil_div(cand.n, BLK)), dim3(BLK), 0, s, cand, (const uint32_t*)winner, map, time);
 }
