@@ -66,6 +66,15 @@ class ef_register_result(C.Structure):
                 ("A", C.c_double * 36)]
 
 
+class ef_map_selection(C.Structure):
+    _fields_ = [("tests", c_u32), ("T_bw", C.c_double * 16), ("box_min", c_f * 3), ("box_max", c_f * 3), ("conf_min", c_f), ("conf_max", c_f),
+                ("init_time_min", c_i), ("init_time_max", c_i), ("last_time_min", c_i), ("last_time_max", c_i), ("radius_min", c_f),
+                ("radius_max", c_f), ("id_min", c_u32), ("id_max", c_u32), ("label_class", c_i), ("label_min_prob", c_f)]
+
+
+# EF_SEL_* of include/ef_hip.h
+SEL_BOX, SEL_CONF, SEL_INIT_TIME, SEL_LAST_TIME, SEL_RADIUS, SEL_ID, SEL_LABEL, SEL_INVERT = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x100
+
 REG_CONVERGED, REG_MAX_ITERATIONS, REG_TOO_FEW_PAIRS, REG_DEGENERATE = 0, 1, 2, 3   # EF_REG_* of include/ef_hip.h
 REG_STATUS = {REG_CONVERGED: "CONVERGED", REG_MAX_ITERATIONS: "MAX_ITERATIONS", REG_TOO_FEW_PAIRS: "TOO_FEW_PAIRS", REG_DEGENERATE: "DEGENERATE"}
 
@@ -1032,6 +1041,87 @@ class ElasticFusion:
         _chk(lib().ef_register_cloud_dev(self.h, args[0], args[1], c_u32(n), C.byref(params), pT, _ptr(T), C.byref(res), args[2], args[3]),
              self.h)
         return T.reshape(4, 4), self._registerResult(res)
+
+    # --- select, extract and erase surfels (ef_map_select / ef_map_gather / ef_map_erase) ---
+    @staticmethod
+    def mapSelection(**kw) -> ef_map_selection:
+        """ef_default_map_selection (tests 0 = every row) with fields replaced by keyword: tests (OR of api.SEL_*), T_bw (4 x 4, box <- world),
+        box_min / box_max (3 each), conf_min / conf_max, init_time_min / _max, last_time_min / _max, radius_min / _max, id_min / id_max,
+        label_class, label_min_prob"""
+        s = ef_map_selection()
+        lib().ef_default_map_selection(C.byref(s))
+        for k, v in kw.items():
+            if not hasattr(s, k):
+                raise TypeError(f"unknown selection field {k}")
+            if k == "T_bw":
+                s.T_bw[:] = [float(x) for x in np.asarray(v, np.float64).reshape(16)]
+            elif k in ("box_min", "box_max"):
+                getattr(s, k)[:] = [float(x) for x in np.asarray(v, np.float32).reshape(3)]
+            else:
+                setattr(s, k, v)
+        return s
+
+    def _selection(self, sel, kw) -> ef_map_selection:
+        if sel is None:
+            return self.mapSelection(**kw)
+        assert not kw, "give a selection or keywords, not both"
+        return sel
+
+    def selectSurfels(self, sel: ef_map_selection | None = None, max_rows: int | None = None, count: bool = False, **kw):
+        """the selected rows of downloadMap() in ascending order (uint32), at most max_rows of them (None: all); count=True: (rows, total)"""
+        sel = self._selection(sel, kw)
+        cap = self.lastCount() if max_rows is None else int(max_rows)
+        rows = np.zeros(max(cap, 1), np.uint32)
+        total = c_u32(0)
+        _chk(lib().ef_map_select(self.h, C.byref(sel), _ptr(rows) if cap else None, c_u32(cap), C.byref(total)), self.h)
+        out = rows[:min(cap, total.value)].copy()
+        return (out, total.value) if count else out
+
+    def countSurfels(self, sel: ef_map_selection | None = None, **kw) -> int:
+        """the number of selected rows (ef_map_select without a list)"""
+        sel = self._selection(sel, kw)
+        total = c_u32(0)
+        _chk(lib().ef_map_select(self.h, C.byref(sel), None, c_u32(0), C.byref(total)), self.h)
+        return total.value
+
+    def selectSurfelsDevice(self, sel: ef_map_selection, rows_dev, max_rows: int, count_dev):
+        """ef_map_select_dev: raw device pointers (int, c_void_p or None for rows with max_rows 0), enqueued on the context's stream"""
+        args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (rows_dev, count_dev)]
+        _chk(lib().ef_map_select_dev(self.h, C.byref(sel), args[0], c_u32(int(max_rows)), args[1]), self.h)
+
+    def gatherSurfels(self, rows) -> np.ndarray:
+        """downloadMap()[rows] without the download: n x 12 float32 in the order of rows (duplicates allowed; a row past the map gives zeros)"""
+        rows = np.ascontiguousarray(rows, np.uint32).reshape(-1)
+        n = len(rows)
+        out = np.zeros((max(n, 1), 12), np.float32)
+        _chk(lib().ef_map_gather(self.h, _ptr(rows) if n else None, c_u32(n), _ptr(out)), self.h)
+        return out[:n].copy()
+
+    def gatherSurfelsDevice(self, rows_dev, n: int, surfels_dev):
+        """ef_map_gather_dev: raw device pointers (int or c_void_p), enqueued on the context's stream"""
+        args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (rows_dev, surfels_dev)]
+        _chk(lib().ef_map_gather_dev(self.h, args[0], c_u32(int(n)), args[1]), self.h)
+
+    def eraseSurfels(self, sel: ef_map_selection | None = None, **kw) -> int:
+        """removes the selected surfels from the map (stable; the prediction is renewed once frames have run); returns how many went"""
+        sel = self._selection(sel, kw)
+        removed = c_u32(0)
+        _chk(lib().ef_map_erase(self.h, C.byref(sel), C.byref(removed)), self.h)
+        return removed.value
+
+    def eraseRows(self, rows) -> int:
+        """removes the named rows of downloadMap() (any order; duplicates and rows past the map are ignored); returns how many went"""
+        rows = np.ascontiguousarray(rows, np.uint32).reshape(-1)
+        removed = c_u32(0)
+        _chk(lib().ef_map_erase_rows(self.h, _ptr(rows) if len(rows) else None, c_u32(len(rows)), C.byref(removed)), self.h)
+        return removed.value
+
+    def eraseRowsDevice(self, rows_dev, n: int) -> int:
+        """ef_map_erase_rows_dev: a raw device pointer (int or c_void_p) to n uint32 rows; synchronises like every erase"""
+        removed = c_u32(0)
+        p = None if rows_dev is None else P(int(rows_dev.value if isinstance(rows_dev, P) else rows_dev))
+        _chk(lib().ef_map_erase_rows_dev(self.h, p, c_u32(int(n)), C.byref(removed)), self.h)
+        return removed.value
 
     def setReferenceDownload(self, on=True):
         """downloadMap / savePly read what GlobalModel::downloadMap reads (the pre-clean buffer, quirk Q14) instead of model()"""

@@ -273,4 +273,39 @@ struct RegisterArgs {
 unsigned register_blocks(unsigned n);   // workgroups (= slabs) of a step over n points: a function of n alone
 void register_step(const RegisterArgs& a, hipStream_t s);
 
+// ---- select, extract and erase surfels (ef_select.inc; ef_map_select / ef_map_gather / ef_map_erase of include/ef_hip.h) ----
+constexpr unsigned SEL_BOX = 0x01u, SEL_CONF = 0x02u, SEL_INIT_TIME = 0x04u, SEL_LAST_TIME = 0x08u, SEL_RADIUS = 0x10u, SEL_ID = 0x20u,
+                   SEL_LABEL = 0x40u;   // EF_SEL_* without EF_SEL_INVERT (SelectArgs::invert)
+struct SelectArgs {
+  SurfelSoA map;
+  unsigned n;               // rows of the map (the host knows the count: it sizes the grid)
+  unsigned tests;           // OR of SEL_*
+  unsigned invert;
+  float R[9], t[3];         // T_bw rounded to f32 once (row-major rotation block, translation)
+  float box_min[3], box_max[3];
+  float conf_min, conf_max;
+  float init_min, init_max, last_min, last_max;   // the int bounds converted to float once
+  float radius_min, radius_max;
+  unsigned id_min, id_max;
+  const float* tab;         // the aligned label table [rows][C] (SEL_LABEL only)
+  int C, label_class;
+  float label_min_prob;
+};
+struct SelectScratch {
+  uint8_t* flags;           // one byte per row
+  uint32_t* chunk_count;    // per chunk of 256 rows
+  uint32_t* chunk_offset;   // their exclusive scan
+};
+unsigned select_chunks(unsigned n);
+// flags of the selected rows, their per-chunk counts and offsets; *total = the number selected
+void select_flags(const SelectArgs& a, const SelectScratch& sc, uint32_t* total, hipStream_t s);
+// flags = 1 for the named rows (< n; duplicates harmless); counts, offsets and *total of the rows whose flag differs from `flip`
+void select_mark_rows(const uint32_t* rows, unsigned n_rows, unsigned n, unsigned flip, const SelectScratch& sc, uint32_t* total, hipStream_t s);
+// the flagged rows in ascending order, the first max_rows of them
+void select_rows(const SelectScratch& sc, unsigned n, uint32_t* rows, unsigned max_rows, hipStream_t s);
+// dst = the rows of src whose flag differs from `flip`, in their old order (all three streams as data)
+void select_compact(const SelectScratch& sc, unsigned n, unsigned flip, SurfelSoA src, SurfelSoA dst, hipStream_t s);
+// out: n_rows x 12 floats in the download's layout, in the order of rows[]; a row >= n gives twelve zero words
+void map_gather(SurfelSoA map, unsigned n, const uint32_t* rows, unsigned n_rows, float* out, hipStream_t s);
+
 }  // namespace efm

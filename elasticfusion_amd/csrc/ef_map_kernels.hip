@@ -1490,5 +1490,6 @@ void sample_graph(SurfelSoA map, const unsigned* count_dev, int stride, int max_
 #include "ef_labels.inc"
 #include "ef_query.inc"
 #include "ef_register.inc"
+#include "ef_select.inc"
 
 }  // namespace efm

@@ -587,6 +587,96 @@ int ef_register_cloud_dev(ef_ctx* ctx, const float* points3_dev, const float* no
                           const ef_register_params* params, const double* T_init16_or_null, double* T_out16, ef_register_result* result,
                           uint32_t* row_dev_or_null, float* plane_dev_or_null);
 
+/* ---- Select, extract and erase surfels: act on a subset of the map without moving it through the host.  Off until first used: no select /
+ * gather / erase call, nothing allocated, nothing run, and no frame kernel knows of it.
+ *
+ * "Row" is the map row at the time of the call: the row space of ef_map_download (reference download off), ef_get_surfel_ids, the index image
+ * of ef_render_model and the queries.  A surfel (row of 12 floats as ef_map_download returns it) has the position (x, y, z) = floats 0 .. 2,
+ * the confidence = float 3, the ID bits = float 5, the creation time = float 6, the time last seen = float 7, the radius = float 11.
+ *
+ * THE SELECTION.  All per-row arithmetic is f32, one rounding per operation, no contraction, in the written order.  Comparisons with NaN are
+ * false.  `tests` says which of the tests below are ENABLED; the fields of a test that is not enabled are neither read nor checked.
+ *   EF_SEL_BOX        Rf, tf are T_bw's rotation block and translation rounded to f32 once (T_bw maps world coordinates into the box's
+ *                     frame; row-major 4 x 4 double like every other pose here):
+ *                       bx = ((Rf00*x + Rf01*y) + Rf02*z) + tfx,  by = ((Rf10*x + Rf11*y) + Rf12*z) + tfy,  bz = ((Rf20*x + Rf21*y) + Rf22*z) + tfz
+ *                     (the expression ef_register_step documents).  Passes iff box_min[a] <= b[a] && b[a] <= box_max[a] for a = 0, 1, 2.
+ *                     Infinite bounds are allowed (a half-space, a slab).
+ *   EF_SEL_CONF       conf_min <= c && c <= conf_max on the stored confidence.
+ *   EF_SEL_RADIUS     radius_min <= r && r <= radius_max on the stored radius.
+ *   EF_SEL_INIT_TIME  (float)init_time_min <= t && t <= (float)init_time_max on the stored creation time (a float that holds a tick).
+ *   EF_SEL_LAST_TIME  (float)last_time_min <= t && t <= (float)last_time_max on the stored time last seen.
+ *   EF_SEL_ID         id_min <= id && id <= id_max on the ID lane's uint32 bits.  Needs ef_set_surfel_ids on; rows created since the last
+ *                     ID-consuming call are numbered first, as in every other ID-consuming call.
+ *   EF_SEL_LABEL      needs ef_enable_labels on; the table is aligned to the current rows first, as in every label call.  With p the row's C
+ *                     floats: best = 0, m = p[0]; for c = 1 .. C-1 in ascending order: if p[c] > m then best = c, m = p[c] (the argmax of
+ *                     ef_render_labels: ties to the lowest class).  Passes iff best == label_class && m >= label_min_prob.
+ * A row is SELECTED iff (every enabled test passes) XOR (EF_SEL_INVERT is set).  tests = 0 selects every row, tests = EF_SEL_INVERT none.
+ * Under EF_SEL_INVERT a row that fails a test only because a comparison met a NaN IS selected: a surfel with a NaN position fails EF_SEL_BOX
+ * and is therefore selected by EF_SEL_BOX | EF_SEL_INVERT.
+ *
+ * ef_map_select writes the first min(max_rows, total) selected rows in ASCENDING order and *count = total, the number of ALL selected rows, which
+ * may exceed max_rows; rows may be NULL with max_rows 0 (a count only).  Entries of rows[] past min(max_rows, total) are left as they were.
+ *
+ * ef_map_gather writes n x 12 floats in ef_map_download's layout in the order of rows[]; duplicates are allowed, a row >= the map count yields
+ * twelve zero words.  While IDs are on, float 5 carries the ID bits (rows created since the last ID-consuming call are numbered first).  surfels12_dev
+ * is written in 16-byte words: it must be 16-byte aligned, as every ef_dev_alloc pointer is.
+ *
+ * ef_map_erase removes the selected rows; ef_map_erase_rows[_dev] removes the named rows: any order, duplicates and rows >= the map count are
+ * ignored.  *removed (may be NULL) = the number of distinct rows actually removed.  What an erase leaves behind:
+ *   the map       the kept rows in their old order (the compaction is stable), every word of them bit for bit, ID lane included;
+ *   the context   the state that ef_map_upload(the kept rows) followed by ef_restore_state(tick, ef_get_pose_qt, the last processed frame) would
+ *                 leave: tick, pose, trajectory, last frame and tracking statistics are unchanged, and if ef_process_frame* or ef_restore_state
+ *                 has run on the context the model prediction (what the next frame is tracked against) is renewed from the edited map at the
+ *                 current pose.  On a context whose map was only uploaded, only the map changes;
+ *   the index     of the queries and the registration is stale and rebuilt by their next call;
+ *   IDs           are never reused: the counter stays above the largest ID ever handed out, not above the largest survivor (with IDs on, an
+ *                 erase numbers the new rows first like every ID-consuming call);
+ *   labels        the next label call re-aligns by ID as it does after a frame's clean: kept rows keep their C floats bit for bit;
+ *   the shadow buffer of ef_set_reference_download is left as it is: until the next frame a reference download still shows the unedited rows.
+ * Erasing nothing (an empty selection, n = 0) is valid and still leaves the state described.  All three erase calls synchronise before and after.
+ *
+ * Host variants stage their arrays and synchronise.  The _dev variants of select and gather take DEVICE pointers and only enqueue on the context's
+ * stream, except for what ID numbering or label alignment need and except that the first call after a call that can change the map
+ * (ef_process_frame*, ef_map_upload, ef_restore_state, an erase) waits for the device once: the map count sizes the launches, as for the queries.
+ *
+ * EF_EINVAL, before any GPU work (the selection is checked before the context, so with a NULL context ef_last_error(NULL) names what is wrong
+ * with the arguments): a NULL context, selection, count (select) or surfels12 (gather, n > 0); n > 0 or max_rows > 0 with a NULL array; unknown
+ * bits in tests; with EF_SEL_BOX a non-finite entry of T_bw or a NaN bound; NaN in the range of an enabled float test; with EF_SEL_LABEL a
+ * label_class outside 0 .. C-1 or a NaN label_min_prob.
+ * EF_ESTATE: the context's stream is being captured; EF_SEL_ID while IDs are off or EF_SEL_LABEL while labels are off; an ID-consuming call on a
+ * context whose uploaded ID lane was refused (ef_set_surfel_ids above).  The erase calls only: a context created with close_loops = 1 (its
+ * sampled graph nodes, fern keyframes and pending end-of-frame record describe the unedited map); select and gather work on such contexts. */
+#define EF_SEL_BOX        0x01u
+#define EF_SEL_CONF       0x02u
+#define EF_SEL_INIT_TIME  0x04u
+#define EF_SEL_LAST_TIME  0x08u
+#define EF_SEL_RADIUS     0x10u
+#define EF_SEL_ID         0x20u   /* needs ef_set_surfel_ids on */
+#define EF_SEL_LABEL      0x40u   /* needs ef_enable_labels on  */
+#define EF_SEL_INVERT     0x100u
+typedef struct ef_map_selection {
+  uint32_t tests;                 /* OR of EF_SEL_*; 0 selects every row */
+  double T_bw[16];                /* box frame <- world, row-major; rounded to f32 once on the host */
+  float box_min[3], box_max[3];
+  float conf_min, conf_max;
+  int init_time_min, init_time_max;
+  int last_time_min, last_time_max;
+  float radius_min, radius_max;
+  uint32_t id_min, id_max;
+  int label_class;
+  float label_min_prob;
+} ef_map_selection;
+/* tests 0, T_bw the identity, the box -inf .. +inf, every range covering everything (times INT_MIN .. INT_MAX, IDs 0 .. 0xFFFFFFFF), label_class 0,
+ * label_min_prob -inf.  Needs neither a context nor a GPU. */
+void ef_default_map_selection(ef_map_selection* sel);
+int ef_map_select(ef_ctx* ctx, const ef_map_selection* sel, uint32_t* rows, uint32_t max_rows, uint32_t* count);
+int ef_map_select_dev(ef_ctx* ctx, const ef_map_selection* sel, uint32_t* rows_dev, uint32_t max_rows, uint32_t* count_dev);
+int ef_map_gather(ef_ctx* ctx, const uint32_t* rows, uint32_t n, float* surfels12);
+int ef_map_gather_dev(ef_ctx* ctx, const uint32_t* rows_dev, uint32_t n, float* surfels12_dev);
+int ef_map_erase(ef_ctx* ctx, const ef_map_selection* sel, uint32_t* removed_or_null);
+int ef_map_erase_rows(ef_ctx* ctx, const uint32_t* rows, uint32_t n, uint32_t* removed_or_null);
+int ef_map_erase_rows_dev(ef_ctx* ctx, const uint32_t* rows_dev, uint32_t n, uint32_t* removed_or_null);
+
 /* named internal images, copied to HOST (synchronises); for tests and for a front-end's drawing code */
 enum ef_image {
   EF_IMG_DEPTH_FILTERED = 0,      /* u16  */
