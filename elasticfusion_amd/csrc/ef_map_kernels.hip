@@ -402,6 +402,9 @@ struct Sprite {
   float u, v, hs;
   bool ok;
 };
+// GLSL's min(x, y) = y < x ? y : x and max(x, y) = x < y ? y : x (fminf / fmaxf treat a NaN operand differently)
+__device__ __forceinline__ float glmin(float x, float y) { return y < x ? y : x; }
+__device__ __forceinline__ float glmax(float x, float y) { return x < y ? y : x; }
 // splat.vert:53-87 for one surfel
 __device__ __forceinline__ Sprite make_sprite(const Cam& cam, const rt34& T, float4 pc, float4 ct, float4 nr, float maxDepth,
                                               float confThreshold, float ftime, float fmaxTime, float ftd) {
@@ -421,12 +424,11 @@ __device__ __forceinline__ Sprite make_sprite(const Cam& cam, const rt34& T, flo
   const float q2x = ((fx * b.x) / b.z) + cx, q2y = ((fy * b.y) / b.z) + cy;
   const float q3x = ((fx * c.x) / c.z) + cx, q3y = ((fy * c.y) / c.z) + cy;
   const float q4x = ((fx * d.x) / d.z) + cx, q4y = ((fy * d.y) / d.z) + cy;
-  const float xmin = fminf(q1x, fminf(q2x, fminf(q3x, q4x))), xmax = fmaxf(q1x, fmaxf(q2x, fmaxf(q3x, q4x)));
-  const float ymin = fminf(q1y, fminf(q2y, fminf(q3y, q4y))), ymax = fmaxf(q1y, fmaxf(q2y, fmaxf(q3y, q4y)));
-  // fminf/fmaxf drop NaNs, so test the operands themselves: any NaN corner => degenerate sprite, skipped (spec)
-  if (q1x != q1x || q2x != q2x || q3x != q3x || q4x != q4x || q1y != q1y || q2y != q2y || q3y != q3y || q4y != q4y) return S;
-  float size = fmaxf(0.f, fmaxf(fabsf(xmax - xmin), fabsf(ymax - ymin)));
-  if (size != size) return S;
+  // splat.vert:79-85 with GLSL's min / max to the letter (N6, efo_combined_predict): a NaN corner coordinate is dropped or kept by its position in
+  // the nest, and max(0, NaN) = 0 — the size is never NaN; a sprite whose extent is NaN is a point of size 0, clamped to 1 below
+  const float xmin = glmin(q1x, glmin(q2x, glmin(q3x, q4x))), xmax = glmax(q1x, glmax(q2x, glmax(q3x, q4x)));
+  const float ymin = glmin(q1y, glmin(q2y, glmin(q3y, q4y))), ymax = glmax(q1y, glmax(q2y, glmax(q3y, q4y)));
+  float size = glmax(0.f, glmax(fabsf(xmax - xmin), fabsf(ymax - ymin)));
   size = fminf(fmaxf(size, 1.0f), 2047.0f);  // N3
   S.u = ((fx * S.p.x) / S.p.z) + cx;
   S.v = ((fy * S.p.y) / S.p.z) + cy;
@@ -595,8 +597,12 @@ __global__ void __launch_bounds__(BLK) k_surface_resolve(const Cam cam, const fl
     dense_sample(cam, px, py, im, dense_counter);
   }
 }
-// IndexMap::synthesizeDepth (G6): depth_splat.frag's only output is the intersection depth the z-buffer key already holds
-__global__ void __launch_bounds__(BLK) k_depth_resolve(int cols, int rows, unsigned long long* zbuf, float* __restrict__ depth) {
+// IndexMap::synthesizeDepth (G6): depth_splat.frag's only output is the intersection depth the z-buffer key already holds — except for the sign
+// of a zero, which the key does not keep (ef_zkey.hpp: -0 and +0 tie): there the winner's fragment is evaluated again, as k_surface_resolve does
+__global__ void __launch_bounds__(BLK) k_depth_resolve(const Cam cam, const float* __restrict__ T16, SurfelSoA map, float maxDepth,
+                                                        float confThreshold, int time, int maxTime, int timeDelta, unsigned long long* zbuf,
+                                                        float* __restrict__ depth) {
+  const int cols = cam.cols, rows = cam.rows;
   const int pi = blockIdx.x * blockDim.x + threadIdx.x;
   if (pi >= cols * rows) return;
   const int py = pi / cols, px = pi - py * cols, zi = px * rows + py;   // (column-major z-buffer: k_surface_resolve)
@@ -605,6 +611,14 @@ __global__ void __launch_bounds__(BLK) k_depth_resolve(int cols, int rows, unsig
   if (key != ZBUF_EMPTY) {
     zbuf[zi] = ZBUF_EMPTY;
     z = depth_of_key((uint32_t)(key >> 32));
+    if (z == 0.f) {
+      const uint32_t id = (uint32_t)key;
+      const rt34 T = rt34_load16(T16);
+      const Sprite S = make_sprite(cam, T, map.pos_conf[id], map.col_time[id], map.nrm_rad[id], maxDepth, confThreshold, (float)time,
+                                   (float)maxTime, (float)timeDelta);
+      // (S.ok and the fragment's own verdict are not looked at: the winner passed both in the splat, as in k_surface_resolve)
+      sprite_fragment(cam, S, px, py, z);  // same operations as the splat => same bits
+    }
   }
   depth[pi] = z;
 }
@@ -1400,7 +1414,8 @@ void synthesize_depth(const Cam& cam, const float* T_cw16_dev, SurfelSoA map, co
     hipLaunchKernelGGL(k_surface_splat<false>, dim3(SPLAT_GRID), dim3(BLK), 0, s, cam, T_cw16_dev, map, count_dev, maxDepth, confThreshold,
                        time, maxTime, timeDelta, zbuf, (unsigned*)nullptr, 0u, (const float4*)nullptr);
   const int n = cam.cols * cam.rows;
-  hipLaunchKernelGGL(k_depth_resolve, dim3(ceil_div(n, BLK)), dim3(BLK), 0, s, cam.cols, cam.rows, zbuf, depth);
+  hipLaunchKernelGGL(k_depth_resolve, dim3(ceil_div(n, BLK)), dim3(BLK), 0, s, cam, T_cw16_dev, map, maxDepth, confThreshold, time, maxTime, timeDelta,
+                     zbuf, depth);
 }
 void build_ray_table(const Cam& cam, float* rays4, hipStream_t s) {
   hipLaunchKernelGGL(k_ray_table, dim3(ceil_div(cam.cols * cam.rows, BLK)), dim3(BLK), 0, s, cam, (float4*)rays4);

@@ -210,6 +210,10 @@ void efo_predict_indices(const efo_cam* cam, const double* T_wc16, int time, con
   }
 }
 
+// GLSL 4.x 8.3: min(x, y) "returns y if y < x, otherwise it returns x"; max(x, y) "returns y if x < y, otherwise it returns x"
+inline float glmin(float x, float y) { return y < x ? y : x; }
+inline float glmax(float x, float y) { return x < y ? y : x; }
+
 // IndexMap::combinedPredict + splat.vert + combo_splat.frag (G5)
 void efo_combined_predict(const efo_cam* cam, const double* T_wc16, const float* surfels, int count, float maxDepth,
                           float confThreshold, int time, int maxTime, int timeDelta, uint8_t* image, float* vertex,
@@ -236,10 +240,11 @@ void efo_combined_predict(const efo_cam* cam, const double* T_wc16, const float*
     f3 x1{(t1.x * rad) * 1.41421356f, (t1.y * rad) * 1.41421356f, (t1.z * rad) * 1.41421356f};
     f3 y1 = cross(n, x1);
     f3 q1 = projImage(p + x1), q2 = projImage(p + y1), q3 = projImage(p - y1), q4 = projImage(p - x1);
-    float xmin = fminf(q1.x, fminf(q2.x, fminf(q3.x, q4.x))), xmax = fmaxf(q1.x, fmaxf(q2.x, fmaxf(q3.x, q4.x)));
-    float ymin = fminf(q1.y, fminf(q2.y, fminf(q3.y, q4.y))), ymax = fmaxf(q1.y, fmaxf(q2.y, fmaxf(q3.y, q4.y)));
-    float size = fmaxf(0.f, fmaxf(fabsf(xmax - xmin), fabsf(ymax - ymin)));
-    if (std::isnan(size) || std::isnan(xmin) || std::isnan(ymin)) continue;  // degenerate sprite axis: specified skip
+    // splat.vert:79-85 with GLSL's min / max to the letter (glmin / glmax above): a NaN corner coordinate is dropped or kept by its POSITION in
+    // the nest, and max(0, NaN) = 0 — the point size is never NaN; a sprite whose extent is NaN is a point of size 0, clamped to 1 (N6)
+    float xmin = glmin(q1.x, glmin(q2.x, glmin(q3.x, q4.x))), xmax = glmax(q1.x, glmax(q2.x, glmax(q3.x, q4.x)));
+    float ymin = glmin(q1.y, glmin(q2.y, glmin(q3.y, q4.y))), ymax = glmax(q1.y, glmax(q2.y, glmax(q3.y, q4.y)));
+    float size = glmax(0.f, glmax(fabsf(xmax - xmin), fabsf(ymax - ymin)));
     size = fminf(fmaxf(size, 1.0f), 2047.0f);                                // N3
     float u = ((fx * p.x) / p.z) + cx, v = ((fy * p.y) / p.z) + cy;
     if (!(u >= 0 && u < (float)cols && v >= 0 && v < (float)rows)) continue;  // point clipped by its centre

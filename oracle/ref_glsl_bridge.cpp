@@ -185,7 +185,7 @@ void efg_combined_predict(const efo_cam* cam, const double* T_wc16, const float*
     V::shader_main();
     if (glsl::gl_Position.w != 1.0f) continue;   // the rejected-vertex marker of splat.vert:58-62 (w = 1000): far outside the clip volume
     float size = glsl::gl_PointSize;
-    if (std::isnan(size) || std::isnan(glsl::gl_Position.x) || std::isnan(glsl::gl_Position.y)) continue;   // degenerate sprite axis: specified skip
+    if (std::isnan(size) || std::isnan(glsl::gl_Position.x) || std::isnan(glsl::gl_Position.y)) continue;   // (the size never is: max(0, NaN) = 0, N6; a NaN centre is outside the viewport)
     size = std::min(std::max(size, 1.0f), 2047.0f);   // N3
     const double u = window_coord(glsl::gl_Position.x, cols), v = window_coord(glsl::gl_Position.y, rows);
     if (!(u >= 0 && u < cols && v >= 0 && v < rows)) continue;   // N1: a point is clipped by its centre
