@@ -30,6 +30,20 @@ struct StageTimer {
   bool used;
 };
 
+// A device buffer that grows on demand (reserve, beside dev_alloc).  No growth policy: the caller asks for the size it wants, slack included.
+struct DevBuf {
+  uint8_t* p = nullptr;
+  size_t bytes = 0;
+  int reserve(ef_ctx* c, size_t need, const char* what, bool* grew = nullptr);
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+  template <class T>
+  T* as() const { return (T*)p; }
+};
+
 }  // namespace
 
 struct ef_ctx {
@@ -201,57 +215,57 @@ struct ef_ctx {
   std::vector<hipEvent_t> ka_start, ka_stop;   // the persistent tracker launch (fast order)
   eft::KernelProbe probe_all{nullptr, nullptr, 0, 0};
   hipStream_t debug_stream = nullptr;          // ef_debug_occupy
-  // ef_render_model: its own z-buffer (never the frame's) and, for host-pointer renders, a device landing area for the requested outputs;
-  // both allocated on first use, grown on demand, freed by ef_destroy
-  unsigned long long* render_zbuf = nullptr;
-  size_t render_zbuf_n = 0;
-  uint8_t* render_out = nullptr;
-  size_t render_out_bytes = 0;
+  // Host-pointer entry points of the map operations (ef_host_*.inc): the ONE device landing area their host arguments are staged through, grown
+  // on demand, freed by ef_destroy.  Each call lays its own bytes out in it.  What makes one area enough:
+  //  - a host-pointer entry point reserves `stage` at most once, before it enqueues anything that reads or writes it;
+  //  - it never calls another host-pointer entry point (the _dev tier and the helpers below it take device pointers);
+  //  - it ends with hipStreamSynchronize(stream) on success, so nothing of it is in flight when the next one starts;
+  //  - after an early error return the next user's copies are ordered behind the leftovers on the same stream, and a reserve that grows
+  //    synchronises before it frees.
+  DevBuf stage;
+  // ef_render_model: its own z-buffer (never the frame's), allocated on first use, grown on demand, freed by ef_destroy
+  struct RenderState { DevBuf zbuf; } render;
   // stable surfel IDs and labels (ef_set_surfel_ids / ef_enable_labels; kernels in ef_labels.inc).  ids_state (device, kept for the context's
   // lifetime once allocated): [0] the next ID, [1] the shape flag of ids_check, [2 + k] the row count of label alignment k.  The table and
-  // the ID list it was aligned to exist twice (ping-pong, label_cur the live half), label_rows rows each, grown on demand.  label_known is
-  // the map count as of label_known_frames frames (stamps.size()): an upper bound of the count needs no device round trip.
-  bool ids_on = false, ids_bad = false;
-  unsigned* ids_state = nullptr;
-  int label_C = 0, label_cur = 0;
-  float* label_tab[2] = {};
-  uint32_t* label_ids[2] = {};
-  size_t label_rows = 0, label_bound = 0;
-  size_t label_known = 0, label_known_frames = 0, label_ev_frames = 0;
-  unsigned* label_count_h = nullptr;       // pinned: the count each label call leaves behind, valid once label_ev has completed
-  hipEvent_t label_ev = nullptr;
-  bool label_ev_pending = false;
-  uint32_t* label_index = nullptr;         // the view's index image
-  size_t label_index_n = 0;
-  uint8_t* label_stage = nullptr;          // host-pointer calls: the probability image in, the label images out
-  size_t label_stage_bytes = 0;
+  // the ID list it was aligned to exist twice (ping-pong, cur the live half), rows rows each, grown on demand.  known is
+  // the map count as of known_frames frames (stamps.size()): an upper bound of the count needs no device round trip.
+  struct LabelState {
+    bool ids_on = false, ids_bad = false;
+    unsigned* ids_state = nullptr;
+    int C = 0, cur = 0;
+    float* tab[2] = {};
+    uint32_t* ids[2] = {};
+    size_t rows = 0, bound = 0;
+    size_t known = 0, known_frames = 0, ev_frames = 0;
+    unsigned* count_h = nullptr;           // pinned: the count each label call leaves behind, valid once ev has completed
+    hipEvent_t ev = nullptr;
+    bool ev_pending = false;
+    DevBuf index;                          // the view's index image
+  } labels;
   // spatial index and nearest / kNN queries (ef_query_nearest / ef_query_knn; kernels in ef_query.inc).  map_gen counts the calls that can
   // change the map's rows or positions; the index is rebuilt when it or the cell size differs from what the index was built for.
-  uint64_t map_gen = 1, query_gen = 0;
-  float query_cell = EF_QUERY_DEFAULT_CELL, query_built_cell = 0.f;
-  int query_lanes = 0;                     // lanes per query; 0 = the measured choice: 16 for nearest, 1 for kNN (ef_debug_query_lanes)
-  float4* query_sorted = nullptr;          // the cell-sorted copy {x, y, z, conf} and each record's map row
-  uint32_t* query_rows = nullptr;
-  size_t query_cap = 0;
-  uint32_t* query_cells = nullptr;         // buckets (ends after the build) followed by the scan's tile sums
-  size_t query_cells_cap = 0;
-  uint32_t query_nb = 0, query_n = 0;
-  uint8_t* query_stage = nullptr;          // host-pointer calls: the points in, the results out
-  size_t query_stage_bytes = 0;
+  uint64_t map_gen = 1;
+  struct QueryState {
+    uint64_t gen = 0;
+    float cell = EF_QUERY_DEFAULT_CELL, built_cell = 0.f;
+    int lanes = 0;                         // lanes per query; 0 = the measured choice: 16 for nearest, 1 for kNN (ef_debug_query_lanes)
+    DevBuf sorted, rows;                   // the cell-sorted copy {x, y, z, conf} and each record's map row: grown together
+    DevBuf cells;                          // buckets (ends after the build) followed by the scan's tile sums
+    uint32_t nb = 0, n = 0;
+  } query;
   // registration against the map (ef_register_step / ef_register_cloud; kernels in ef_register.inc): grown by the first call, freed with the context
-  uint8_t* reg_slabs = nullptr;            // the workgroups' slabs followed by the step's 32 sums
-  size_t reg_slabs_bytes = 0;
-  double* reg_sums_h = nullptr;            // pinned: the 32 sums of a step
-  uint8_t* reg_stage = nullptr;            // host-pointer calls: points and normals in, row and plane out
-  size_t reg_stage_bytes = 0;
+  struct RegisterState {
+    DevBuf slabs;                          // the workgroups' slabs followed by the step's 32 sums
+    double* sums_h = nullptr;              // pinned: the 32 sums of a step
+  } reg;
   // select / gather / erase (ef_map_select, ef_map_gather, ef_map_erase; kernels in ef_select.inc): scratch of their own (never c->cs: clean()
-  // owns its halves), grown by the first call, freed with the context.  sel_count is the map count as of map_gen == sel_gen.
-  uint8_t* sel_scratch = nullptr;          // chunk counts | chunk offsets | 4 words (the total) | one flag byte per row
-  size_t sel_scratch_bytes = 0, sel_rows = 0;
-  uint8_t* sel_stage = nullptr;            // host-pointer calls: rows in or out, the surfels out
-  size_t sel_stage_bytes = 0;
-  uint64_t sel_gen = 0;
-  uint32_t sel_count = 0;
+  // owns its halves), grown by the first call, freed with the context.  count is the map count as of map_gen == gen.
+  struct SelectState {
+    DevBuf scratch;                        // chunk counts | chunk offsets | 4 words (the total) | one flag byte per row
+    size_t rows = 0;
+    uint64_t gen = 0;
+    uint32_t count = 0;
+  } sel;
 };
 
 namespace {
@@ -303,6 +317,19 @@ int dev_alloc(ef_ctx* c, T** p, size_t n, int fill = 0) {
     int _r = dev_alloc((c), &(p), (size_t)(n), ##__VA_ARGS__);   \
     if (_r != EF_OK) return _r;                                  \
   } while (0)
+// Nothing when `need` bytes are there; else the stream is waited for (work still queued may use the old buffer), the old buffer freed and a
+// new one allocated, its contents undefined.  A failed allocation leaves the buffer empty.
+int DevBuf::reserve(ef_ctx* c, size_t need, const char* what, bool* grew) {
+  if (grew) *grew = false;
+  if (need <= bytes) return EF_OK;
+  EF_HIP(c, hipStreamSynchronize(c->stream));
+  release();
+  hipError_t e = hipMalloc((void**)&p, need);
+  if (e != hipSuccess) { p = nullptr; c->err = std::string("hipMalloc (") + what + "): " + hipGetErrorString(e); return EF_ENOMEM; }
+  bytes = need;
+  if (grew) *grew = true;
+  return EF_OK;
+}
 
 // scalar per-frame bookkeeping kernels -----------------------------------------------------------
 __global__ void k_init_state(eft::TrackState* st, int dense_samples, int pixels) {
@@ -1207,32 +1234,72 @@ void ctx_free(ef_ctx* c) {
   for (auto e : c->ka_stop) (void)hipEventDestroy(e);
   for (auto e : c->ks_start) (void)hipEventDestroy(e);
   for (auto e : c->ks_stop) (void)hipEventDestroy(e);
-  if (c->render_zbuf) (void)hipFree(c->render_zbuf);
-  if (c->render_out) (void)hipFree(c->render_out);
+  for (DevBuf* b : {&c->stage, &c->render.zbuf, &c->labels.index, &c->query.sorted, &c->query.rows, &c->query.cells, &c->reg.slabs, &c->sel.scratch})
+    b->release();
   for (int k = 0; k < 2; ++k) {
-    if (c->label_tab[k]) (void)hipFree(c->label_tab[k]);
-    if (c->label_ids[k]) (void)hipFree(c->label_ids[k]);
+    if (c->labels.tab[k]) (void)hipFree(c->labels.tab[k]);
+    if (c->labels.ids[k]) (void)hipFree(c->labels.ids[k]);
   }
-  if (c->ids_state) (void)hipFree(c->ids_state);
-  if (c->label_index) (void)hipFree(c->label_index);
-  if (c->label_stage) (void)hipFree(c->label_stage);
-  if (c->label_count_h) (void)hipHostFree(c->label_count_h);
-  if (c->label_ev) (void)hipEventDestroy(c->label_ev);
-  if (c->query_sorted) (void)hipFree(c->query_sorted);
-  if (c->query_rows) (void)hipFree(c->query_rows);
-  if (c->query_cells) (void)hipFree(c->query_cells);
-  if (c->query_stage) (void)hipFree(c->query_stage);
-  if (c->reg_slabs) (void)hipFree(c->reg_slabs);
-  if (c->reg_sums_h) (void)hipHostFree(c->reg_sums_h);
-  if (c->reg_stage) (void)hipFree(c->reg_stage);
-  if (c->sel_scratch) (void)hipFree(c->sel_scratch);
-  if (c->sel_stage) (void)hipFree(c->sel_stage);
+  if (c->labels.ids_state) (void)hipFree(c->labels.ids_state);
+  if (c->labels.count_h) (void)hipHostFree(c->labels.count_h);
+  if (c->labels.ev) (void)hipEventDestroy(c->labels.ev);
+  if (c->reg.sums_h) (void)hipHostFree(c->reg.sums_h);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
 }
 
-// surfel IDs around the map's download / upload (defined with the label entry points at the end of this file)
-int ids_prepare(ef_ctx* c, const char* fn);
-int ids_uploaded(ef_ctx* c, uint32_t count);
+// ---- what the map's download / upload and the map operations (ef_host_*.inc) share ----
+// never inside a capture: a map operation recorded into a graph would be replayed with every frame
+int capture_check(ef_ctx* c, const char* fn) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  EF_HIP(c, hipStreamIsCapturing(c->stream, &cs));
+  if (cs != hipStreamCaptureStatusNone) { c->err = std::string(fn) + ": the context's stream is being captured"; return EF_ESTATE; }
+  return EF_OK;
+}
+int read_count(ef_ctx* c, uint32_t* n) {
+  EF_HIP(c, hipMemcpyAsync(n, &c->st->map_counts[c->cur], sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  EF_HIP(c, hipStreamSynchronize(c->stream));
+  return EF_OK;
+}
+// the two float pose matrices derived from a double T_wc
+void pose_mats(const double* T16, float* Tcw_host, float* pose_host) {
+  const efl::SE3 T = efl::se3_from_matrix(T16);
+  efl::se3_inverse_matrix_f(T, Tcw_host);
+  efl::se3_castf_matrix(T, pose_host);
+}
+bool finite16(const double* T) {
+  for (int i = 0; i < 16; ++i)
+    if (!std::isfinite(T[i])) return false;
+  return true;
+}
+// the lazy numbering every ID-consuming call starts with
+int ids_prepare(ef_ctx* c, const char* fn) {
+  if (c->labels.ids_bad) {
+    c->err = std::string(fn) + ": the uploaded map's ID lane (float 5 of each surfel) is not a strictly increasing non-zero prefix followed by "
+             "a zero suffix";
+    return EF_ESTATE;
+  }
+  efm::ids_assign(c->maps[c->cur], &c->st->map_counts[c->cur], c->labels.ids_state, c->stream);
+  EF_HIP(c, hipGetLastError());
+  return EF_OK;
+}
+// ef_map_upload with IDs on: the uploaded lane is kept when its shape is valid (the counter then continues above its largest ID, ids_assign);
+// any other shape is remembered and refused by the next ID-consuming call.  Labels restart from the prior.
+int ids_uploaded(ef_ctx* c, uint32_t count) {
+  EF_HIP(c, hipMemsetAsync(c->labels.ids_state + 1, 0, sizeof(unsigned), c->stream));
+  efm::ids_check(c->maps[c->cur], count, c->labels.ids_state + 1, c->stream);
+  EF_HIP(c, hipGetLastError());
+  unsigned flag = 0;
+  EF_HIP(c, hipMemcpyAsync(&flag, c->labels.ids_state + 1, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+  EF_HIP(c, hipStreamSynchronize(c->stream));
+  c->labels.ids_bad = flag != 0;
+  if (c->labels.C) {
+    EF_HIP(c, hipMemsetAsync(c->labels.ids_state + 2 + c->labels.cur, 0, sizeof(unsigned), c->stream));
+    c->labels.known = count;
+    c->labels.known_frames = c->stamps.size();
+    c->labels.ev_pending = false;
+  }
+  return EF_OK;
+}
 
 }  // namespace
 
@@ -1762,7 +1829,7 @@ int ef_map_count(ef_ctx* c, uint32_t* count) {
 int ef_map_download(ef_ctx* c, float* surfels, uint32_t max_surfels, uint32_t* count) {
   if (!c || !count) return EF_EINVAL;
   DeviceGuard dg_(c);
-  if (c->ids_on) {   // rows created since the last ID-consuming call get theirs first
+  if (c->labels.ids_on) {   // rows created since the last ID-consuming call get theirs first
     const int ri = ids_prepare(c, "ef_map_download");
     if (ri != EF_OK) return ri;
   }
@@ -1811,7 +1878,7 @@ int ef_map_upload(ef_ctx* c, const float* surfels, uint32_t count) {
     EF_HIP(c, e);
   }
   hipLaunchKernelGGL(k_set_count, dim3(1), dim3(64), 0, c->stream, &c->st->map_counts[c->cur], count);
-  if (c->ids_on) return ids_uploaded(c, count);
+  if (c->labels.ids_on) return ids_uploaded(c, count);
   return EF_OK;
 }
 int ef_get_pose_qt(ef_ctx* c, double* q4_t3) {
@@ -2184,1697 +2251,12 @@ int ef_get_splat_timing(ef_ctx* c, ef_kernel_time* out) {
   return EF_OK;
 }
 
-// Box calibration for bench.py (GPU boxes of one pool differ by 10-20 %): an EMPTY kernel and a kernel that streams 16 MB in and 16 MB out
-// with 16-byte accesses, 200 back-to-back launches each on `stream`, averaged over the batch with two events (so launch gaps are in).
-__global__ void k_calib_empty() {}
-__global__ void __launch_bounds__(256) k_calib_stream(const float4* __restrict__ src, float4* __restrict__ dst, int n) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) dst[i] = src[i];
-}
-int ef_dev_calibrate(void* stream, float* empty_us, float* stream16mb_us) {
-  if (!empty_us || !stream16mb_us) return EF_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const int n = 1 << 20, reps = 200;   // 1 Mi float4 = 16 MiB
-  float4 *a = nullptr, *b = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  int rc = EF_EHIP;
-  float ms = 0;
-  if (hipMalloc((void**)&a, (size_t)n * sizeof(float4)) != hipSuccess || hipMalloc((void**)&b, (size_t)n * sizeof(float4)) != hipSuccess) { rc = EF_ENOMEM; goto done; }
-  if (hipMemsetAsync(a, 0, (size_t)n * sizeof(float4), s) != hipSuccess) goto done;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) goto done;
-  for (int pass = 0; pass < 2; ++pass) {   // pass 0 warms up
-    if (hipEventRecord(e0, s) != hipSuccess) goto done;
-    for (int i = 0; i < reps; ++i) hipLaunchKernelGGL(k_calib_empty, dim3(256), dim3(256), 0, s);
-    if (hipEventRecord(e1, s) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) goto done;
-    *empty_us = 1e3f * ms / reps;
-    if (hipEventRecord(e0, s) != hipSuccess) goto done;
-    for (int i = 0; i < reps; ++i) hipLaunchKernelGGL(k_calib_stream, dim3(2048), dim3(256), 0, s, (const float4*)a, b, n);
-    if (hipEventRecord(e1, s) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) goto done;
-    *stream16mb_us = 1e3f * ms / reps;
-  }
-  rc = EF_OK;
-done:
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (a) (void)hipFree(a);
-  if (b) (void)hipFree(b);
-  return rc;
-}
-
-int ef_dev_alloc(void** dev, size_t bytes) { return hipMalloc(dev, bytes ? bytes : 1) == hipSuccess ? EF_OK : EF_ENOMEM; }
-int ef_dev_free(void* dev) { return hipFree(dev) == hipSuccess ? EF_OK : EF_EHIP; }
-int ef_dev_upload(void* dev, const void* host, size_t bytes) { return hipMemcpy(dev, host, bytes, hipMemcpyHostToDevice) == hipSuccess ? EF_OK : EF_EHIP; }
-int ef_dev_download(void* host, const void* dev, size_t bytes) { return hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost) == hipSuccess ? EF_OK : EF_EHIP; }
-int ef_dev_memset(void* dev, int value, size_t bytes) { return hipMemset(dev, value, bytes) == hipSuccess ? EF_OK : EF_EHIP; }
-int ef_dev_sync(void) { return hipDeviceSynchronize() == hipSuccess ? EF_OK : EF_EHIP; }
-int ef_device_count(int* n) { return hipGetDeviceCount(n) == hipSuccess ? EF_OK : EF_EHIP; }
-int ef_set_device(int d) { return hipSetDevice(d) == hipSuccess ? EF_OK : EF_EHIP; }
-
-// ---- operator tier: tracking ----
-#define OP_TAIL(s)                                                         \
-  do {                                                                     \
-    hipError_t _e = hipGetLastError();                                     \
-    if (_e != hipSuccess) { g_create_error = hipGetErrorString(_e); return EF_EHIP; } \
-    return EF_OK;                                                          \
-  } while (0)
-#define OP_SYNC(s)                                                         \
-  do {                                                                     \
-    hipError_t _e = hipStreamSynchronize((hipStream_t)(s));                \
-    if (_e == hipSuccess) _e = hipGetLastError();                          \
-    if (_e != hipSuccess) { g_create_error = hipGetErrorString(_e); return EF_EHIP; } \
-  } while (0)
-
-int ef_op_pyr_down(const uint16_t* src, int sc, int sr, uint16_t* dst, void* s) { eft::pyr_down_u16(src, sc, sr, dst, (hipStream_t)s); OP_TAIL(s); }
-int ef_op_create_vmap(const ef_intr* k, const uint16_t* depth, int cols, int rows, float cutoff, float* vmap, void* s) {
-  eft::create_vmap(depth, cols, rows, eft::Intr{k->fx, k->fy, k->cx, k->cy}, cutoff, vmap, (hipStream_t)s);
-  OP_TAIL(s);
-}
-int ef_op_create_nmap(const float* vmap, int cols, int rows, float* nmap, void* s) { eft::create_nmap(vmap, cols, rows, nmap, (hipStream_t)s); OP_TAIL(s); }
-int ef_op_transform_maps(const float* vs, const float* ns, int cols, int rows, const float* R9, const float* t3, float* vd, float* nd, void* s) {
-  float* rt = nullptr;
-  if (hipMalloc((void**)&rt, 12 * sizeof(float)) != hipSuccess) return EF_ENOMEM;
-  float h[12];
-  memcpy(h, R9, 36);
-  memcpy(h + 9, t3, 12);
-  (void)hipMemcpyAsync(rt, h, sizeof(h), hipMemcpyHostToDevice, (hipStream_t)s);
-  eft::transform_maps(vs, ns, cols, rows, rt, rt + 9, vd, nd, (hipStream_t)s);
-  (void)hipStreamSynchronize((hipStream_t)s);
-  (void)hipFree(rt);
-  OP_TAIL(s);
-}
-int ef_op_copy_maps(const float* v4, const float* n4, int cols, int rows, float* tmp, float* vd, float* nd, void* s) {
-  eft::copy_maps(v4, n4, cols, rows, tmp, vd, nd, (hipStream_t)s);
-  OP_TAIL(s);
-}
-int ef_op_resize_vmap(const float* in, int sc, int sr, float* out, void* s) { eft::resize_map(in, sc, sr, out, false, (hipStream_t)s); OP_TAIL(s); }
-int ef_op_resize_nmap(const float* in, int sc, int sr, float* out, void* s) { eft::resize_map(in, sc, sr, out, true, (hipStream_t)s); OP_TAIL(s); }
-int ef_op_pyr_down_gauss_f(const float* src, int sc, int sr, float* dst, void* s) { eft::pyr_down_gauss_f(src, sc, sr, dst, (hipStream_t)s); OP_TAIL(s); }
-int ef_op_pyr_down_uchar_gauss(const uint8_t* src, int sc, int sr, uint8_t* dst, void* s) { eft::pyr_down_uchar_gauss(src, sc, sr, dst, (hipStream_t)s); OP_TAIL(s); }
-int ef_op_vertices_to_depth(const float* tmp, int cols, int rows, float cutoff, float* dst, void* s) { eft::vertices_to_depth(tmp, cols, rows, cutoff, dst, (hipStream_t)s); OP_TAIL(s); }
-int ef_op_image_bgr_to_intensity(const uint8_t* rgba, int cols, int rows, uint8_t* dst, void* s) { eft::bgr_to_intensity(rgba, 4, cols, rows, dst, (hipStream_t)s); OP_TAIL(s); }
-int ef_op_compute_derivative_images(const uint8_t* src, int cols, int rows, int16_t* dx, int16_t* dy, void* s) {
-  eft::derivative_images(src, cols, rows, dx, dy, (hipStream_t)s);
-  OP_TAIL(s);
-}
-int ef_op_project_to_point_cloud(const float* depth, int cols, int rows, const ef_intr* k0, int level, float* cloud, void* s) {
-  eft::project_to_point_cloud(depth, cols, rows, eft::intr_level(eft::Intr{k0->fx, k0->fy, k0->cx, k0->cy}, level), cloud, (hipStream_t)s);
-  OP_TAIL(s);
-}
-
-static int op_scratch(float** partials, float** out, int nfloats_out) {
-  if (hipMalloc((void**)partials, (size_t)eft::OP_SCRATCH_FLOATS * sizeof(float)) != hipSuccess) return EF_ENOMEM;
-  if (hipMalloc((void**)out, nfloats_out * sizeof(float)) != hipSuccess) { (void)hipFree(*partials); return EF_ENOMEM; }
-  return EF_OK;
-}
-static void unpack29_host(const float* h, float* A, float* b) {
-  int shift = 0;
-  for (int i = 0; i < 6; ++i)
-    for (int j = i; j < 7; ++j) {
-      const float v = h[shift++];
-      if (j == 6) b[i] = v;
-      else A[j * 6 + i] = A[i * 6 + j] = v;
-    }
-}
-int ef_op_icp_step(const float* Rc, const float* tc, const float* vc, const float* nc, const float* Rpi, const float* tp, const ef_intr* k,
-                   const float* vg, const float* ng, float dist, float ang, int cols, int rows, float* A, float* b, float* res, void* s) {
-  if (cols <= 0 || rows <= 0 || cols > 2048 || rows > 2048) return EF_EINVAL;
-  eft::IcpArgs a;
-  memcpy(a.Rcurr, Rc, 36); memcpy(a.tcurr, tc, 12); memcpy(a.Rprev_inv, Rpi, 36); memcpy(a.tprev, tp, 12);
-  a.k = eft::Intr{k->fx, k->fy, k->cx, k->cy};
-  a.distThres = dist; a.angleThres = ang;
-  float *partials, *out;
-  int r = op_scratch(&partials, &out, 32);
-  if (r != EF_OK) return r;
-  eft::icp_step_op(a, vc, nc, vg, ng, cols, rows, partials, out, (hipStream_t)s);
-  float h[32];
-  (void)hipMemcpyAsync(h, out, 29 * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)s);
-  hipError_t e = hipStreamSynchronize((hipStream_t)s);
-  (void)hipFree(partials); (void)hipFree(out);
-  if (e != hipSuccess) { g_create_error = hipGetErrorString(e); return EF_EHIP; }
-  unpack29_host(h, A, b);
-  res[0] = h[27]; res[1] = h[28];
-  return EF_OK;
-}
-int ef_op_compute_rgb_residual(float minScale, const int16_t* dIdx, const int16_t* dIdy, const float* lastDepth, const float* nextDepth,
-                               const uint8_t* lastImage, const uint8_t* nextImage, void* corres, float maxDepthDelta, const float* kt,
-                               const float* krkinv, int cols, int rows, int* sigma, int* count, void* s) {
-  eft::RgbResidualArgs a;
-  a.minScale = minScale; a.maxDepthDelta = maxDepthDelta;
-  memcpy(a.kt, kt, 12); memcpy(a.krkinv, krkinv, 36);
-  int* out;
-  if (hipMalloc((void**)&out, 2 * sizeof(int)) != hipSuccess) return EF_ENOMEM;
-  eft::rgb_residual_op(a, dIdx, dIdy, lastDepth, nextDepth, lastImage, nextImage, corres, cols, rows, out, (hipStream_t)s);
-  int h[2] = {0, 0};
-  hipError_t e = hipMemcpy(h, out, sizeof(h), hipMemcpyDeviceToHost);
-  (void)hipFree(out);
-  if (e != hipSuccess) { g_create_error = hipGetErrorString(e); return EF_EHIP; }
-  *count = h[0];
-  *sigma = h[1];
-  return EF_OK;
-}
-int ef_op_rgb_step(const void* corres, float sigma, const float* cloud, float fx, float fy, const int16_t* dIdx, const int16_t* dIdy,
-                   float sobelScale, int cols, int rows, float* A, float* b, void* s) {
-  float *partials, *out;
-  int r = op_scratch(&partials, &out, 32);
-  if (r != EF_OK) return r;
-  eft::rgb_step_op(corres, sigma, cloud, fx, fy, dIdx, dIdy, sobelScale, cols, rows, partials, out, (hipStream_t)s);
-  float h[32];
-  (void)hipMemcpyAsync(h, out, 29 * sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)s);
-  hipError_t e = hipStreamSynchronize((hipStream_t)s);
-  (void)hipFree(partials); (void)hipFree(out);
-  if (e != hipSuccess) { g_create_error = hipGetErrorString(e); return EF_EHIP; }
-  unpack29_host(h, A, b);
-  return EF_OK;
-}
-int ef_op_so3_step(const uint8_t* lastImage, const uint8_t* nextImage, const float* ib, const float* kinv, const float* krlr, int cols,
-                   int rows, float* A, float* b, float* res, void* s) {
-  eft::So3Args a;
-  memcpy(a.imageBasis, ib, 36); memcpy(a.kinv, kinv, 36); memcpy(a.krlr, krlr, 36);
-  float *partials, *out;
-  int r = op_scratch(&partials, &out, 16);
-  if (r != EF_OK) return r;
-  eft::so3_step_op(a, lastImage, nextImage, cols, rows, partials, out, (hipStream_t)s);
-  float h[11];
-  (void)hipMemcpyAsync(h, out, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)s);
-  hipError_t e = hipStreamSynchronize((hipStream_t)s);
-  (void)hipFree(partials); (void)hipFree(out);
-  if (e != hipSuccess) { g_create_error = hipGetErrorString(e); return EF_EHIP; }
-  int shift = 0;
-  for (int i = 0; i < 3; ++i)
-    for (int j = i; j < 4; ++j) {
-      const float v = h[shift++];
-      if (j == 3) b[i] = v;
-      else A[j * 3 + i] = A[i * 3 + j] = v;
-    }
-  res[0] = h[9]; res[1] = h[10];
-  return EF_OK;
-}
-
-// ---- operator tier: the driver's small linear algebra, evaluated on the device ----
-}  // extern "C"
-namespace {
-__global__ void k_linalg_probe(int which, const double* __restrict__ in, double* __restrict__ out) {
-  if (which == EF_LINALG_LDLT6_WAVE) {  // the one-element-per-lane factorisation the tracker uses (ef_solve_dev.hpp)
-    __shared__ efs::SolveScratch S;
-    const int lane = threadIdx.x;
-    if (lane < 6) S.b[lane] = in[36 + lane];
-    efs::wave_sync();
-    efs::ldlt6_wave(in[lane < 36 ? lane : 0], S);
-    if (lane < 6) out[lane] = S.x[lane];
-    return;
-  }
-  if (threadIdx.x != 0) return;
-  switch (which) {
-    case EF_LINALG_LDLT6: efl::ldlt_solve<double, 6>(in, in + 36, out); break;
-    case EF_LINALG_LDLT3F: {
-      float A[9], b[3], x[3];
-      for (int i = 0; i < 9; ++i) A[i] = (float)in[i];
-      for (int i = 0; i < 3; ++i) b[i] = (float)in[9 + i];
-      efl::ldlt_solve<float, 3>(A, b, x);
-      for (int i = 0; i < 3; ++i) out[i] = (double)x[i];
-      break;
-    }
-    case EF_LINALG_POLAR3: efl::polar3(in, out); break;
-    case EF_LINALG_RODRIGUES: efl::rodrigues(in, out); break;
-    case EF_LINALG_SE3_INVERSE: efl::se3_matrix(efl::se3_inverse(efl::se3_from_matrix(in)), out); break;
-    case EF_LINALG_SE3_LOG_NORM: out[0] = efl::se3_log_norm(efl::se3_from_matrix(in)); break;
-    case EF_LINALG_SCALAR:
-      out[0] = sqrt(in[0]); out[1] = in[0] / in[1]; out[2] = sin(in[0]); out[3] = cos(in[0]); out[4] = atan2(in[0], in[1]);
-      break;
-    default: break;
-  }
-}
-}  // namespace
-extern "C" {
-int ef_op_linalg(int which, const double* in, int n_in, double* out, int n_out) {
-  if (!in || !out || n_in <= 0 || n_out <= 0 || n_in > 64 || n_out > 64 || which < 0 || which > EF_LINALG_LDLT6_WAVE) return EF_EINVAL;
-  double* d;
-  if (hipMalloc((void**)&d, 128 * sizeof(double)) != hipSuccess) return EF_ENOMEM;
-  (void)hipMemset(d, 0, 128 * sizeof(double));
-  (void)hipMemcpy(d, in, n_in * sizeof(double), hipMemcpyHostToDevice);
-  hipLaunchKernelGGL(k_linalg_probe, dim3(1), dim3(64), 0, 0, which, (const double*)d, d + 64);
-  hipError_t e = hipMemcpy(out, d + 64, n_out * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  if (e != hipSuccess) { g_create_error = hipGetErrorString(e); return EF_EHIP; }
-  return EF_OK;
-}
-
-// ---- operator tier: pre-processing + map ----
-int ef_op_filter_depth(const uint16_t* raw, int cols, int rows, float maxD, uint16_t* filtered, void* s) {
-  if (!efm::filter_depth(raw, cols, rows, maxD, filtered, (hipStream_t)s)) return EF_EHIP;   // (no weight table: device ordinal >= 64, allocation or launch failure)
-  OP_TAIL(s);
-}
-int ef_op_metricise_depth(const uint16_t* in, int cols, int rows, float maxD, float* out, void* s) {
-  efm::metricise_depth(in, cols, rows, maxD, out, (hipStream_t)s);
-  OP_TAIL(s);
-}
-
-}  // extern "C"
-namespace {
-struct OpMap {  // temporary SoA mirror of an AoS surfel list + scratch, for the operator tier
-  std::vector<void*> allocs;
-  template <typename T>
-  T* alloc(size_t n, int fill = 0) {
-    void* p = nullptr;
-    if (hipMalloc(&p, (n ? n : 1) * sizeof(T)) != hipSuccess) return nullptr;
-    (void)hipMemset(p, fill, (n ? n : 1) * sizeof(T));
-    allocs.push_back(p);
-    return (T*)p;
-  }
-  efm::SurfelSoA soa(size_t n) { return efm::SurfelSoA{alloc<float4>(n), alloc<float4>(n), alloc<float4>(n)}; }
-  ~OpMap() { for (void* p : allocs) (void)hipFree(p); }
-};
-efm::Cam to_cam(const ef_cam* c) { return efm::Cam{c->cols, c->rows, c->fx, c->fy, c->cx, c->cy}; }
-// device copies of the two float pose matrices derived from a double T_wc
-void pose_mats(const double* T16, float* Tcw_host, float* pose_host) {
-  const efl::SE3 T = efl::se3_from_matrix(T16);
-  efl::se3_inverse_matrix_f(T, Tcw_host);
-  efl::se3_castf_matrix(T, pose_host);
-}
-}  // namespace
-extern "C" {
-
-int ef_op_seed_map(const ef_cam* cam, const uint8_t* rgb, const float* dm, const float* dmf, int time, float maxDepth, float* surfels,
-                   uint32_t* count_host, void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  OpMap m;
-  const size_t P = (size_t)cam->cols * cam->rows;
-  efm::SurfelSoA soa = m.soa(P);
-  efm::CompactScratch cs;
-  cs.max_chunks = (int)(2 * P / efm::CHUNK + 8);
-  cs.flags = m.alloc<uint8_t>(2 * P);
-  cs.chunk_count = m.alloc<uint32_t>(cs.max_chunks);
-  cs.chunk_offset = m.alloc<uint32_t>(cs.max_chunks);
-  cs.totals = m.alloc<uint32_t>(8);
-  unsigned* cnt = m.alloc<unsigned>(1);
-  efm::seed_map(to_cam(cam), rgb, dm, dmf, time, maxDepth, soa, cnt, cs, s);
-  unsigned h = 0;
-  (void)hipMemcpyAsync(&h, cnt, sizeof(h), hipMemcpyDeviceToHost, s);
-  OP_SYNC(s);
-  efm::soa_to_aos(soa, h, surfels, s);
-  OP_SYNC(s);
-  *count_host = h;
-  return EF_OK;
-}
-
-int ef_op_predict_indices(const ef_cam* cam, const double* T16, int time, const float* surfels, uint32_t count, float maxDepth, int timeDelta,
-                          uint32_t* index, float* vc, float* ct, float* nr, void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  OpMap m;
-  const size_t P = (size_t)cam->cols * cam->rows;
-  efm::SurfelSoA soa = m.soa(count);
-  efm::aos_to_soa(surfels, count, soa, s);
-  float h[32];
-  pose_mats(T16, h, h + 16);
-  float* mats = m.alloc<float>(32);
-  (void)hipMemcpyAsync(mats, h, sizeof(h), hipMemcpyHostToDevice, s);
-  unsigned* cnt = m.alloc<unsigned>(1);
-  (void)hipMemcpyAsync(cnt, &count, sizeof(unsigned), hipMemcpyHostToDevice, s);
-  unsigned long long* zbuf = m.alloc<unsigned long long>(P, 0xFF);
-  efm::IndexMaps im{index, (float4*)vc, (float4*)ct, (float4*)nr};
-  efm::predict_indices(to_cam(cam), mats, time, soa, cnt, maxDepth, timeDelta, zbuf, im, s);
-  OP_SYNC(s);
-  return EF_OK;
-}
-
-int ef_op_combined_predict(const ef_cam* cam, const double* T16, const float* surfels, uint32_t count, float maxDepth, float confThreshold,
-                           int time, int maxTime, int timeDelta, uint8_t* image, float* vertex, float* normal, uint16_t* timeMap, void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  OpMap m;
-  const size_t P = (size_t)cam->cols * cam->rows;
-  efm::SurfelSoA soa = m.soa(count);
-  efm::aos_to_soa(surfels, count, soa, s);
-  float h[32];
-  pose_mats(T16, h, h + 16);
-  float* mats = m.alloc<float>(32);
-  (void)hipMemcpyAsync(mats, h, sizeof(h), hipMemcpyHostToDevice, s);
-  unsigned* cnt = m.alloc<unsigned>(1);
-  (void)hipMemcpyAsync(cnt, &count, sizeof(unsigned), hipMemcpyHostToDevice, s);
-  unsigned long long* zbuf = m.alloc<unsigned long long>(P, 0xFF);
-  efm::PredictMaps pm{(uchar4*)image, (float4*)vertex, (float4*)normal, timeMap};
-  efm::FillMaps none{nullptr, nullptr, nullptr};
-  efm::combined_predict(to_cam(cam), mats, soa, cnt, maxDepth, confThreshold, time, maxTime, timeDelta, zbuf, pm, none, nullptr, nullptr, false,
-                        nullptr, s);
-  OP_SYNC(s);
-  return EF_OK;
-}
-
-int ef_op_synthesize_depth(const ef_cam* cam, const double* T16, const float* surfels, uint32_t count, float maxDepth, float confThreshold,
-                           int time, int maxTime, int timeDelta, float* depth, void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  OpMap m;
-  const size_t P = (size_t)cam->cols * cam->rows;
-  efm::SurfelSoA soa = m.soa(count);
-  efm::aos_to_soa(surfels, count, soa, s);
-  float h[32];
-  pose_mats(T16, h, h + 16);
-  float* mats = m.alloc<float>(32);
-  (void)hipMemcpyAsync(mats, h, sizeof(h), hipMemcpyHostToDevice, s);
-  unsigned* cnt = m.alloc<unsigned>(1);
-  (void)hipMemcpyAsync(cnt, &count, sizeof(unsigned), hipMemcpyHostToDevice, s);
-  unsigned long long* zbuf = m.alloc<unsigned long long>(P, 0xFF);
-  efm::synthesize_depth(to_cam(cam), mats, soa, cnt, maxDepth, confThreshold, time, maxTime, timeDelta, zbuf, depth, s);
-  OP_SYNC(s);
-  return EF_OK;
-}
-
-int ef_op_fill_in(const ef_cam* cam, const uint8_t* image, const float* vertex, const float* normal, const uint16_t* depthFiltered,
-                  const uint8_t* rgb, int passthrough, int passthroughImage, uint8_t* fimage, float* fvertex, float* fnormal, void* s_) {
-  efm::PredictMaps pm{(uchar4*)image, (float4*)vertex, (float4*)normal, nullptr};
-  efm::FillMaps fm{(uchar4*)fimage, (float4*)fvertex, (float4*)fnormal};
-  efm::fill_in(to_cam(cam), pm, depthFiltered, rgb, passthrough != 0, passthroughImage != 0, fm, (hipStream_t)s_);
-  OP_TAIL(s_);
-}
-
-int ef_op_dense_enough(const ef_cam* cam, const uint8_t* image, int* dense_host, void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  OpMap m;
-  unsigned* cnt = m.alloc<unsigned>(1);
-  efm::dense_count(to_cam(cam), (const uchar4*)image, cnt, s);
-  unsigned h = 0;
-  (void)hipMemcpyAsync(&h, cnt, sizeof(h), hipMemcpyDeviceToHost, s);
-  OP_SYNC(s);
-  *dense_host = ((float)h / (float)((cam->cols / 20) * (cam->rows / 20)) > 0.75f) ? 1 : 0;
-  return EF_OK;
-}
-
-int ef_op_fuse(const ef_cam* cam, const double* T16, int time, const uint8_t* rgb, const float* dm, const float* dmf, const uint32_t* index,
-               const float* vc, const float* ct, const float* nr, float maxDepth, float weighting, float* surfels, uint32_t count,
-               float* newUnstable, uint32_t* newCount, void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  OpMap m;
-  efm::SurfelSoA soa = m.soa(count);
-  efm::aos_to_soa(surfels, count, soa, s);
-  float h[33];
-  pose_mats(T16, h, h + 16);
-  h[32] = weighting;
-  float* mats = m.alloc<float>(33);
-  (void)hipMemcpyAsync(mats, h, sizeof(h), hipMemcpyHostToDevice, s);
-  unsigned* cnt = m.alloc<unsigned>(2);
-  (void)hipMemcpyAsync(cnt, &count, sizeof(unsigned), hipMemcpyHostToDevice, s);
-  efm::Candidates cand;
-  cand.n = (cam->cols / 2) * (cam->rows / 2);
-  cand.pos_conf = m.alloc<float4>(cand.n);
-  cand.col_time = m.alloc<float4>(cand.n);
-  cand.nrm_rad = m.alloc<float4>(cand.n);
-  cand.best = m.alloc<uint32_t>(cand.n);
-  uint32_t* winner = m.alloc<uint32_t>(count, 0xFF);
-  efm::IndexMaps im{(uint32_t*)index, (float4*)vc, (float4*)ct, (float4*)nr};
-  efm::fuse(to_cam(cam), mats + 16, time, rgb, dm, dmf, im, maxDepth, mats + 32, soa, cnt, cand, winner, s);
-  efm::soa_to_aos(soa, count, surfels, s);
-  efm::CompactScratch cs;
-  cs.max_chunks = cand.n / efm::CHUNK + 8;
-  cs.flags = m.alloc<uint8_t>(cand.n);
-  cs.chunk_count = m.alloc<uint32_t>(cs.max_chunks);
-  cs.chunk_offset = m.alloc<uint32_t>(cs.max_chunks);
-  cs.totals = m.alloc<uint32_t>(8);
-  efm::candidates_to_aos(cand, newUnstable, cnt + 1, cs, s);
-  unsigned hn = 0;
-  (void)hipMemcpyAsync(&hn, cnt + 1, sizeof(hn), hipMemcpyDeviceToHost, s);
-  OP_SYNC(s);
-  *newCount = hn;
-  return EF_OK;
-}
-
-}  // extern "C"
-namespace {
-// scatter an AoS "newUnstable" list (draw order) back into candidate slots 0..n-1: the clean kernels only
-// need the relative order, which consecutive slots preserve
-__global__ void k_aos_to_cand(const float4* __restrict__ aos, uint32_t n, efm::Candidates cand) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (uint32_t)cand.n) return;
-  if (i < n) {
-    cand.pos_conf[i] = aos[(size_t)i * 3];
-    cand.col_time[i] = aos[(size_t)i * 3 + 1];
-    cand.nrm_rad[i] = aos[(size_t)i * 3 + 2];
-  } else {
-    cand.col_time[i] = make_float4(0, 0, 0, 0);
-  }
-}
-}  // namespace
-extern "C" {
-
-int ef_op_clean_deform(const ef_cam* cam, const double* T16, int time, const uint32_t* index, const float* vc, const float* ct, const float* nr,
-                       float confThreshold, int timeDelta, float maxDepth, const float* surfels, uint32_t count, const float* newUnstable,
-                       uint32_t newCount, const float* graph, int nodes, const float* depth, int isFern, float* surfels_out,
-                       uint32_t* outCount, void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  OpMap m;
-  const uint32_t cap = count + newCount;
-  efm::SurfelSoA soa = m.soa(count), out = m.soa(cap);
-  efm::aos_to_soa(surfels, count, soa, s);
-  float h[32];
-  pose_mats(T16, h, h + 16);
-  float* mats = m.alloc<float>(32);
-  (void)hipMemcpyAsync(mats, h, sizeof(h), hipMemcpyHostToDevice, s);
-  unsigned* cnt = m.alloc<unsigned>(1);
-  (void)hipMemcpyAsync(cnt, &count, sizeof(unsigned), hipMemcpyHostToDevice, s);
-  efm::Candidates cand;
-  cand.n = (int)(newCount ? newCount : 1);
-  cand.pos_conf = m.alloc<float4>(cand.n);
-  cand.col_time = m.alloc<float4>(cand.n);
-  cand.nrm_rad = m.alloc<float4>(cand.n);
-  cand.best = m.alloc<uint32_t>(cand.n);
-  hipLaunchKernelGGL(k_aos_to_cand, dim3((cand.n + 255) / 256), dim3(256), 0, s, (const float4*)newUnstable, newCount, cand);
-  uint32_t* winner = m.alloc<uint32_t>(count, 0xFF);
-  efm::CompactScratch cs;
-  cs.max_chunks = (int)((cap + 1) / efm::CLEAN_ROW + 8);
-  cs.flags = m.alloc<uint8_t>((size_t)cap + 1);
-  cs.chunk_count = m.alloc<uint32_t>(cs.max_chunks);
-  cs.chunk_offset = m.alloc<uint32_t>(cs.max_chunks);
-  cs.totals = m.alloc<uint32_t>(8);
-  efm::IndexMaps im{(uint32_t*)index, (float4*)vc, (float4*)ct, (float4*)nr};
-  unsigned* cnt_out = m.alloc<unsigned>(1);
-  const efm::Deformation def{graph, nodes, depth, isFern, maxDepth};
-  efm::clean(to_cam(cam), mats, time, im, confThreshold, timeDelta, soa, cnt, cand, winner, out, cnt_out, cap, cs, nullptr, s,
-             nodes > 0 ? &def : nullptr);
-  unsigned hn = 0;
-  (void)hipMemcpyAsync(&hn, cnt_out, sizeof(hn), hipMemcpyDeviceToHost, s);
-  OP_SYNC(s);
-  efm::soa_to_aos(out, hn, surfels_out, s);
-  OP_SYNC(s);
-  *outCount = hn;
-  return EF_OK;
-}
-int ef_op_clean(const ef_cam* cam, const double* T16, int time, const uint32_t* index, const float* vc, const float* ct, const float* nr,
-                float confThreshold, int timeDelta, float maxDepth, const float* surfels, uint32_t count, const float* newUnstable,
-                uint32_t newCount, float* surfels_out, uint32_t* outCount, void* s_) {
-  return ef_op_clean_deform(cam, T16, time, index, vc, ct, nr, confThreshold, timeDelta, maxDepth, surfels, count, newUnstable, newCount,
-                            nullptr, 0, nullptr, 0, surfels_out, outCount, s_);
-}
-
 }  // extern "C"
 
-// ================================================================================================
-// GlobalModel::renderPointCloud without OpenGL (include/ef_hip.h; kernels in ef_render.inc)
-// ================================================================================================
-namespace {
-// the parameters are checked before the context: with a NULL context the message goes where ef_last_error(NULL) finds it
-int render_check(ef_ctx* c, const ef_render_params* p, const char* fn) {
-  std::string& err = c ? c->err : g_create_error;
-  const char* why = nullptr;
-  if (!p) why = "null params";
-  else if (p->width < 1 || p->width > 4096 || p->height < 1 || p->height > 4096) why = "width and height must lie in 1 .. 4096";
-  else if (p->color_type < 0 || p->color_type > 3) why = "color_type must be 0 .. 3";
-  else if (!std::isfinite(p->fx) || !std::isfinite(p->fy) || !std::isfinite(p->cx) || !std::isfinite(p->cy) || p->fx == 0.f || p->fy == 0.f)
-    why = "intrinsics must be finite with non-zero focal lengths";
-  else if (!c) why = "null context";
-  if (!why) return EF_OK;
-  err = std::string(fn) + ": " + why;
-  return EF_EINVAL;
-}
-// the render's z-buffer: grown to P keys, 0xFF bytes (ZBUF_EMPTY) once; every resolve leaves it so
-int render_zbuf(ef_ctx* c, size_t P) {
-  if (c->render_zbuf_n >= P) return EF_OK;
-  EF_HIP(c, hipStreamSynchronize(c->stream));   // (a render still queued may use the old one)
-  if (c->render_zbuf) { (void)hipFree(c->render_zbuf); c->render_zbuf = nullptr; c->render_zbuf_n = 0; }
-  hipError_t e = hipMalloc((void**)&c->render_zbuf, P * sizeof(unsigned long long));
-  if (e != hipSuccess) { c->render_zbuf = nullptr; c->err = std::string("hipMalloc (render z-buffer): ") + hipGetErrorString(e); return EF_ENOMEM; }
-  c->render_zbuf_n = P;
-  EF_HIP(c, hipMemsetAsync(c->render_zbuf, 0xFF, P * sizeof(unsigned long long), c->stream));
-  return EF_OK;
-}
-int render_enqueue(ef_ctx* c, const ef_render_params* p, const efm::RenderOut& out) {
-  {
-    // never inside a capture: a render recorded into a graph would be replayed with every frame
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    EF_HIP(c, hipStreamIsCapturing(c->stream, &cs));
-    if (cs != hipStreamCaptureStatusNone) { c->err = "ef_render_model: the context's stream is being captured"; return EF_ESTATE; }
-  }
-  const size_t P = (size_t)p->width * p->height;
-  const int r = render_zbuf(c, P);
-  if (r != EF_OK) return r;
-  efm::RenderArgs a{};
-  a.cam = efm::Cam{p->width, p->height, p->fx, p->fy, p->cx, p->cy};
-  float pose_f[16];
-  pose_mats(p->T_wc, a.Tcw, pose_f);
-  a.maxDepth = p->max_depth;
-  a.threshold = p->threshold;
-  a.drawUnstable = p->draw_unstable != 0;
-  a.colorType = p->color_type;
-  a.drawWindow = p->draw_window != 0;
-  a.time = p->time;
-  a.timeDelta = p->time_delta;
-  efm::render_model(a, c->maps[c->cur], &c->st->map_counts[c->cur], c->render_zbuf, out, c->stream);
-  EF_HIP(c, hipGetLastError());
-  return EF_OK;
-}
-}  // namespace
-extern "C" {
-
-int ef_default_render_params(ef_ctx* c, ef_render_params* p) {
-  if (!c) return EF_EINVAL;
-  if (!p) { c->err = "ef_default_render_params: null params"; return EF_EINVAL; }
-  memset(p, 0, sizeof(*p));
-  const int r = ef_get_pose(c, p->T_wc);
-  if (r != EF_OK) return r;
-  p->width = c->cam.cols; p->height = c->cam.rows;
-  p->fx = c->cam.fx; p->fy = c->cam.fy; p->cx = c->cam.cx; p->cy = c->cam.cy;
-  p->max_depth = 1000.0f;   // the GUI's far plane
-  p->threshold = c->cfg.confidence;
-  p->time = c->tick;
-  p->time_delta = c->cfg.time_delta;
-  return EF_OK;
-}
-int ef_render_model_dev(ef_ctx* c, const ef_render_params* p, uint8_t* rgba, float* depth, float* vertex, float* normal, uint32_t* index) {
-  const int r = render_check(c, p, "ef_render_model_dev");
-  if (r != EF_OK) return r;
-  DeviceGuard dg_(c);
-  return render_enqueue(c, p, efm::RenderOut{(uchar4*)rgba, depth, (float4*)vertex, (float4*)normal, index});
-}
-int ef_render_model(ef_ctx* c, const ef_render_params* p, uint8_t* rgba, float* depth, float* vertex, float* normal, uint32_t* index) {
-  int r = render_check(c, p, "ef_render_model");
-  if (r != EF_OK) return r;
-  DeviceGuard dg_(c);
-  const size_t P = (size_t)p->width * p->height;
-  // the requested outputs land in one device area (grown on demand), then are copied out
-  const size_t sz[5] = {rgba ? P * 4 : 0, depth ? P * 4 : 0, vertex ? P * 16 : 0, normal ? P * 16 : 0, index ? P * 4 : 0};
-  const size_t bytes = sz[0] + sz[1] + sz[2] + sz[3] + sz[4];
-  if (bytes > c->render_out_bytes) {
-    EF_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->render_out) { (void)hipFree(c->render_out); c->render_out = nullptr; c->render_out_bytes = 0; }
-    hipError_t e = hipMalloc((void**)&c->render_out, bytes);
-    if (e != hipSuccess) { c->render_out = nullptr; c->err = std::string("hipMalloc (render outputs): ") + hipGetErrorString(e); return EF_ENOMEM; }
-    c->render_out_bytes = bytes;
-  }
-  void* host[5] = {rgba, depth, vertex, normal, index};
-  void* dev[5] = {};
-  size_t off = 0;
-  for (int i = 0; i < 5; ++i) {
-    if (sz[i]) dev[i] = c->render_out + off;
-    off += sz[i];
-  }
-  r = render_enqueue(c, p, efm::RenderOut{(uchar4*)dev[0], (float*)dev[1], (float4*)dev[2], (float4*)dev[3], (uint32_t*)dev[4]});
-  if (r != EF_OK) return r;
-  for (int i = 0; i < 5; ++i)
-    if (sz[i]) EF_HIP(c, hipMemcpyAsync(host[i], dev[i], sz[i], hipMemcpyDeviceToHost, c->stream));
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  return EF_OK;
-}
-
-}  // extern "C"
-
-// ================================================================================================
-// Stable surfel IDs and per-surfel label fusion (include/ef_hip.h; kernels in ef_labels.inc)
-// ================================================================================================
-namespace {
-int capture_check(ef_ctx* c, const char* fn) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  EF_HIP(c, hipStreamIsCapturing(c->stream, &cs));
-  if (cs != hipStreamCaptureStatusNone) { c->err = std::string(fn) + ": the context's stream is being captured"; return EF_ESTATE; }
-  return EF_OK;
-}
-// the lazy numbering every ID-consuming call starts with
-int ids_prepare(ef_ctx* c, const char* fn) {
-  if (c->ids_bad) {
-    c->err = std::string(fn) + ": the uploaded map's ID lane (float 5 of each surfel) is not a strictly increasing non-zero prefix followed by "
-             "a zero suffix";
-    return EF_ESTATE;
-  }
-  efm::ids_assign(c->maps[c->cur], &c->st->map_counts[c->cur], c->ids_state, c->stream);
-  EF_HIP(c, hipGetLastError());
-  return EF_OK;
-}
-int read_count(ef_ctx* c, uint32_t* n) {
-  EF_HIP(c, hipMemcpyAsync(n, &c->st->map_counts[c->cur], sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  return EF_OK;
-}
-// An upper bound of the map count without a device round trip: the count a label call left behind (once its event has completed) or an
-// upload set, plus one image of new surfels per frame since (the first frame seeds at most width x height, fusion appends fewer).
-size_t labels_count_bound(ef_ctx* c) {
-  if (c->label_ev_pending && hipEventQuery(c->label_ev) == hipSuccess) {
-    c->label_known = *c->label_count_h;
-    c->label_known_frames = c->label_ev_frames;
-    c->label_ev_pending = false;
-  }
-  const size_t P = (size_t)c->cam.cols * c->cam.rows;
-  const size_t b = c->label_known + (c->stamps.size() - c->label_known_frames) * P;
-  return b < c->capacity ? b : c->capacity;
-}
-void labels_free(ef_ctx* c) {
-  for (int k = 0; k < 2; ++k) {
-    if (c->label_tab[k]) (void)hipFree(c->label_tab[k]);
-    if (c->label_ids[k]) (void)hipFree(c->label_ids[k]);
-    c->label_tab[k] = nullptr;
-    c->label_ids[k] = nullptr;
-  }
-  c->label_rows = 0;
-  c->label_C = 0;
-}
-// table and ID lists for at least the map count; waits for the device only when the bound outgrows them
-int labels_reserve(ef_ctx* c) {
-  c->label_bound = labels_count_bound(c);
-  if (c->label_bound <= c->label_rows) return EF_OK;
-  uint32_t n = 0;
-  int r = read_count(c, &n);
-  if (r != EF_OK) return r;
-  unsigned np[2] = {0, 0};
-  EF_HIP(c, hipMemcpy(np, c->ids_state + 2, sizeof(np), hipMemcpyDeviceToHost));
-  c->label_known = n;
-  c->label_known_frames = c->stamps.size();
-  c->label_ev_pending = false;
-  c->label_bound = n;
-  if (n <= c->label_rows) return EF_OK;
-  const size_t P = (size_t)c->cam.cols * c->cam.rows, C = (size_t)c->label_C;
-  size_t rows = (size_t)n + std::max((size_t)n / 4, P);
-  if (rows > c->capacity) rows = c->capacity;
-  float* tab[2] = {};
-  uint32_t* ids[2] = {};
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-    e = hipMalloc((void**)&tab[k], rows * C * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void**)&ids[k], rows * sizeof(uint32_t));
-  }
-  if (e != hipSuccess) {
-    for (int k = 0; k < 2; ++k) { if (tab[k]) (void)hipFree(tab[k]); if (ids[k]) (void)hipFree(ids[k]); }
-    c->err = std::string("hipMalloc (label table): ") + hipGetErrorString(e);
-    return EF_ENOMEM;
-  }
-  const int w = c->label_cur;   // the live alignment moves over; the other half is rewritten by the next one
-  const size_t keep = std::min((size_t)np[w], c->label_rows);
-  if (keep) {
-    EF_HIP(c, hipMemcpyAsync(tab[w], c->label_tab[w], keep * C * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-    EF_HIP(c, hipMemcpyAsync(ids[w], c->label_ids[w], keep * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-    EF_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  const int C_keep = c->label_C;
-  labels_free(c);
-  c->label_C = C_keep;
-  for (int k = 0; k < 2; ++k) { c->label_tab[k] = tab[k]; c->label_ids[k] = ids[k]; }
-  c->label_rows = rows;
-  return EF_OK;
-}
-// what every label call starts with: IDs for the new rows, then the table re-aligned to the current rows
-int labels_begin(ef_ctx* c, const char* fn) {
-  int r = capture_check(c, fn);
-  if (r != EF_OK) return r;
-  if (!c->label_C) { c->err = std::string(fn) + ": labels are off (ef_enable_labels)"; return EF_ESTATE; }
-  r = ids_prepare(c, fn);
-  if (r != EF_OK) return r;
-  r = labels_reserve(c);
-  if (r != EF_OK) return r;
-  const int w = c->label_cur;
-  efm::LabelAlign a{c->maps[c->cur], &c->st->map_counts[c->cur], c->label_ids[w], c->label_tab[w], c->ids_state + 2 + w,
-                    c->label_ids[w ^ 1], c->label_tab[w ^ 1], c->ids_state + 2 + (w ^ 1), c->label_C, 1.0f / (float)c->label_C};
-  efm::labels_align(a, (unsigned)c->label_bound, c->stream);
-  EF_HIP(c, hipGetLastError());
-  c->label_cur ^= 1;
-  // the count this call saw, for the next call's bound
-  EF_HIP(c, hipMemcpyAsync(c->label_count_h, &c->st->map_counts[c->cur], sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-  EF_HIP(c, hipEventRecord(c->label_ev, c->stream));
-  c->label_ev_frames = c->stamps.size();
-  c->label_ev_pending = true;
-  return EF_OK;
-}
-int grow(ef_ctx* c, uint8_t** buf, size_t* have, size_t bytes, const char* what) {
-  if (bytes <= *have) return EF_OK;
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  if (*buf) { (void)hipFree(*buf); *buf = nullptr; *have = 0; }
-  hipError_t e = hipMalloc((void**)buf, bytes);
-  if (e != hipSuccess) { *buf = nullptr; c->err = std::string("hipMalloc (") + what + "): " + hipGetErrorString(e); return EF_ENOMEM; }
-  *have = bytes;
-  return EF_OK;
-}
-// the view's index image into label_index, exactly as ef_render_model draws it
-int labels_index(ef_ctx* c, const ef_render_params* p) {
-  const size_t P = (size_t)p->width * p->height;
-  size_t have = c->label_index_n * sizeof(uint32_t);
-  const int r = grow(c, (uint8_t**)&c->label_index, &have, P * sizeof(uint32_t), "label index image");
-  if (r != EF_OK) return r;
-  c->label_index_n = have / sizeof(uint32_t);
-  return render_enqueue(c, p, efm::RenderOut{nullptr, nullptr, nullptr, nullptr, c->label_index});
-}
-// refusals before any GPU work; the view is checked with the render's rules
-int labels_check(ef_ctx* c, const ef_render_params* view, bool view_required, const void* probs, bool probs_required, const char* fn) {
-  std::string& err = c ? c->err : g_create_error;
-  if (probs_required && !probs) { err = std::string(fn) + ": null probability image"; return EF_EINVAL; }
-  if (view || view_required) return render_check(c, view, fn);
-  if (!c) { err = std::string(fn) + ": null context"; return EF_EINVAL; }
-  return EF_OK;
-}
-int labels_view(ef_ctx* c, const ef_render_params* view, ef_render_params* q) {
-  if (view) { *q = *view; return EF_OK; }
-  const int r = ef_default_render_params(c, q);
-  q->draw_unstable = 1;
-  return r;
-}
-int fuse_enqueue(ef_ctx* c, const ef_render_params* q, const float* probs_dev) {
-  int r = labels_index(c, q);
-  if (r != EF_OK) return r;
-  efm::LabelFuse f{};
-  f.map = c->maps[c->cur];
-  f.count_dev = &c->st->map_counts[c->cur];
-  f.cam = efm::Cam{q->width, q->height, q->fx, q->fy, q->cx, q->cy};
-  float pose_f[16];
-  pose_mats(q->T_wc, f.Tcw, pose_f);
-  f.index = c->label_index;
-  f.probs = probs_dev;
-  f.tab = c->label_tab[c->label_cur];
-  f.C = c->label_C;
-  efm::labels_fuse(f, (unsigned)c->label_bound, c->stream);
-  EF_HIP(c, hipGetLastError());
-  return EF_OK;
-}
-int render_labels_enqueue(ef_ctx* c, const ef_render_params* p, int32_t* label, float* prob) {
-  int r = labels_index(c, p);
-  if (r != EF_OK) return r;
-  efm::labels_gather(c->label_index, p->width * p->height, c->label_tab[c->label_cur], c->label_C, label, prob, c->stream);
-  EF_HIP(c, hipGetLastError());
-  return EF_OK;
-}
-}  // namespace
-extern "C" {
-
-int ef_set_surfel_ids(ef_ctx* c, int on) {
-  if (!c) { g_create_error = "ef_set_surfel_ids: null context"; return EF_EINVAL; }
-  DeviceGuard dg_(c);
-  int r = capture_check(c, "ef_set_surfel_ids");
-  if (r != EF_OK) return r;
-  if ((on != 0) == c->ids_on) return EF_OK;
-  if (on && !c->ids_state) {
-    const unsigned init[4] = {1u, 0u, 0u, 0u};
-    EF_HIP(c, hipMalloc((void**)&c->ids_state, sizeof(init)));
-    EF_HIP(c, hipMemcpy(c->ids_state, init, sizeof(init), hipMemcpyHostToDevice));
-    EF_HIP(c, hipHostMalloc((void**)&c->label_count_h, sizeof(unsigned)));
-    EF_HIP(c, hipEventCreateWithFlags(&c->label_ev, hipEventDisableTiming));
-  }
-  if (!on) labels_free(c);
-  // on: the lane is numbered from the counter by the next ID-consuming call (1 .. N the first time); off: as if IDs had never been on
-  efm::ids_zero(c->maps[c->cur], &c->st->map_counts[c->cur], c->capacity, c->stream);
-  EF_HIP(c, hipGetLastError());
-  c->ids_on = on != 0;
-  c->ids_bad = false;
-  return EF_OK;
-}
-
-int ef_get_surfel_ids(ef_ctx* c, uint32_t* ids, uint32_t max_ids, uint32_t* count) {
-  if (!c || !count) { (c ? c->err : g_create_error) = c ? "ef_get_surfel_ids: null count" : "ef_get_surfel_ids: null context"; return EF_EINVAL; }
-  DeviceGuard dg_(c);
-  int r = capture_check(c, "ef_get_surfel_ids");
-  if (r != EF_OK) return r;
-  if (!c->ids_on) { c->err = "ef_get_surfel_ids: surfel IDs are off (ef_set_surfel_ids)"; return EF_ESTATE; }
-  r = ids_prepare(c, "ef_get_surfel_ids");
-  if (r != EF_OK) return r;
-  uint32_t n = 0;
-  r = read_count(c, &n);
-  if (r != EF_OK) return r;
-  if (n > max_ids) n = max_ids;
-  *count = n;
-  if (!ids || !n) return EF_OK;
-  uint32_t* tmp = nullptr;
-  EF_HIP(c, hipMalloc((void**)&tmp, (size_t)n * sizeof(uint32_t)));
-  efm::ids_gather(c->maps[c->cur], n, tmp, c->stream);
-  hipError_t e = hipMemcpyAsync(ids, tmp, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(tmp);
-  EF_HIP(c, e);
-  return EF_OK;
-}
-
-int ef_enable_labels(ef_ctx* c, int num_classes) {
-  if (num_classes < 0 || num_classes > 256) {
-    (c ? c->err : g_create_error) = "ef_enable_labels: num_classes must lie in 0 .. 256";
-    return EF_EINVAL;
-  }
-  if (!c) { g_create_error = "ef_enable_labels: null context"; return EF_EINVAL; }
-  DeviceGuard dg_(c);
-  int r = capture_check(c, "ef_enable_labels");
-  if (r != EF_OK) return r;
-  labels_free(c);
-  if (!num_classes) return EF_OK;
-  if (!c->ids_on) {
-    r = ef_set_surfel_ids(c, 1);
-    if (r != EF_OK) return r;
-  }
-  EF_HIP(c, hipMemsetAsync(c->ids_state + 2, 0, 2 * sizeof(unsigned), c->stream));   // no previous alignment: every row starts at the prior
-  c->label_C = num_classes;
-  c->label_cur = 0;
-  c->label_ev_pending = false;
-  c->label_known = c->capacity;   // unknown: the first label call reads it
-  c->label_known_frames = c->stamps.size();
-  return EF_OK;
-}
-
-int ef_set_labels(ef_ctx* c, const float* probs, uint32_t count) {
-  int r = labels_check(c, nullptr, false, probs, count != 0, "ef_set_labels");
-  if (r != EF_OK) return r;
-  DeviceGuard dg_(c);
-  r = labels_begin(c, "ef_set_labels");
-  if (r != EF_OK) return r;
-  uint32_t n = 0;
-  r = read_count(c, &n);
-  if (r != EF_OK) return r;
-  if (count != n) { c->err = "ef_set_labels: count must equal the map count (" + std::to_string(n) + ")"; return EF_EINVAL; }
-  if (n) {
-    EF_HIP(c, hipMemcpyAsync(c->label_tab[c->label_cur], probs, (size_t)n * c->label_C * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    EF_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  return EF_OK;
-}
-
-int ef_get_labels(ef_ctx* c, uint32_t* ids, float* probs, uint32_t max_rows, uint32_t* count) {
-  if (!c || !count) { (c ? c->err : g_create_error) = c ? "ef_get_labels: null count" : "ef_get_labels: null context"; return EF_EINVAL; }
-  DeviceGuard dg_(c);
-  int r = labels_begin(c, "ef_get_labels");
-  if (r != EF_OK) return r;
-  uint32_t n = 0;
-  r = read_count(c, &n);
-  if (r != EF_OK) return r;
-  if (n > max_rows) n = max_rows;
-  *count = n;
-  if (!n) return EF_OK;
-  if (ids) EF_HIP(c, hipMemcpyAsync(ids, c->label_ids[c->label_cur], (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  if (probs)
-    EF_HIP(c, hipMemcpyAsync(probs, c->label_tab[c->label_cur], (size_t)n * c->label_C * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  return EF_OK;
-}
-
-int ef_fuse_labels_dev(ef_ctx* c, const ef_render_params* view, const float* probs_dev) {
-  int r = labels_check(c, view, false, probs_dev, true, "ef_fuse_labels_dev");
-  if (r != EF_OK) return r;
-  DeviceGuard dg_(c);
-  r = labels_begin(c, "ef_fuse_labels_dev");
-  if (r != EF_OK) return r;
-  ef_render_params q;
-  r = labels_view(c, view, &q);
-  if (r != EF_OK) return r;
-  return fuse_enqueue(c, &q, probs_dev);
-}
-
-int ef_fuse_labels(ef_ctx* c, const ef_render_params* view, const float* probs_chw) {
-  int r = labels_check(c, view, false, probs_chw, true, "ef_fuse_labels");
-  if (r != EF_OK) return r;
-  DeviceGuard dg_(c);
-  r = labels_begin(c, "ef_fuse_labels");
-  if (r != EF_OK) return r;
-  ef_render_params q;
-  r = labels_view(c, view, &q);
-  if (r != EF_OK) return r;
-  const size_t bytes = (size_t)q.width * q.height * c->label_C * sizeof(float);
-  r = grow(c, &c->label_stage, &c->label_stage_bytes, bytes, "label staging");
-  if (r != EF_OK) return r;
-  EF_HIP(c, hipMemcpyAsync(c->label_stage, probs_chw, bytes, hipMemcpyHostToDevice, c->stream));
-  r = fuse_enqueue(c, &q, (const float*)c->label_stage);
-  if (r != EF_OK) return r;
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  return EF_OK;
-}
-
-int ef_render_labels_dev(ef_ctx* c, const ef_render_params* p, int32_t* label_dev, float* prob_dev) {
-  int r = labels_check(c, p, true, nullptr, false, "ef_render_labels_dev");
-  if (r != EF_OK) return r;
-  DeviceGuard dg_(c);
-  r = labels_begin(c, "ef_render_labels_dev");
-  if (r != EF_OK) return r;
-  return render_labels_enqueue(c, p, label_dev, prob_dev);
-}
-
-int ef_render_labels(ef_ctx* c, const ef_render_params* p, int32_t* label, float* prob) {
-  int r = labels_check(c, p, true, nullptr, false, "ef_render_labels");
-  if (r != EF_OK) return r;
-  DeviceGuard dg_(c);
-  r = labels_begin(c, "ef_render_labels");
-  if (r != EF_OK) return r;
-  const size_t P = (size_t)p->width * p->height;
-  r = grow(c, &c->label_stage, &c->label_stage_bytes, P * 8, "label staging");
-  if (r != EF_OK) return r;
-  int32_t* dl = label ? (int32_t*)c->label_stage : nullptr;
-  float* dp = prob ? (float*)(c->label_stage + P * 4) : nullptr;
-  r = render_labels_enqueue(c, p, dl, dp);
-  if (r != EF_OK) return r;
-  if (label) EF_HIP(c, hipMemcpyAsync(label, dl, P * 4, hipMemcpyDeviceToHost, c->stream));
-  if (prob) EF_HIP(c, hipMemcpyAsync(prob, dp, P * 4, hipMemcpyDeviceToHost, c->stream));
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  return EF_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// ef_map_upload with IDs on: the uploaded lane is kept when its shape is valid (the counter then continues above its largest ID, ids_assign);
-// any other shape is remembered and refused by the next ID-consuming call.  Labels restart from the prior.
-int ids_uploaded(ef_ctx* c, uint32_t count) {
-  EF_HIP(c, hipMemsetAsync(c->ids_state + 1, 0, sizeof(unsigned), c->stream));
-  efm::ids_check(c->maps[c->cur], count, c->ids_state + 1, c->stream);
-  EF_HIP(c, hipGetLastError());
-  unsigned flag = 0;
-  EF_HIP(c, hipMemcpyAsync(&flag, c->ids_state + 1, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  c->ids_bad = flag != 0;
-  if (c->label_C) {
-    EF_HIP(c, hipMemsetAsync(c->ids_state + 2 + c->label_cur, 0, sizeof(unsigned), c->stream));
-    c->label_known = count;
-    c->label_known_frames = c->stamps.size();
-    c->label_ev_pending = false;
-  }
-  return EF_OK;
-}
-}  // namespace
-
-// ================================================================================================
-// Spatial index and nearest-surfel / kNN queries (include/ef_hip.h; kernels in ef_query.inc)
-// ================================================================================================
-namespace {
-struct QueryCall {
-  const char* fn;
-  const float* points;
-  uint32_t n;
-  int k;
-  float max_dist, min_conf;
-  uint32_t* row;
-  uint32_t* id;
-  float* dist2;
-  float* plane;
-  uint32_t* count;
-};
-// refusals before any GPU work
-int query_check(ef_ctx* c, const QueryCall& q) {
-  std::string& err = c ? c->err : g_create_error;
-  const std::string fn = q.fn;
-  if (q.k < 1 || q.k > 16) { err = fn + ": k must lie in 1 .. 16"; return EF_EINVAL; }
-  if (!(q.max_dist > 0.f) || !std::isfinite(q.max_dist)) { err = fn + ": max_dist must be finite and positive"; return EF_EINVAL; }
-  if (std::isnan(q.min_conf)) { err = fn + ": min_conf is NaN"; return EF_EINVAL; }
-  if (q.n && !q.points) { err = fn + ": null points"; return EF_EINVAL; }
-  if (!q.row) { err = fn + ": null row output"; return EF_EINVAL; }
-  if (!c) { err = fn + ": null context"; return EF_EINVAL; }
-  if (!(q.max_dist / c->query_cell <= (float)EF_QUERY_MAX_RATIO)) {
-    err = fn + ": max_dist / cell must not exceed " + std::to_string(EF_QUERY_MAX_RATIO) + " (ef_set_query_cell)";
-    return EF_EINVAL;
-  }
-  return EF_OK;
-}
-// the index for the current map and cell size: reused while neither has changed, else rebuilt (waits for the device once: the count sizes it)
-int query_index(ef_ctx* c) {
-  if (c->query_gen == c->map_gen && c->query_built_cell == c->query_cell) return EF_OK;
-  uint32_t n = 0;
-  int r = read_count(c, &n);
-  if (r != EF_OK) return r;
-  const uint32_t nb = efm::query_buckets(n);
-  const size_t words = (size_t)nb + 2 * ((size_t)nb / 1024 + 1);
-  if (words > c->query_cells_cap) {
-    if (c->query_cells) { (void)hipFree(c->query_cells); c->query_cells = nullptr; c->query_cells_cap = 0; }
-    EF_HIP(c, hipMalloc((void**)&c->query_cells, words * sizeof(uint32_t)));
-    c->query_cells_cap = words;
-  }
-  if (n > c->query_cap) {
-    if (c->query_sorted) { (void)hipFree(c->query_sorted); c->query_sorted = nullptr; }
-    if (c->query_rows) { (void)hipFree(c->query_rows); c->query_rows = nullptr; }
-    c->query_cap = 0;
-    const size_t cap = std::min((size_t)c->capacity, (size_t)n + (size_t)n / 4 + 1024);
-    EF_HIP(c, hipMalloc((void**)&c->query_sorted, cap * sizeof(float4)));
-    EF_HIP(c, hipMalloc((void**)&c->query_rows, cap * sizeof(uint32_t)));
-    c->query_cap = cap;
-  }
-  c->query_gen = 0;   // nothing valid until the build below is enqueued
-  EF_HIP(c, hipMemsetAsync(c->query_cells, 0, (size_t)nb * sizeof(uint32_t), c->stream));
-  efm::query_build(c->maps[c->cur], n, 1.0f / c->query_cell, nb, c->query_cells, c->query_cells + nb, c->query_sorted, c->query_rows, c->stream);
-  EF_HIP(c, hipGetLastError());
-  c->query_nb = nb;
-  c->query_n = n;
-  c->query_built_cell = c->query_cell;
-  c->query_gen = c->map_gen;
-  return EF_OK;
-}
-// device pointers in q; enqueues only (but for a rebuild)
-int query_enqueue(ef_ctx* c, const QueryCall& q) {
-  int r = capture_check(c, q.fn);
-  if (r != EF_OK) return r;
-  if (q.id) {
-    if (!c->ids_on) { c->err = std::string(q.fn) + ": surfel IDs are off (ef_set_surfel_ids)"; return EF_ESTATE; }
-    r = ids_prepare(c, q.fn);
-    if (r != EF_OK) return r;
-  }
-  if (!q.n) return EF_OK;
-  r = query_index(c);
-  if (r != EF_OK) return r;
-  efm::QueryArgs a{};
-  a.map = c->maps[c->cur];
-  a.sorted = c->query_sorted;
-  a.rows = c->query_rows;
-  a.cells = c->query_cells;
-  a.mask = c->query_nb - 1;
-  a.n_sorted = c->query_n;
-  a.inv_cell = 1.0f / c->query_built_cell;
-  a.points = q.points;
-  a.n = q.n;
-  a.k = q.k;
-  a.max_dist = q.max_dist;
-  a.r2 = q.max_dist * q.max_dist;
-  a.min_conf = q.min_conf;
-  a.row = q.row;
-  a.dist2 = q.dist2;
-  a.id = q.id;
-  a.plane = q.plane;
-  a.count = q.count;
-  efm::query_run(a, q.k, c->query_lanes, c->stream);
-  EF_HIP(c, hipGetLastError());
-  return EF_OK;
-}
-// host pointers in q: staged through query_stage, synchronised
-int query_host(ef_ctx* c, const QueryCall& q) {
-  int r = capture_check(c, q.fn);
-  if (r != EF_OK) return r;
-  const size_t n = q.n, nk = n * (size_t)q.k;
-  const size_t o_pts = 0, o_row = o_pts + n * 12, o_d2 = o_row + nk * 4, o_id = o_d2 + nk * 4, o_pl = o_id + n * 4, o_cnt = o_pl + n * 4;
-  r = grow(c, &c->query_stage, &c->query_stage_bytes, o_cnt + n * 4 + 16, "query staging");
-  if (r != EF_OK) return r;
-  uint8_t* st = c->query_stage;
-  QueryCall d = q;
-  d.points = (const float*)(st + o_pts);
-  d.row = (uint32_t*)(st + o_row);
-  d.dist2 = q.dist2 ? (float*)(st + o_d2) : nullptr;
-  d.id = q.id ? (uint32_t*)(st + o_id) : nullptr;
-  d.plane = q.plane ? (float*)(st + o_pl) : nullptr;
-  d.count = q.count ? (uint32_t*)(st + o_cnt) : nullptr;
-  if (n) EF_HIP(c, hipMemcpyAsync(st + o_pts, q.points, n * 12, hipMemcpyHostToDevice, c->stream));
-  r = query_enqueue(c, d);
-  if (r != EF_OK) return r;
-  if (n) {
-    EF_HIP(c, hipMemcpyAsync(q.row, d.row, nk * 4, hipMemcpyDeviceToHost, c->stream));
-    if (q.dist2) EF_HIP(c, hipMemcpyAsync(q.dist2, d.dist2, nk * 4, hipMemcpyDeviceToHost, c->stream));
-    if (q.id) EF_HIP(c, hipMemcpyAsync(q.id, d.id, n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (q.plane) EF_HIP(c, hipMemcpyAsync(q.plane, d.plane, n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (q.count) EF_HIP(c, hipMemcpyAsync(q.count, d.count, n * 4, hipMemcpyDeviceToHost, c->stream));
-  }
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  return EF_OK;
-}
-}  // namespace
-extern "C" {
-
-int ef_set_query_cell(ef_ctx* c, float cell_m) {
-  if (!(cell_m > 0.f) || !std::isfinite(cell_m) || !std::isfinite(1.0f / cell_m)) {
-    (c ? c->err : g_create_error) = "ef_set_query_cell: cell_m must be finite and positive";
-    return EF_EINVAL;
-  }
-  if (!c) { g_create_error = "ef_set_query_cell: null context"; return EF_EINVAL; }
-  c->query_cell = cell_m;
-  return EF_OK;
-}
-int ef_debug_query_lanes(ef_ctx* c, int lanes) {
-  if (!c || (lanes != 0 && lanes != 1 && lanes != 8 && lanes != 16 && lanes != 64)) return EF_EINVAL;
-  c->query_lanes = lanes;
-  return EF_OK;
-}
-int ef_query_nearest_dev(ef_ctx* c, const float* points3, uint32_t n, float max_dist, float min_conf, uint32_t* row, uint32_t* id, float* dist2,
-                         float* plane) {
-  const QueryCall q{"ef_query_nearest_dev", points3, n, 1, max_dist, min_conf, row, id, dist2, plane, nullptr};
-  const int r = query_check(c, q);
-  if (r != EF_OK) return r;
-  DeviceGuard dg_(c);
-  return query_enqueue(c, q);
-}
-int ef_query_nearest(ef_ctx* c, const float* points3, uint32_t n, float max_dist, float min_conf, uint32_t* row, uint32_t* id, float* dist2,
-                     float* plane) {
-  const QueryCall q{"ef_query_nearest", points3, n, 1, max_dist, min_conf, row, id, dist2, plane, nullptr};
-  const int r = query_check(c, q);
-  if (r != EF_OK) return r;
-  DeviceGuard dg_(c);
-  return query_host(c, q);
-}
-int ef_query_knn_dev(ef_ctx* c, const float* points3, uint32_t n, int k, float max_dist, float min_conf, uint32_t* rows, float* dist2,
-                     uint32_t* count) {
-  const QueryCall q{"ef_query_knn_dev", points3, n, k, max_dist, min_conf, rows, nullptr, dist2, nullptr, count};
-  const int r = query_check(c, q);
-  if (r != EF_OK) return r;
-  DeviceGuard dg_(c);
-  return query_enqueue(c, q);
-}
-int ef_query_knn(ef_ctx* c, const float* points3, uint32_t n, int k, float max_dist, float min_conf, uint32_t* rows, float* dist2,
-                 uint32_t* count) {
-  const QueryCall q{"ef_query_knn", points3, n, k, max_dist, min_conf, rows, nullptr, dist2, nullptr, count};
-  const int r = query_check(c, q);
-  if (r != EF_OK) return r;
-  DeviceGuard dg_(c);
-  return query_host(c, q);
-}
-
-}  // extern "C"
-
-// ================================================================================================
-// Rigid registration of a point set against the map (include/ef_hip.h; kernels in ef_register.inc)
-// ================================================================================================
-namespace {
-struct RegisterCall {
-  const char* fn;
-  const float* points;
-  const float* normals;
-  uint32_t n;
-  const ef_register_params* p;
-  const double* T;   // null = identity
-  uint32_t* row;
-  float* plane;
-};
-const double REG_IDENTITY[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-bool finite16(const double* T) {
-  for (int i = 0; i < 16; ++i)
-    if (!std::isfinite(T[i])) return false;
-  return true;
-}
-// refusals before any GPU work
-int register_check(ef_ctx* c, const RegisterCall& q, const void* out, const char* out_name) {
-  std::string& err = c ? c->err : g_create_error;
-  const std::string fn = q.fn;
-  if (!q.p) { err = fn + ": null params"; return EF_EINVAL; }
-  if (!out) { err = fn + ": null " + out_name; return EF_EINVAL; }
-  static uint32_t row_stand_in;
-  const QueryCall qc{q.fn, q.points, q.n, 1, q.p->max_dist, q.p->min_conf, &row_stand_in, nullptr, nullptr, nullptr, nullptr};
-  if (std::isnan(q.p->min_normal_cos)) { err = fn + ": min_normal_cos is NaN"; return EF_EINVAL; }
-  if (q.p->max_iterations < 1 || q.p->max_iterations > EF_REGISTER_MAX_ITERATIONS) {
-    err = fn + ": max_iterations must lie in 1 .. " + std::to_string(EF_REGISTER_MAX_ITERATIONS);
-    return EF_EINVAL;
-  }
-  if (q.p->min_pairs < 6) { err = fn + ": min_pairs must be at least 6"; return EF_EINVAL; }
-  if (!(q.p->stop_translation >= 0.0) || !std::isfinite(q.p->stop_translation) || !(q.p->stop_rotation >= 0.0) ||
-      !std::isfinite(q.p->stop_rotation)) {
-    err = fn + ": the stop bounds must be finite and not negative";
-    return EF_EINVAL;
-  }
-  if (q.T && !finite16(q.T)) { err = fn + ": T has a non-finite entry"; return EF_EINVAL; }
-  return query_check(c, qc);
-}
-double register_rms(const ef_register_sums& s) { return s.pairs ? std::sqrt(s.e / (double)s.pairs) : 0.0; }
-// one step with DEVICE pointers in q; waits for the 29 sums
-int register_step_run(ef_ctx* c, const RegisterCall& q, const double* T, ef_register_sums* out) {
-  memset(out, 0, sizeof(*out));
-  out->points = q.n;
-  if (!q.n) return EF_OK;
-  int r = query_index(c);
-  if (r != EF_OK) return r;
-  const size_t slab_bytes = (size_t)efm::REGISTER_MAX_BLOCKS * efm::REGISTER_SLOTS * sizeof(double);
-  r = grow(c, &c->reg_slabs, &c->reg_slabs_bytes, slab_bytes + efm::REGISTER_SLOTS * sizeof(double), "registration slabs");
-  if (r != EF_OK) return r;
-  if (!c->reg_sums_h) EF_HIP(c, hipHostMalloc((void**)&c->reg_sums_h, efm::REGISTER_SLOTS * sizeof(double)));
-  efm::RegisterArgs a{};
-  a.q.map = c->maps[c->cur];
-  a.q.sorted = c->query_sorted;
-  a.q.rows = c->query_rows;
-  a.q.cells = c->query_cells;
-  a.q.mask = c->query_nb - 1;
-  a.q.n_sorted = c->query_n;
-  a.q.inv_cell = 1.0f / c->query_built_cell;
-  a.q.points = q.points;
-  a.q.n = q.n;
-  a.q.k = 1;
-  a.q.max_dist = q.p->max_dist;
-  a.q.r2 = q.p->max_dist * q.p->max_dist;
-  a.q.min_conf = q.p->min_conf;
-  a.q.row = q.row;
-  a.q.plane = q.plane;
-  a.normals = q.normals;
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) a.R[i * 3 + j] = (float)T[i * 4 + j];
-    a.t[i] = (float)T[i * 4 + 3];
-  }
-  a.min_normal_cos = q.p->min_normal_cos;
-  a.gate = q.normals && q.p->min_normal_cos > -1.0f;
-  a.slabs = (double*)c->reg_slabs;
-  a.sums = (double*)(c->reg_slabs + slab_bytes);
-  efm::register_step(a, c->stream);
-  EF_HIP(c, hipGetLastError());
-  EF_HIP(c, hipMemcpyAsync(c->reg_sums_h, a.sums, efm::REGISTER_SLOTS * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  const double* v = c->reg_sums_h;
-  int k = 0;
-  for (int i = 0; i < 6; ++i)
-    for (int j = i; j < 6; ++j) out->A[i * 6 + j] = out->A[j * 6 + i] = v[k++];
-  for (int i = 0; i < 6; ++i) out->b[i] = v[21 + i];
-  out->e = v[27];
-  out->pairs = (uint32_t)v[28];
-  return EF_OK;
-}
-// the loop of the header comment; DEVICE pointers in q
-int register_loop(ef_ctx* c, const RegisterCall& q, double* T_out, ef_register_result* res) {
-  double T[16];
-  memcpy(T, q.T ? q.T : REG_IDENTITY, sizeof(T));
-  memset(res, 0, sizeof(*res));
-  int closing = -1;
-  for (bool first = true;; first = false) {
-    ef_register_sums s;
-    const int r = register_step_run(c, q, T, &s);
-    if (r != EF_OK) return r;
-    if (first) res->rms_first = register_rms(s);
-    res->rms_last = register_rms(s);
-    res->pairs = s.pairs;
-    memcpy(res->A, s.A, sizeof(res->A));
-    if (closing >= 0) { res->status = closing; break; }
-    if (s.pairs < (uint32_t)q.p->min_pairs) { res->status = EF_REG_TOO_FEW_PAIRS; break; }
-    double Tn[16], xi[6];
-    const int u = ef_register_update(&s, T, Tn, xi);
-    if (u == EF_REG_DEGENERATE) { res->status = EF_REG_DEGENERATE; break; }
-    if (u != EF_OK) { c->err = std::string(q.fn) + ": the update refused its input"; return u; }
-    memcpy(T, Tn, sizeof(T));
-    ++res->iterations;
-    const double dt = std::sqrt(xi[0] * xi[0] + xi[1] * xi[1] + xi[2] * xi[2]), dw = std::sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]);
-    if (dt < q.p->stop_translation && dw < q.p->stop_rotation) closing = EF_REG_CONVERGED;
-    else if (res->iterations >= q.p->max_iterations) closing = EF_REG_MAX_ITERATIONS;
-  }
-  memcpy(T_out, T, sizeof(T));
-  return EF_OK;
-}
-// HOST points / normals / row / plane: staged, the device call run, the per-point outputs copied back
-template <typename Run>
-int register_host(ef_ctx* c, const RegisterCall& q, Run run) {
-  const size_t n = q.n;
-  const size_t o_pts = 0, o_nrm = o_pts + n * 12, o_row = o_nrm + (q.normals ? n * 12 : 0), o_pl = o_row + n * 4;
-  RegisterCall d = q;
-  if (n) {
-    const int r = grow(c, &c->reg_stage, &c->reg_stage_bytes, o_pl + n * 4 + 16, "registration staging");
-    if (r != EF_OK) return r;
-    uint8_t* st = c->reg_stage;
-    d.points = (const float*)(st + o_pts);
-    d.normals = q.normals ? (const float*)(st + o_nrm) : nullptr;
-    d.row = q.row ? (uint32_t*)(st + o_row) : nullptr;
-    d.plane = q.plane ? (float*)(st + o_pl) : nullptr;
-    EF_HIP(c, hipMemcpyAsync(st + o_pts, q.points, n * 12, hipMemcpyHostToDevice, c->stream));
-    if (q.normals) EF_HIP(c, hipMemcpyAsync(st + o_nrm, q.normals, n * 12, hipMemcpyHostToDevice, c->stream));
-  }
-  const int r = run(d);
-  if (r != EF_OK) return r;
-  if (n) {
-    if (q.row) EF_HIP(c, hipMemcpyAsync(q.row, d.row, n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (q.plane) EF_HIP(c, hipMemcpyAsync(q.plane, d.plane, n * 4, hipMemcpyDeviceToHost, c->stream));
-    EF_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  return EF_OK;
-}
-}  // namespace
-extern "C" {
-
-int ef_default_register_params(ef_ctx* c, ef_register_params* p) {
-  if (!c) { g_create_error = "ef_default_register_params: null context"; return EF_EINVAL; }
-  if (!p) { c->err = "ef_default_register_params: null params"; return EF_EINVAL; }
-  memset(p, 0, sizeof(*p));
-  p->max_dist = 0.05f;
-  p->min_conf = c->cfg.confidence;
-  p->min_normal_cos = 0.5f;
-  p->max_iterations = 30;
-  p->min_pairs = 32;
-  p->stop_translation = 1e-6;
-  p->stop_rotation = 1e-6;
-  return EF_OK;
-}
-int ef_register_update(const ef_register_sums* s, const double* T_in, double* T_out, double* xi_out) {
-  if (!s || !T_out) { g_create_error = "ef_register_update: null sums or T_out"; return EF_EINVAL; }
-  const double* T = T_in ? T_in : REG_IDENTITY;
-  if (!finite16(T)) { g_create_error = "ef_register_update: T has a non-finite entry"; return EF_EINVAL; }
-  double d[6], xi[6];
-  efl::ldlt_pivots<double, 6>(s->A, d);
-  bool ok = true;
-  for (int i = 0; i < 6; ++i) ok = ok && std::isfinite(d[i]) && d[i] > 0.0;
-  if (ok) {
-    efl::ldlt_solve<double, 6>(s->A, s->b, xi);
-    for (int i = 0; i < 6; ++i) ok = ok && std::isfinite(xi[i]);
-  }
-  if (!ok) {
-    double keep[16];
-    memcpy(keep, T, sizeof(keep));
-    memcpy(T_out, keep, sizeof(keep));
-    if (xi_out) for (int i = 0; i < 6; ++i) xi_out[i] = 0.0;
-    return EF_REG_DEGENERATE;
-  }
-  bool none = true;
-  for (int i = 0; i < 6; ++i) none = none && xi[i] == 0.0;
-  if (none) {   // exp(0) = I: T as it is, bit for bit (a product with I would turn a -0 entry into +0)
-    double keep[16];
-    memcpy(keep, T, sizeof(keep));
-    memcpy(T_out, keep, sizeof(keep));
-    if (xi_out) for (int i = 0; i < 6; ++i) xi_out[i] = 0.0;
-    return EF_OK;
-  }
-  // exp(xi): R = I + a W + b W^2, V = I + b W + c W^2
-  const double wx = xi[3], wy = xi[4], wz = xi[5];
-  const double th2 = wx * wx + wy * wy + wz * wz, th = std::sqrt(th2);
-  double a, b, cc;
-  if (th < EF_REGISTER_SMALL_ANGLE) {
-    a = 1.0 - th2 / 6.0;
-    b = 0.5 - th2 / 24.0;
-    cc = 1.0 / 6.0 - th2 / 120.0;
-  } else {
-    a = std::sin(th) / th;
-    b = (1.0 - std::cos(th)) / th2;
-    cc = (1.0 - a) / th2;
-  }
-  const double W[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
-  double W2[9], R[9], V[9];
-  efl::m3_mul(W, W, W2);
-  for (int k = 0; k < 9; ++k) {
-    const double id = (k % 4 == 0) ? 1.0 : 0.0;
-    R[k] = (id + a * W[k]) + b * W2[k];
-    V[k] = (id + b * W[k]) + cc * W2[k];
-  }
-  double tv[3];
-  efl::m3_mulv(V, xi, tv);
-  double o[16] = {0};
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) o[i * 4 + j] = (R[i * 3] * T[j] + R[i * 3 + 1] * T[4 + j]) + R[i * 3 + 2] * T[8 + j];
-    o[i * 4 + 3] = ((R[i * 3] * T[3] + R[i * 3 + 1] * T[7]) + R[i * 3 + 2] * T[11]) + tv[i];
-  }
-  o[15] = 1.0;
-  memcpy(T_out, o, sizeof(o));
-  if (xi_out) for (int i = 0; i < 6; ++i) xi_out[i] = xi[i];
-  return EF_OK;
-}
-int ef_register_step_dev(ef_ctx* c, const float* points3, const float* normals3, uint32_t n, const ef_register_params* p, const double* T,
-                         ef_register_sums* out, uint32_t* row, float* plane) {
-  const RegisterCall q{"ef_register_step_dev", points3, normals3, n, p, T, row, plane};
-  int r = register_check(c, q, out, "out");
-  if (r != EF_OK) return r;
-  DeviceGuard dg_(c);
-  r = capture_check(c, q.fn);
-  if (r != EF_OK) return r;
-  return register_step_run(c, q, T ? T : REG_IDENTITY, out);
-}
-int ef_register_step(ef_ctx* c, const float* points3, const float* normals3, uint32_t n, const ef_register_params* p, const double* T,
-                     ef_register_sums* out, uint32_t* row, float* plane) {
-  const RegisterCall q{"ef_register_step", points3, normals3, n, p, T, row, plane};
-  int r = register_check(c, q, out, "out");
-  if (r != EF_OK) return r;
-  DeviceGuard dg_(c);
-  r = capture_check(c, q.fn);
-  if (r != EF_OK) return r;
-  return register_host(c, q, [&](const RegisterCall& d) { return register_step_run(c, d, T ? T : REG_IDENTITY, out); });
-}
-int ef_register_cloud_dev(ef_ctx* c, const float* points3, const float* normals3, uint32_t n, const ef_register_params* p, const double* T,
-                          double* T_out, ef_register_result* res, uint32_t* row, float* plane) {
-  const RegisterCall q{"ef_register_cloud_dev", points3, normals3, n, p, T, row, plane};
-  int r = register_check(c, q, T_out, "T_out");
-  if (r != EF_OK) return r;
-  if (!res) { c->err = "ef_register_cloud_dev: null result"; return EF_EINVAL; }
-  DeviceGuard dg_(c);
-  r = capture_check(c, q.fn);
-  if (r != EF_OK) return r;
-  return register_loop(c, q, T_out, res);
-}
-int ef_register_cloud(ef_ctx* c, const float* points3, const float* normals3, uint32_t n, const ef_register_params* p, const double* T,
-                      double* T_out, ef_register_result* res, uint32_t* row, float* plane) {
-  const RegisterCall q{"ef_register_cloud", points3, normals3, n, p, T, row, plane};
-  int r = register_check(c, q, T_out, "T_out");
-  if (r != EF_OK) return r;
-  if (!res) { c->err = "ef_register_cloud: null result"; return EF_EINVAL; }
-  DeviceGuard dg_(c);
-  r = capture_check(c, q.fn);
-  if (r != EF_OK) return r;
-  return register_host(c, q, [&](const RegisterCall& d) { return register_loop(c, d, T_out, res); });
-}
-
-}  // extern "C"
-
-// ================================================================================================
-// Select, extract and erase surfels (include/ef_hip.h; kernels in ef_select.inc)
-// ================================================================================================
-namespace {
-constexpr uint32_t SEL_KNOWN = EF_SEL_BOX | EF_SEL_CONF | EF_SEL_INIT_TIME | EF_SEL_LAST_TIME | EF_SEL_RADIUS | EF_SEL_ID | EF_SEL_LABEL | EF_SEL_INVERT;
-// refusals before any GPU work: the selection first, the context last (with a NULL context ef_last_error(NULL) names the argument)
-int select_check(ef_ctx* c, const ef_map_selection* s, const char* fn_) {
-  std::string& err = c ? c->err : g_create_error;
-  const std::string fn = fn_;
-  if (!s) { err = fn + ": null selection"; return EF_EINVAL; }
-  if (s->tests & ~SEL_KNOWN) { err = fn + ": unknown bits in tests"; return EF_EINVAL; }
-  if (s->tests & EF_SEL_BOX) {
-    if (!finite16(s->T_bw)) { err = fn + ": T_bw has a non-finite entry"; return EF_EINVAL; }
-    for (int a = 0; a < 3; ++a)
-      if (std::isnan(s->box_min[a]) || std::isnan(s->box_max[a])) { err = fn + ": a box bound is NaN"; return EF_EINVAL; }
-  }
-  if ((s->tests & EF_SEL_CONF) && (std::isnan(s->conf_min) || std::isnan(s->conf_max))) { err = fn + ": a confidence bound is NaN"; return EF_EINVAL; }
-  if ((s->tests & EF_SEL_RADIUS) && (std::isnan(s->radius_min) || std::isnan(s->radius_max))) { err = fn + ": a radius bound is NaN"; return EF_EINVAL; }
-  if (s->tests & EF_SEL_LABEL) {
-    if (std::isnan(s->label_min_prob)) { err = fn + ": label_min_prob is NaN"; return EF_EINVAL; }
-    if (s->label_class < 0 || (c && c->label_C && s->label_class >= c->label_C)) { err = fn + ": label_class outside 0 .. C-1"; return EF_EINVAL; }
-  }
-  return EF_OK;
-}
-int select_null(ef_ctx* c, const char* fn, const char* what) {
-  (c ? c->err : g_create_error) = std::string(fn) + ": null " + what;
-  return EF_EINVAL;
-}
-// the map count without a device round trip while no call that can change the map has run since it was read
-int select_count(ef_ctx* c, uint32_t* n) {
-  if (c->sel_gen != c->map_gen) {
-    const int r = read_count(c, &c->sel_count);
-    if (r != EF_OK) return r;
-    c->sel_gen = c->map_gen;
-  }
-  *n = c->sel_count;
-  return EF_OK;
-}
-// flags, chunk counts and offsets for n rows, and the word the scan leaves the total in
-int select_scratch(ef_ctx* c, uint32_t n, efm::SelectScratch* sc, uint32_t** total) {
-  if (n > c->sel_rows || !c->sel_scratch) {
-    const size_t P = (size_t)c->cam.cols * c->cam.rows;
-    const size_t rows = std::min((size_t)c->capacity, (size_t)n + std::max((size_t)n / 4, P));
-    const size_t chunks = efm::select_chunks((unsigned)rows) + 1;
-    c->sel_rows = 0;
-    const int r = grow(c, &c->sel_scratch, &c->sel_scratch_bytes, (2 * chunks + 4) * sizeof(uint32_t) + rows, "selection scratch");
-    if (r != EF_OK) return r;
-    c->sel_rows = rows;
-  }
-  const size_t chunks = efm::select_chunks((unsigned)c->sel_rows) + 1;
-  uint32_t* w = (uint32_t*)c->sel_scratch;
-  sc->chunk_count = w;
-  sc->chunk_offset = w + chunks;
-  *total = w + 2 * chunks;
-  sc->flags = (uint8_t*)(w + 2 * chunks + 4);
-  return EF_OK;
-}
-// state refusals, ID numbering and label alignment of a selection, then its device form for the n rows of the map
-int select_prepare(ef_ctx* c, const ef_map_selection* s, const char* fn, efm::SelectArgs* a, uint32_t* n) {
-  if ((s->tests & EF_SEL_ID) && !c->ids_on) { c->err = std::string(fn) + ": EF_SEL_ID while surfel IDs are off (ef_set_surfel_ids)"; return EF_ESTATE; }
-  if ((s->tests & EF_SEL_LABEL) && !c->label_C) { c->err = std::string(fn) + ": EF_SEL_LABEL while labels are off (ef_enable_labels)"; return EF_ESTATE; }
-  int r;
-  if (s->tests & EF_SEL_LABEL) r = labels_begin(c, fn);   // (numbers the new rows too)
-  else if (s->tests & EF_SEL_ID) r = ids_prepare(c, fn);
-  else r = EF_OK;
-  if (r != EF_OK) return r;
-  r = select_count(c, n);
-  if (r != EF_OK) return r;
-  *a = efm::SelectArgs{};
-  a->map = c->maps[c->cur];
-  a->n = *n;
-  a->tests = s->tests & ~EF_SEL_INVERT;
-  a->invert = (s->tests & EF_SEL_INVERT) ? 1u : 0u;
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) a->R[i * 3 + j] = (float)s->T_bw[i * 4 + j];
-    a->t[i] = (float)s->T_bw[i * 4 + 3];
-    a->box_min[i] = s->box_min[i];
-    a->box_max[i] = s->box_max[i];
-  }
-  a->conf_min = s->conf_min; a->conf_max = s->conf_max;
-  a->init_min = (float)s->init_time_min; a->init_max = (float)s->init_time_max;
-  a->last_min = (float)s->last_time_min; a->last_max = (float)s->last_time_max;
-  a->radius_min = s->radius_min; a->radius_max = s->radius_max;
-  a->id_min = s->id_min; a->id_max = s->id_max;
-  a->tab = (s->tests & EF_SEL_LABEL) ? c->label_tab[c->label_cur] : nullptr;
-  a->C = c->label_C;
-  a->label_class = s->label_class;
-  a->label_min_prob = s->label_min_prob;
-  return EF_OK;
-}
-// device pointers; enqueues only (but for what select_prepare and the scratch need)
-int select_enqueue(ef_ctx* c, const ef_map_selection* s, const char* fn, uint32_t* rows_dev, uint32_t max_rows, uint32_t* count_dev) {
-  efm::SelectArgs a;
-  uint32_t n = 0;
-  int r = select_prepare(c, s, fn, &a, &n);
-  if (r != EF_OK) return r;
-  efm::SelectScratch sc;
-  uint32_t* total = nullptr;
-  r = select_scratch(c, n, &sc, &total);
-  if (r != EF_OK) return r;
-  efm::select_flags(a, sc, count_dev, c->stream);
-  efm::select_rows(sc, n, rows_dev, max_rows, c->stream);
-  EF_HIP(c, hipGetLastError());
-  return EF_OK;
-}
-int gather_enqueue(ef_ctx* c, const char* fn, const uint32_t* rows_dev, uint32_t n_rows, float* out_dev) {
-  if (c->ids_on) {
-    const int ri = ids_prepare(c, fn);
-    if (ri != EF_OK) return ri;
-  }
-  if (!n_rows) return EF_OK;
-  uint32_t n = 0;
-  const int r = select_count(c, &n);
-  if (r != EF_OK) return r;
-  efm::map_gather(c->maps[c->cur], n, rows_dev, n_rows, out_dev, c->stream);
-  EF_HIP(c, hipGetLastError());
-  return EF_OK;
-}
-// The erase, after the arguments were checked.  mark(n, sc, total) enqueues the flags, the chunk counts and offsets of the KEPT rows (those whose
-// flag differs from `flip`) and their number into *total.
-template <typename Mark>
-int erase_run(ef_ctx* c, const char* fn, unsigned flip, uint32_t* removed, Mark mark) {
-  int r = capture_check(c, fn);
-  if (r != EF_OK) return r;
-  if (c->cfg.close_loops) {
-    c->err = std::string(fn) + ": the context closes loops (close_loops = 1): its graph nodes, fern keyframes and pending end-of-frame record describe "
-             "the unedited map";
-    return EF_ESTATE;
-  }
-  // (every frame, every input stage on in_stream that the last frame's events ordered behind it, and every upload has been waited for by what
-  // follows a synchronised stream: no new event logic)
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  if (c->ids_on) {   // the new rows are numbered before any of them can go: the counter then stands above every ID handed out
-    r = ids_prepare(c, fn);
-    if (r != EF_OK) return r;
-  }
-  uint32_t n = 0;
-  r = select_count(c, &n);
-  if (r != EF_OK) return r;
-  efm::SelectScratch sc;
-  uint32_t* total = nullptr;
-  r = select_scratch(c, n, &sc, &total);
-  if (r != EF_OK) return r;
-  r = mark(n, sc, total);
-  if (r != EF_OK) return r;
-  EF_HIP(c, hipGetLastError());
-  uint32_t kept = 0;
-  EF_HIP(c, hipMemcpyAsync(&kept, total, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  if (kept > n) { c->err = std::string(fn) + ": internal error (more rows kept than the map holds)"; return EF_EHIP; }
-  ++c->map_gen;   // the index of the queries is stale
-  if (kept < n) {
-    // after a keyed frame maps[cur ^ 1] is the buffer the kept z-buffer keys name: the four index maps are resolved from it before it is overwritten
-    im_materialise(c);
-    efm::select_compact(sc, n, flip, c->maps[c->cur], c->maps[c->cur ^ 1], c->stream);
-    hipLaunchKernelGGL(k_set_count, dim3(1), dim3(64), 0, c->stream, &c->st->map_counts[c->cur ^ 1], kept);
-    EF_HIP(c, hipGetLastError());
-    c->cur ^= 1;
-  }
-  c->sel_count = kept;
-  c->sel_gen = c->map_gen;
-  if (c->tick > 1 || !c->stamps.empty()) {   // a frame or a restore has run: the next frame is tracked against a prediction of the edited map
-    EF_HIP(c, hipMemsetAsync(&c->st->dense_count, 0, sizeof(unsigned), c->stream));   // (as ef_predict: this prediction's tally replaces the last one's)
-    r = do_predict(c);
-    if (r != EF_OK) return r;
-    EF_HIP(c, hipGetLastError());
-  }
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  if (removed) *removed = n - kept;
-  return EF_OK;
-}
-}  // namespace
-
-extern "C" {
-
-void ef_default_map_selection(ef_map_selection* s) {
-  if (!s) return;
-  memset(s, 0, sizeof(*s));
-  const float inf = std::numeric_limits<float>::infinity();
-  s->T_bw[0] = s->T_bw[5] = s->T_bw[10] = s->T_bw[15] = 1.0;
-  for (int a = 0; a < 3; ++a) { s->box_min[a] = -inf; s->box_max[a] = inf; }
-  s->conf_min = -inf; s->conf_max = inf;
-  s->init_time_min = s->last_time_min = std::numeric_limits<int>::min();
-  s->init_time_max = s->last_time_max = std::numeric_limits<int>::max();
-  s->radius_min = -inf; s->radius_max = inf;
-  s->id_min = 0u; s->id_max = 0xFFFFFFFFu;
-  s->label_class = 0;
-  s->label_min_prob = -inf;
-}
-
-int ef_map_select_dev(ef_ctx* c, const ef_map_selection* s, uint32_t* rows_dev, uint32_t max_rows, uint32_t* count_dev) {
-  int r = select_check(c, s, "ef_map_select_dev");
-  if (r != EF_OK) return r;
-  if (max_rows && !rows_dev) return select_null(c, "ef_map_select_dev", "rows");
-  if (!count_dev) return select_null(c, "ef_map_select_dev", "count");
-  if (!c) return select_null(c, "ef_map_select_dev", "context");
-  DeviceGuard dg_(c);
-  r = capture_check(c, "ef_map_select_dev");
-  if (r != EF_OK) return r;
-  return select_enqueue(c, s, "ef_map_select_dev", rows_dev, max_rows, count_dev);
-}
-int ef_map_select(ef_ctx* c, const ef_map_selection* s, uint32_t* rows, uint32_t max_rows, uint32_t* count) {
-  int r = select_check(c, s, "ef_map_select");
-  if (r != EF_OK) return r;
-  if (max_rows && !rows) return select_null(c, "ef_map_select", "rows");
-  if (!count) return select_null(c, "ef_map_select", "count");
-  if (!c) return select_null(c, "ef_map_select", "context");
-  DeviceGuard dg_(c);
-  r = capture_check(c, "ef_map_select");
-  if (r != EF_OK) return r;
-  // (the list is never longer than the map: the staging is sized by the capacity at most)
-  const size_t cap_rows = std::min((size_t)max_rows, (size_t)c->capacity);
-  r = grow(c, &c->sel_stage, &c->sel_stage_bytes, 16 + cap_rows * 4, "selection staging");
-  if (r != EF_OK) return r;
-  uint32_t* d_count = (uint32_t*)c->sel_stage;
-  uint32_t* d_rows = (uint32_t*)(c->sel_stage + 16);
-  r = select_enqueue(c, s, "ef_map_select", d_rows, (uint32_t)cap_rows, d_count);
-  if (r != EF_OK) return r;
-  EF_HIP(c, hipMemcpyAsync(count, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  const size_t got = std::min((size_t)*count, cap_rows);
-  if (got) {
-    EF_HIP(c, hipMemcpyAsync(rows, d_rows, got * 4, hipMemcpyDeviceToHost, c->stream));
-    EF_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  return EF_OK;
-}
-
-int ef_map_gather_dev(ef_ctx* c, const uint32_t* rows_dev, uint32_t n, float* out_dev) {
-  if (n && !rows_dev) return select_null(c, "ef_map_gather_dev", "rows");
-  if (n && !out_dev) return select_null(c, "ef_map_gather_dev", "surfels12");
-  if (!c) return select_null(c, "ef_map_gather_dev", "context");
-  DeviceGuard dg_(c);
-  const int r = capture_check(c, "ef_map_gather_dev");
-  if (r != EF_OK) return r;
-  return gather_enqueue(c, "ef_map_gather_dev", rows_dev, n, out_dev);
-}
-int ef_map_gather(ef_ctx* c, const uint32_t* rows, uint32_t n, float* out) {
-  if (n && !rows) return select_null(c, "ef_map_gather", "rows");
-  if (n && !out) return select_null(c, "ef_map_gather", "surfels12");
-  if (!c) return select_null(c, "ef_map_gather", "context");
-  DeviceGuard dg_(c);
-  int r = capture_check(c, "ef_map_gather");
-  if (r != EF_OK) return r;
-  const size_t o_out = ((size_t)n * 4 + 15) & ~(size_t)15;
-  r = grow(c, &c->sel_stage, &c->sel_stage_bytes, 16 + o_out + (size_t)n * 48, "selection staging");
-  if (r != EF_OK) return r;
-  uint32_t* d_rows = (uint32_t*)c->sel_stage;
-  float* d_out = (float*)(c->sel_stage + o_out);
-  if (n) EF_HIP(c, hipMemcpyAsync(d_rows, rows, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  r = gather_enqueue(c, "ef_map_gather", d_rows, n, d_out);
-  if (r != EF_OK) return r;
-  if (n) EF_HIP(c, hipMemcpyAsync(out, d_out, (size_t)n * 48, hipMemcpyDeviceToHost, c->stream));
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  return EF_OK;
-}
-
-int ef_map_erase(ef_ctx* c, const ef_map_selection* s, uint32_t* removed) {
-  const int r = select_check(c, s, "ef_map_erase");
-  if (r != EF_OK) return r;
-  if (!c) return select_null(c, "ef_map_erase", "context");
-  DeviceGuard dg_(c);
-  // the flags are those of the KEPT rows: the selection with its inversion toggled
-  ef_map_selection keep = *s;
-  keep.tests ^= EF_SEL_INVERT;
-  return erase_run(c, "ef_map_erase", 0u, removed, [&](uint32_t, const efm::SelectScratch& sc, uint32_t* total) {
-    efm::SelectArgs a;
-    uint32_t n = 0;
-    const int rp = select_prepare(c, &keep, "ef_map_erase", &a, &n);
-    if (rp != EF_OK) return rp;
-    efm::select_flags(a, sc, total, c->stream);
-    return (int)EF_OK;
-  });
-}
-int ef_map_erase_rows_dev(ef_ctx* c, const uint32_t* rows_dev, uint32_t n_rows, uint32_t* removed) {
-  if (n_rows && !rows_dev) return select_null(c, "ef_map_erase_rows_dev", "rows");
-  if (!c) return select_null(c, "ef_map_erase_rows_dev", "context");
-  DeviceGuard dg_(c);
-  return erase_run(c, "ef_map_erase_rows_dev", 1u, removed, [&](uint32_t n, const efm::SelectScratch& sc, uint32_t* total) {
-    efm::select_mark_rows(rows_dev, n_rows, n, 1u, sc, total, c->stream);
-    return (int)EF_OK;
-  });
-}
-int ef_map_erase_rows(ef_ctx* c, const uint32_t* rows, uint32_t n_rows, uint32_t* removed) {
-  if (n_rows && !rows) return select_null(c, "ef_map_erase_rows", "rows");
-  if (!c) return select_null(c, "ef_map_erase_rows", "context");
-  DeviceGuard dg_(c);
-  return erase_run(c, "ef_map_erase_rows", 1u, removed, [&](uint32_t n, const efm::SelectScratch& sc, uint32_t* total) {
-    const int rg = grow(c, &c->sel_stage, &c->sel_stage_bytes, 16 + (size_t)n_rows * 4, "selection staging");
-    if (rg != EF_OK) return rg;
-    if (n_rows) EF_HIP(c, hipMemcpyAsync(c->sel_stage, rows, (size_t)n_rows * 4, hipMemcpyHostToDevice, c->stream));
-    efm::select_mark_rows((const uint32_t*)c->sel_stage, n_rows, n, 1u, sc, total, c->stream);
-    return (int)EF_OK;
-  });
-}
-
-}  // extern "C"
+// The map operations' host code, one file beside each kernel file of ef_map_kernels.hip, in dependency order (each may use what the ones before it define)
+#include "ef_host_ops.inc"
+#include "ef_host_render.inc"
+#include "ef_host_labels.inc"
+#include "ef_host_query.inc"
+#include "ef_host_register.inc"
+#include "ef_host_select.inc"
