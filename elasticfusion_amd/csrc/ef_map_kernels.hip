@@ -60,6 +60,18 @@ __device__ __forceinline__ float encodeColor(f3 c) {
   rgb = (rgb << 8) + (int)roundf(c.z * 255.0f);
   return (float)rgb;
 }
+// update.vert's int(round(mean * 255)) where the weighted mean is not finite (c_k + a == 0 gives 0 / 0 or x / 0): GLSL leaves that conversion
+// undefined, the specification is what the compiled shaders give on their host — INT_MIN for NaN and for every value outside int's range
+// ("still specified") — and the shifts wrap.  Only the update pass can see such a mean: a new point's colour is a byte / 255.
+__device__ __forceinline__ unsigned int_or_indefinite(float v) {
+  return (v >= -2147483648.0f && v < 2147483648.0f) ? (unsigned)(int)v : 0x80000000u;
+}
+__device__ __forceinline__ float encodeColorMerged(f3 c) {
+  unsigned rgb = int_or_indefinite(roundf(c.x * 255.0f));
+  rgb = (rgb << 8) + int_or_indefinite(roundf(c.y * 255.0f));
+  rgb = (rgb << 8) + int_or_indefinite(roundf(c.z * 255.0f));
+  return (float)(int)rgb;
+}
 __device__ __forceinline__ f3 decodeColor(float c) {
   const int ic = (int)c;
   return {(float)((ic >> 16) & 0xFF) / 255.0f, (float)((ic >> 8) & 0xFF) / 255.0f, (float)(ic & 0xFF) / 255.0f};
@@ -840,7 +852,7 @@ __device__ __forceinline__ void merge_surfel(const Candidates& cand, int r, uint
     const f3 oldCol = decodeColor(sc.x), newCol = decodeColor(ucol.x);
     const f3 avg{((c_k * oldCol.x) + (a * newCol.x)) / (c_k + a), ((c_k * oldCol.y) + (a * newCol.y)) / (c_k + a),
                  ((c_k * oldCol.z) + (a * newCol.z)) / (c_k + a)};
-    sc.x = encodeColor(avg);
+    sc.x = encodeColorMerged(avg);
     sc.w = ftime;
     const float nx = ((c_k * sn.x) + (a * un.x)) / (c_k + a), ny = ((c_k * sn.y) + (a * un.y)) / (c_k + a),
                 nz = ((c_k * sn.z) + (a * un.z)) / (c_k + a), nw = ((c_k * sn.w) + (a * un.w)) / (c_k + a);

@@ -47,11 +47,14 @@ inline f3 trans_of(const Mat4f& M) { return {M.m[3], M.m[7], M.m[11]}; }
 inline f3 xform(const Mat4f& M, f3 p) { return mul(rot_of(M), p) + trans_of(M); }
 
 // color.glsl:19-34
+// int(round(x)) of a value that is not finite (update.vert with c_k + a == 0) or outside int's range is undefined in GLSL and in C++; the
+// specification is what the compiled shaders give on their host: INT_MIN ("still specified", README.md), and the shifts wrap
+inline unsigned int_or_indefinite(float v) { return (v >= -2147483648.0f && v < 2147483648.0f) ? (unsigned)(int)v : 0x80000000u; }
 inline float encodeColor(f3 c) {
-  int rgb = (int)roundf(c.x * 255.0f);
-  rgb = (rgb << 8) + (int)roundf(c.y * 255.0f);
-  rgb = (rgb << 8) + (int)roundf(c.z * 255.0f);
-  return (float)rgb;
+  unsigned rgb = int_or_indefinite(roundf(c.x * 255.0f));
+  rgb = (rgb << 8) + int_or_indefinite(roundf(c.y * 255.0f));
+  rgb = (rgb << 8) + int_or_indefinite(roundf(c.z * 255.0f));
+  return (float)(int)rgb;
 }
 inline f3 decodeColor(float c) {
   int ic = (int)c;
