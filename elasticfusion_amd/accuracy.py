@@ -72,6 +72,19 @@ def register_to_map(ef: "api.ElasticFusion", surfels_or_points: np.ndarray, T_in
     return T, stages
 
 
+def merge_session(ef: "api.ElasticFusion", surfels: np.ndarray, T_init=None, register: dict | None = None, rows: bool = False, **insert) -> tuple:
+    """Continues ef's map with the surfels of another session ([m, 12] as downloadMap() gives them, in their own frame): register_to_map on
+    their positions and normals from T_init (keywords in `register`), then insertSurfels with the pose found (ef_map_insert: the records
+    the map does not already hold within min_separation are appended; other keywords are ef_insert_params fields).  A registration whose last
+    stage ended TOO_FEW_PAIRS or DEGENERATE inserts nothing.  Returns (T 4 x 4 float64, [per-stage registration results], the insert
+    result or None) — with rows=True the insert result is insertSurfels' (result, new_row, match_row)."""
+    rec = np.ascontiguousarray(surfels, np.float32).reshape(-1, 12)
+    T, stages = register_to_map(ef, rec, T_init=T_init, **(register or {}))
+    if not stages or stages[-1]["status"] in (api.REG_TOO_FEW_PAIRS, api.REG_DEGENERATE):
+        return T, stages, None
+    return T, stages, ef.insertSurfels(rec, T=T, rows=rows, **insert)
+
+
 def map_accuracy(ef: "api.ElasticFusion", gt_surfels: np.ndarray, max_dist: float = 0.05, map_rows=None, gt_rows=None, device: int = 0,
                  align: bool = False, align_schedule=REGISTER_SCHEDULE) -> dict:
     """ef: a context with a map; gt_surfels: [m, 12] float32, laid out as downloadMap() gives them (synth.sample_surfels), in the map's world

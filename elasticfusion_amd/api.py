@@ -72,6 +72,17 @@ class ef_map_selection(C.Structure):
                 ("radius_max", c_f), ("id_min", c_u32), ("id_max", c_u32), ("label_class", c_i), ("label_min_prob", c_f)]
 
 
+class ef_insert_params(C.Structure):
+    _fields_ = [("gate", c_i), ("min_separation", c_f), ("min_conf", c_f), ("min_normal_cos", c_f), ("init_time", c_i), ("last_time", c_i)]
+
+
+class ef_insert_result(C.Structure):
+    _fields_ = [("inserted", c_u32), ("duplicates", c_u32), ("skipped", c_u32), ("count_after", c_u32)]
+
+
+INSERT_KEEP = -1   # EF_INSERT_KEEP of include/ef_hip.h
+ROW_NONE = 0xFFFFFFFF
+
 # EF_SEL_* of include/ef_hip.h
 SEL_BOX, SEL_CONF, SEL_INIT_TIME, SEL_LAST_TIME, SEL_RADIUS, SEL_ID, SEL_LABEL, SEL_INVERT = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40, 0x100
 
@@ -1122,6 +1133,57 @@ class ElasticFusion:
         p = None if rows_dev is None else P(int(rows_dev.value if isinstance(rows_dev, P) else rows_dev))
         _chk(lib().ef_map_erase_rows_dev(self.h, p, c_u32(int(n)), C.byref(removed)), self.h)
         return removed.value
+
+    # --- insert surfels (ef_map_insert) ---
+    def insertParams(self, **kw) -> ef_insert_params:
+        """ef_default_insert_params (gate 1, min_separation 0.01, min_conf -1, min_normal_cos 0.5, both times the tick) with fields replaced
+        by keyword"""
+        p = ef_insert_params()
+        _chk(lib().ef_default_insert_params(self.h, C.byref(p)), self.h)
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise TypeError(f"unknown insert parameter {k}")
+            setattr(p, k, v)
+        return p
+
+    def insertSurfels(self, surfels, T=None, params: ef_insert_params | None = None, rows: bool = False, n: int | None = None, **kw):
+        """appends the records (n x 12 float32 in downloadMap()'s layout, or a DevBuf holding n of them: ef_map_insert_dev) moved by T (4 x 4,
+        records -> world; None: copied) that pass the gate: {"inserted", "duplicates", "skipped", "count_after"}; rows=True: (result, new_row,
+        match_row), uint32 per record with api.ROW_NONE where there is none.  A refused insert (EF_ECAPACITY: nothing changed) raises EFError
+        with the counts in its .result"""
+        if params is None:
+            params = self.insertParams(**kw)
+        else:
+            assert not kw, "give params or keywords, not both"
+        keep, pT = _pose16(T)
+        res = ef_insert_result()
+        if isinstance(surfels, DevBuf):
+            n = surfels.nbytes // 48 if n is None else int(n)
+            assert n * 48 <= surfels.nbytes, (n, surfels.nbytes)
+            new_dev = DevBuf(max(n, 1) * 4) if rows else None
+            match_dev = DevBuf(max(n, 1) * 4) if rows else None
+            rc = lib().ef_map_insert_dev(self.h, surfels.p if n else None, c_u32(n), pT, C.byref(params), C.byref(res),
+                                         new_dev.p if rows else None, match_dev.p if rows else None)
+            new_row = new_dev.to_array(np.uint32, (n,)) if rows and rc == 0 else None
+            match_row = match_dev.to_array(np.uint32, (n,)) if rows and rc == 0 else None
+        else:
+            rec = np.ascontiguousarray(surfels, np.float32).reshape(-1, 12)
+            n = len(rec)
+            new_row = np.full(max(n, 1), ROW_NONE, np.uint32) if rows else None
+            match_row = np.full(max(n, 1), ROW_NONE, np.uint32) if rows else None
+            rc = lib().ef_map_insert(self.h, _ptr(rec) if n else None, c_u32(n), pT, C.byref(params), C.byref(res),
+                                     _ptr(new_row) if rows else None, _ptr(match_row) if rows else None)
+            if rows:
+                new_row, match_row = new_row[:n], match_row[:n]
+        out = {"inserted": int(res.inserted), "duplicates": int(res.duplicates), "skipped": int(res.skipped), "count_after": int(res.count_after)}
+        if rc != 0:
+            try:
+                _chk(rc, self.h)
+            except EFError as e:
+                e.result = out
+                e.rc = rc
+                raise
+        return (out, new_row, match_row) if rows else out
 
     def setReferenceDownload(self, on=True):
         """downloadMap / savePly read what GlobalModel::downloadMap reads (the pre-clean buffer, quirk Q14) instead of model()"""

@@ -266,6 +266,12 @@ struct ef_ctx {
     uint64_t gen = 0;
     uint32_t count = 0;
   } sel;
+  // insert (ef_map_insert; kernels in ef_insert.inc): scratch of its own, sized by the records of a call (which may outnumber the map's capacity),
+  // grown by the first call, freed with the context
+  struct InsertState {
+    DevBuf scratch;                        // chunk counts | chunk offsets | 4 words (the total) | one flag byte per record
+    size_t rows = 0;
+  } ins;
 };
 
 namespace {
@@ -1234,7 +1240,7 @@ void ctx_free(ef_ctx* c) {
   for (auto e : c->ka_stop) (void)hipEventDestroy(e);
   for (auto e : c->ks_start) (void)hipEventDestroy(e);
   for (auto e : c->ks_stop) (void)hipEventDestroy(e);
-  for (DevBuf* b : {&c->stage, &c->render.zbuf, &c->labels.index, &c->query.sorted, &c->query.rows, &c->query.cells, &c->reg.slabs, &c->sel.scratch})
+  for (DevBuf* b : {&c->stage, &c->render.zbuf, &c->labels.index, &c->query.sorted, &c->query.rows, &c->query.cells, &c->reg.slabs, &c->sel.scratch, &c->ins.scratch})
     b->release();
   for (int k = 0; k < 2; ++k) {
     if (c->labels.tab[k]) (void)hipFree(c->labels.tab[k]);
@@ -2260,3 +2266,4 @@ int ef_get_splat_timing(ef_ctx* c, ef_kernel_time* out) {
 #include "ef_host_query.inc"
 #include "ef_host_register.inc"
 #include "ef_host_select.inc"
+#include "ef_host_insert.inc"

@@ -308,4 +308,28 @@ void select_compact(const SelectScratch& sc, unsigned n, unsigned flip, SurfelSo
 // out: n_rows x 12 floats in the download's layout, in the order of rows[]; a row >= n gives twelve zero words
 void map_gather(SurfelSoA map, unsigned n, const uint32_t* rows, unsigned n_rows, float* out, hipStream_t s);
 
+// ---- insert surfels (ef_insert.inc; ef_map_insert of include/ef_hip.h) ----
+constexpr int INSERT_KEEP = -1;   // EF_INSERT_KEEP
+struct InsertArgs {
+  QueryArgs q;              // gate only: the index of the OLD map, max_dist / r2 = the separation, min_conf (points, n, k and the outputs unused)
+  const float4* rec;        // n records of three 16-byte words {x, y, z, conf} {colour, ID bits, initTime, lastTime} {nx, ny, nz, radius}
+  unsigned n;
+  int moved;                // T given: R, t below are applied; 0: position and normal are copied
+  float R[9], t[3];         // T rounded to f32 once (row-major rotation block, translation)
+  int gate;
+  float min_normal_cos;     // gate only; <= -1: no normal test
+  int init_time, last_time; // >= 0: stored as (float); INSERT_KEEP: the record's own
+  unsigned count_before;    // the scatter's first row
+  uint8_t* flags;           // one byte per record: 1 = insert
+  uint8_t* dup;             // gate only, one byte per record: 1 = duplicate (a record with neither byte set was skipped)
+  const uint32_t* chunk_offset;   // of the scatter: the exclusive scan of the flags' counts per SELECT_ROW records
+  uint32_t* match_row;      // n or null (written by the gate)
+  uint32_t* new_row;        // n or null (written by the scatter)
+};
+// flags (and match_row) of the n records, their per-chunk counts into sc.chunk_count, offsets into sc.chunk_offset and *total = records to insert;
+// with the gate on also a.dup and, through dup_sc (whose flags are a.dup), *dup_total = duplicates (gate off: neither is touched)
+void insert_gate(const InsertArgs& a, const SelectScratch& sc, uint32_t* total, const SelectScratch& dup_sc, uint32_t* dup_total, hipStream_t s);
+// the flagged records appended to dst at a.count_before in input order (a.chunk_offset = sc.chunk_offset of insert_gate), and new_row
+void insert_scatter(const InsertArgs& a, SurfelSoA dst, hipStream_t s);
+
 }  // namespace efm

@@ -1518,5 +1518,6 @@ void sample_graph(SurfelSoA map, const unsigned* count_dev, int stride, int max_
 #include "ef_query.inc"
 #include "ef_register.inc"
 #include "ef_select.inc"
+#include "ef_insert.inc"
 
 }  // namespace efm

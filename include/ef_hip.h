@@ -677,6 +677,85 @@ int ef_map_erase(ef_ctx* ctx, const ef_map_selection* sel, uint32_t* removed_or_
 int ef_map_erase_rows(ef_ctx* ctx, const uint32_t* rows, uint32_t n, uint32_t* removed_or_null);
 int ef_map_erase_rows_dev(ef_ctx* ctx, const uint32_t* rows_dev, uint32_t n, uint32_t* removed_or_null);
 
+/* ---- Insert surfels: transform a set of records, keep those the map does not already hold, append them.  Off until first used: no insert
+ * call, nothing allocated, nothing run, and no frame kernel knows of it.
+ *
+ * A RECORD is 12 floats in ef_map_download's layout (what ef_map_download and ef_map_gather produce): position = floats 0 .. 2, confidence = 3,
+ * colour = 4, ID bits = 5, creation time = 6, time last seen = 7, normal = 8 .. 10, radius = 11.  T (row-major 4 x 4 double like every other pose
+ * here) maps the records' frame into the map's world frame, as in ef_register_cloud.  All per-record arithmetic is f32, one rounding per
+ * operation, no contraction, in the written order.  Comparisons with NaN are false.
+ *
+ * TRANSFORM.  With T given, Rf, tf are its rotation block and translation rounded to f32 once, and for the position (x, y, z) and normal m:
+ *   p'x = ((Rf00*x + Rf01*y) + Rf02*z) + tfx, likewise y, z;   m'x = (Rf00*mx + Rf01*my) + Rf02*mz, likewise y, z
+ * (the expressions ef_register_step documents).  With T NULL nothing is computed: p' = p and m' = m bit for bit, -0 and NaN payloads included
+ * (an identity T does compute: it turns -0 + 0 into +0).  Confidence, colour and radius are always copied bit for bit.
+ *
+ * GATE (gate = 1).  s = the row ef_query_nearest returns for p' with max_dist = min_separation and this min_conf, on the map AS IT STANDS BEFORE
+ * THE CALL: the same eligibility, the same (d2, row) order, the same treatment of non-finite input.  The record is a DUPLICATE iff s is a hit and
+ * (min_normal_cos <= -1 or ((m'x*nsx + m'y*nsy) + m'z*nsz) >= min_normal_cos), ns the stored normal of s, not renormalised; a NaN fails the
+ * comparison, so the record is not a duplicate.  Only the NEAREST eligible surfel is asked: where the nearest is the back face of a thin wall whose
+ * normal fails the test, the record is let in even if a surfel of its own side also lies inside the radius.  Records never gate one another: the
+ * outcome of a record depends on the old map alone, never on n or on the records' order.  With gate = 0 no record is a duplicate and
+ * min_separation, min_conf and min_normal_cos are neither read nor checked.
+ *
+ * OUTCOME per record i (new_row, match_row: n words each, either may be NULL):
+ *   SKIPPED    p' has a non-finite coordinate:  new_row[i] = match_row[i] = 0xFFFFFFFF;
+ *   DUPLICATE  new_row[i] = 0xFFFFFFFF, match_row[i] = s;
+ *   INSERTED   match_row[i] = 0xFFFFFFFF, new_row[i] = count_before + (the number of inserted records before i in the input).
+ * result (HOST memory in both variants) = the three counts and count_after, the map count the call leaves.
+ *
+ * What an insert leaves behind:
+ *   the map       the old rows untouched, every word of them, followed by the inserted records in input order (the append is stable).  An inserted
+ *                 row is: p' and the record's confidence; the record's colour, ZERO bits in the ID lane whatever the record held, float 6 =
+ *                 (float)init_time if init_time >= 0 or the record's own under EF_INSERT_KEEP, float 7 likewise from last_time; m' and the
+ *                 record's radius;
+ *   IDs           with IDs on, the rows created since the last ID-consuming call are numbered BEFORE the append (as the erase does), and the next
+ *                 ID-consuming call numbers the inserted rows above every ID ever handed out.  A gathered record does not bring its old ID back;
+ *   the context   the state that ef_map_upload(old rows ++ inserted rows) followed by ef_restore_state(tick, ef_get_pose_qt, the last processed
+ *                 frame) would leave: tick, pose, trajectory, last frame and tracking statistics are unchanged, and if ef_process_frame* or
+ *                 ef_restore_state has run on the context the model prediction is renewed from the edited map at the current pose.  On a context
+ *                 whose map was only uploaded, only the map changes;
+ *   the index     of the queries and the registration is stale and rebuilt by their next call;
+ *   labels        the next label call re-aligns by ID: old rows keep their C floats bit for bit, inserted rows get the prior 1 / C;
+ *   the shadow buffer of ef_set_reference_download is left as it is.
+ * Inserting nothing (n = 0, every record a duplicate or skipped) is valid and still leaves the state described.
+ *
+ * CAPACITY.  The number to insert is known before anything is written.  If count_before + inserted > max_surfels the call returns EF_ECAPACITY
+ * and nothing has changed: map, count, prediction, the index's validity.  result still carries the three counts, with count_after =
+ * count_before; match_row is written, new_row is not.
+ *
+ * Defaults (ef_default_insert_params): gate 1, min_separation 0.01 m, min_conf -1 (every surfel can suppress a record), min_normal_cos 0.5 (the
+ * registration's default), both times the context's tick.  0.01 m is half of EF_QUERY_DEFAULT_CELL, so that a walk visits at most 27 cells: a
+ * convention, not a measurement.
+ *
+ * Both variants synchronise before and after, like the erase calls.  ef_map_insert stages its arrays; ef_map_insert_dev takes DEVICE pointers for
+ * the records and the two row arrays.  surfels12_dev is read in 16-byte words: it must be 16-byte aligned, as every ef_dev_alloc pointer is, and
+ * must not lie inside the map.
+ *
+ * EF_EINVAL, before any GPU work (the arguments are checked before the context, so with a NULL context ef_last_error(NULL) names what is wrong
+ * with them): a NULL context, params or result; n > 0 with NULL records; n above EF_INSERT_MAX_RECORDS (2^28 - 1: 12 GB of records in one
+ * call); a non-finite entry of T; gate outside 0 / 1; a time below
+ * EF_INSERT_KEEP; with gate = 1: min_separation, min_conf and the ratio to the query cell as ef_query_nearest refuses max_dist, min_conf and
+ * max_dist / cell, or a NaN min_normal_cos; surfels12_dev not 16-byte aligned.
+ * EF_ESTATE: the context's stream is being captured; a context created with close_loops = 1 (the erase's reason); with IDs on, a context whose
+ * uploaded ID lane was refused (ef_set_surfel_ids above). */
+#define EF_INSERT_KEEP (-1)
+#define EF_INSERT_MAX_RECORDS 0x0FFFFFFFu
+typedef struct ef_insert_params {
+  int   gate;            /* 0: every record with a finite moved position is inserted; 1: the novelty gate above */
+  float min_separation;  /* gate radius in metres: ef_query_nearest's max_dist */
+  float min_conf;        /* which map surfels can suppress a record: as ef_query_nearest (negative = every surfel) */
+  float min_normal_cos;  /* <= -1: no normal test */
+  int   init_time;       /* >= 0: float 6 of the stored row = (float)init_time; EF_INSERT_KEEP: the record's own */
+  int   last_time;       /* likewise float 7 */
+} ef_insert_params;
+typedef struct ef_insert_result { uint32_t inserted, duplicates, skipped, count_after; } ef_insert_result;
+int ef_default_insert_params(ef_ctx* ctx, ef_insert_params* params);
+int ef_map_insert(ef_ctx* ctx, const float* surfels12, uint32_t n, const double* T16_or_null, const ef_insert_params* params,
+                  ef_insert_result* result, uint32_t* new_row_or_null, uint32_t* match_row_or_null);
+int ef_map_insert_dev(ef_ctx* ctx, const float* surfels12_dev, uint32_t n, const double* T16_or_null, const ef_insert_params* params,
+                      ef_insert_result* result, uint32_t* new_row_dev_or_null, uint32_t* match_row_dev_or_null);
+
 /* named internal images, copied to HOST (synchronises); for tests and for a front-end's drawing code */
 enum ef_image {
   EF_IMG_DEPTH_FILTERED = 0,      /* u16  */
