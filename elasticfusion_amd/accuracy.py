@@ -85,6 +85,13 @@ def merge_session(ef: "api.ElasticFusion", surfels: np.ndarray, T_init=None, reg
     return T, stages, ef.insertSurfels(rec, T=T, rows=rows, **insert)
 
 
+def thinned_map(ef: "api.ElasticFusion", cell: float, keep: int = api.THIN_KEEP_MAX_CONF, among=None) -> np.ndarray:
+    """One surfel per `cell`-sized voxel of ef's map, [k, 12] float32 as downloadMap() gives them, without a download of the map and without
+    changing it: thinSelect(representatives=True) + gatherSurfels (ef_map_thin_select + ef_map_gather).  keep: which surfel stands for its
+    voxel (api.THIN_KEEP_*); among: as thinSelect takes it, only the surfels it selects (and only their representatives) come out."""
+    return ef.gatherSurfels(ef.thinSelect(cell=float(cell), keep=int(keep), among=among, representatives=True))
+
+
 def map_accuracy(ef: "api.ElasticFusion", gt_surfels: np.ndarray, max_dist: float = 0.05, map_rows=None, gt_rows=None, device: int = 0,
                  align: bool = False, align_schedule=REGISTER_SCHEDULE) -> dict:
     """ef: a context with a map; gt_surfels: [m, 12] float32, laid out as downloadMap() gives them (synth.sample_surfels), in the map's world

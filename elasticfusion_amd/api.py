@@ -80,6 +80,16 @@ class ef_insert_result(C.Structure):
     _fields_ = [("inserted", c_u32), ("duplicates", c_u32), ("skipped", c_u32), ("count_after", c_u32)]
 
 
+class ef_thin_params(C.Structure):
+    _fields_ = [("cell", c_f), ("keep", c_i)]
+
+
+class ef_thin_result(C.Structure):
+    _fields_ = [("participants", c_u32), ("cells", c_u32), ("removed", c_u32), ("count_after", c_u32)]
+
+
+THIN_KEEP_MAX_CONF, THIN_KEEP_NEWEST, THIN_KEEP_FIRST = 0, 1, 2   # EF_THIN_KEEP_* of include/ef_hip.h
+THIN_ROWS_REMOVED, THIN_ROWS_REPRESENTATIVES = 0, 1               # EF_THIN_ROWS_*
 INSERT_KEEP = -1   # EF_INSERT_KEEP of include/ef_hip.h
 ROW_NONE = 0xFFFFFFFF
 
@@ -1184,6 +1194,55 @@ class ElasticFusion:
                 e.rc = rc
                 raise
         return (out, new_row, match_row) if rows else out
+
+    # --- thin the map to one surfel per voxel (ef_map_thin / ef_map_thin_select) ---
+    def thinParams(self, **kw) -> ef_thin_params:
+        """ef_default_thin_params (cell = the default query cell, keep = THIN_KEEP_MAX_CONF) with fields replaced by keyword"""
+        p = ef_thin_params()
+        _chk(lib().ef_default_thin_params(self.h, C.byref(p)), self.h)
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise TypeError(f"unknown thin parameter {k}")
+            setattr(p, k, v)
+        return p
+
+    def _thinArgs(self, params, among, kw):
+        if params is None:
+            params = self.thinParams(**kw)
+        else:
+            assert not kw, "give params or keywords, not both"
+        if isinstance(among, dict):
+            among = self.mapSelection(**among)
+        return params, among, (C.byref(among) if among is not None else None)
+
+    def thinSelect(self, params: ef_thin_params | None = None, among=None, representatives: bool = False, max_rows: int | None = None,
+                   count: bool = False, **kw):
+        """the rows a thin with these parameters would remove (or, representatives=True, keep as the one surfel of their cell) in ascending
+        order (uint32), at most max_rows of them (None: all); the map does not change.  among: an ef_map_selection, a dict of mapSelection
+        keywords or None (every surfel participates); other keywords are ef_thin_params fields.  count=True: (rows, total)"""
+        params, among, pa = self._thinArgs(params, among, kw)
+        cap = self.lastCount() if max_rows is None else int(max_rows)
+        rows = np.zeros(max(cap, 1), np.uint32)
+        total = c_u32(0)
+        what = THIN_ROWS_REPRESENTATIVES if representatives else THIN_ROWS_REMOVED
+        _chk(lib().ef_map_thin_select(self.h, C.byref(params), pa, c_i(what), _ptr(rows) if cap else None, c_u32(cap), C.byref(total)), self.h)
+        out = rows[:min(cap, total.value)].copy()
+        return (out, total.value) if count else out
+
+    def thinSelectDevice(self, params: ef_thin_params, among, representatives: bool, rows_dev, max_rows: int, count_dev):
+        """ef_map_thin_select_dev: raw device pointers (int, c_void_p or None for rows with max_rows 0), enqueued on the context's stream"""
+        params, among, pa = self._thinArgs(params, among, {})
+        args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (rows_dev, count_dev)]
+        what = THIN_ROWS_REPRESENTATIVES if representatives else THIN_ROWS_REMOVED
+        _chk(lib().ef_map_thin_select_dev(self.h, C.byref(params), pa, c_i(what), args[0], c_u32(int(max_rows)), args[1]), self.h)
+
+    def thinSurfels(self, params: ef_thin_params | None = None, among=None, **kw) -> dict:
+        """removes every participant that is not the representative of its cell (ef_map_thin: what eraseRows(thinSelect(...)) leaves):
+        {"participants", "cells", "removed", "count_after"}"""
+        params, among, pa = self._thinArgs(params, among, kw)
+        res = ef_thin_result()
+        _chk(lib().ef_map_thin(self.h, C.byref(params), pa, C.byref(res)), self.h)
+        return {"participants": int(res.participants), "cells": int(res.cells), "removed": int(res.removed), "count_after": int(res.count_after)}
 
     def setReferenceDownload(self, on=True):
         """downloadMap / savePly read what GlobalModel::downloadMap reads (the pre-clean buffer, quirk Q14) instead of model()"""

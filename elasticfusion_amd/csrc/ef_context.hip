@@ -272,6 +272,12 @@ struct ef_ctx {
     DevBuf scratch;                        // chunk counts | chunk offsets | 4 words (the total) | one flag byte per record
     size_t rows = 0;
   } ins;
+  // thin (ef_map_thin, ef_map_thin_select; kernels in ef_thin.inc): scratch of its own, sized by the map's rows, grown by the first call, freed
+  // with the context
+  struct ThinState {
+    DevBuf scratch;                        // chunk counts | chunk offsets | 4 words (totals) | participant bytes | representative bytes
+    size_t rows = 0;
+  } thin;
 };
 
 namespace {
@@ -1240,7 +1246,7 @@ void ctx_free(ef_ctx* c) {
   for (auto e : c->ka_stop) (void)hipEventDestroy(e);
   for (auto e : c->ks_start) (void)hipEventDestroy(e);
   for (auto e : c->ks_stop) (void)hipEventDestroy(e);
-  for (DevBuf* b : {&c->stage, &c->render.zbuf, &c->labels.index, &c->query.sorted, &c->query.rows, &c->query.cells, &c->reg.slabs, &c->sel.scratch, &c->ins.scratch})
+  for (DevBuf* b : {&c->stage, &c->render.zbuf, &c->labels.index, &c->query.sorted, &c->query.rows, &c->query.cells, &c->reg.slabs, &c->sel.scratch, &c->ins.scratch, &c->thin.scratch})
     b->release();
   for (int k = 0; k < 2; ++k) {
     if (c->labels.tab[k]) (void)hipFree(c->labels.tab[k]);
@@ -2267,3 +2273,4 @@ int ef_get_splat_timing(ef_ctx* c, ef_kernel_time* out) {
 #include "ef_host_register.inc"
 #include "ef_host_select.inc"
 #include "ef_host_insert.inc"
+#include "ef_host_thin.inc"

@@ -69,7 +69,7 @@ int insert_run(ef_ctx* c, const char* fn, const float* rec_dev, uint32_t n, cons
   res->count_after = n0;
   efm::InsertArgs a{};
   if (p->gate && n) {   // the index of the OLD map, through the query's own path
-    r = query_index(c);
+    r = query_index(c, c->query.cell);
     if (r != EF_OK) return r;
     query_index_args(c, &a.q);
     a.q.max_dist = p->min_separation;

@@ -31,9 +31,10 @@ int query_check(ef_ctx* c, const QueryCall& q) {
   }
   return EF_OK;
 }
-// the index for the current map and cell size: reused while neither has changed, else rebuilt (waits for the device once: the count sizes it)
-int query_index(ef_ctx* c) {
-  if (c->query.gen == c->map_gen && c->query.built_cell == c->query.cell) return EF_OK;
+// the index for the current map at `cell` (the queries pass c->query.cell, a thin its own): reused while neither has changed, else rebuilt
+// (waits for the device once: the count sizes it).  built_cell records what was built, so a caller with another cell rebuilds.
+int query_index(ef_ctx* c, float cell) {
+  if (c->query.gen == c->map_gen && c->query.built_cell == cell) return EF_OK;
   uint32_t n = 0;
   int r = read_count(c, &n);
   if (r != EF_OK) return r;
@@ -51,11 +52,11 @@ int query_index(ef_ctx* c) {
   }
   uint32_t* cells = c->query.cells.as<uint32_t>();
   EF_HIP(c, hipMemsetAsync(cells, 0, (size_t)nb * sizeof(uint32_t), c->stream));
-  efm::query_build(c->maps[c->cur], n, 1.0f / c->query.cell, nb, cells, cells + nb, c->query.sorted.as<float4>(), c->query.rows.as<uint32_t>(), c->stream);
+  efm::query_build(c->maps[c->cur], n, 1.0f / cell, nb, cells, cells + nb, c->query.sorted.as<float4>(), c->query.rows.as<uint32_t>(), c->stream);
   EF_HIP(c, hipGetLastError());
   c->query.nb = nb;
   c->query.n = n;
-  c->query.built_cell = c->query.cell;
+  c->query.built_cell = cell;
   c->query.gen = c->map_gen;
   return EF_OK;
 }
@@ -79,7 +80,7 @@ int query_enqueue(ef_ctx* c, const QueryCall& q) {
     if (r != EF_OK) return r;
   }
   if (!q.n) return EF_OK;
-  r = query_index(c);
+  r = query_index(c, c->query.cell);
   if (r != EF_OK) return r;
   efm::QueryArgs a{};
   query_index_args(c, &a);

@@ -42,7 +42,7 @@ int register_step_run(ef_ctx* c, const RegisterCall& q, const double* T, ef_regi
   memset(out, 0, sizeof(*out));
   out->points = q.n;
   if (!q.n) return EF_OK;
-  int r = query_index(c);
+  int r = query_index(c, c->query.cell);
   if (r != EF_OK) return r;
   const size_t slab_bytes = (size_t)efm::REGISTER_MAX_BLOCKS * efm::REGISTER_SLOTS * sizeof(double);
   r = c->reg.slabs.reserve(c, slab_bytes + efm::REGISTER_SLOTS * sizeof(double), "registration slabs");

@@ -332,4 +332,19 @@ void insert_gate(const InsertArgs& a, const SelectScratch& sc, uint32_t* total, 
 // the flagged records appended to dst at a.count_before in input order (a.chunk_offset = sc.chunk_offset of insert_gate), and new_row
 void insert_scatter(const InsertArgs& a, SurfelSoA dst, hipStream_t s);
 
+// ---- thin the map to one surfel per voxel (ef_thin.inc; ef_map_thin of include/ef_hip.h) ----
+constexpr int THIN_KEEP_MAX_CONF = 0, THIN_KEEP_NEWEST = 1, THIN_KEEP_FIRST = 2;   // EF_THIN_KEEP_*
+struct ThinArgs {
+  QueryArgs q;              // the index built at the thin's cell (sorted, rows, cells, mask, n_sorted, inv_cell) and the live map (NEWEST: col_time)
+  unsigned n;               // rows of the map: the length of the byte arrays below
+  int keep;                 // THIN_KEEP_*
+  const uint8_t* part;      // one byte per row, non-zero = the row passes the selection; null: every row does
+  uint8_t* removed;         // one byte per row, zero on entry: 1 is stored for every removed row; or null
+  uint8_t* rep;             // likewise for every representative; or null
+};
+// one wave per bucket of the index: nothing is launched for an empty index
+void thin_flags(const ThinArgs& a, hipStream_t s);
+// counts, offsets and *total of the rows whose flag differs from `flip` (k_select_count + the scan; n = 0: the scan alone writes 0)
+void thin_count(const SelectScratch& sc, unsigned n, unsigned flip, uint32_t* total, hipStream_t s);
+
 }  // namespace efm

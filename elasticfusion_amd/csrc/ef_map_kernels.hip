@@ -1519,5 +1519,6 @@ void sample_graph(SurfelSoA map, const unsigned* count_dev, int stride, int max_
 #include "ef_register.inc"
 #include "ef_select.inc"
 #include "ef_insert.inc"
+#include "ef_thin.inc"
 
 }  // namespace efm

@@ -756,6 +756,67 @@ int ef_map_insert(ef_ctx* ctx, const float* surfels12, uint32_t n, const double*
 int ef_map_insert_dev(ef_ctx* ctx, const float* surfels12_dev, uint32_t n, const double* T16_or_null, const ef_insert_params* params,
                       ef_insert_result* result, uint32_t* new_row_dev_or_null, uint32_t* match_row_dev_or_null);
 
+/* ---- Thin the map: keep one surfel per voxel of a grid, remove the others (the voxel-grid filter).  Off until first used: no thin call,
+ * nothing allocated, nothing run, and no frame kernel knows of it.
+ *
+ * "Row" and the layout of a surfel are those of the section "Select, extract and erase surfels": position = floats 0 .. 2, confidence = float 3,
+ * time last seen = float 7.  The outcome is a pure function of the map and the arguments: it depends on no order of evaluation and on no sum.
+ *
+ * CELL.  inv_cell = 1.0f / cell, computed once in f32.  Per axis the cell coordinate of a position coordinate v is floor(fl(v * inv_cell)) (the
+ * f32 PRODUCT with inv_cell, not a quotient by cell), clamped to -2^20 .. +2^20: the cell function of the queries' index.  Two surfels share a cell
+ * iff all three coordinates agree.  Everything beyond the clamp (|v * inv_cell| >= 2^20) falls into the boundary cells: such surfels share a cell
+ * however far apart they are, and therefore ONE representative.
+ *
+ * PARTICIPANTS.  With among NULL, every row whose position has three finite coordinates.  With a selection, the rows that are SELECTED by it
+ * (the predicate of ef_map_select, unchanged, EF_SEL_INVERT included) and have a finite position.  A row that does not participate is KEPT: it is
+ * neither a representative nor removed, it beats nobody and counts nowhere.
+ *
+ * REPRESENTATIVE.  The primary of a participant is, by keep:
+ *   EF_THIN_KEEP_MAX_CONF   its confidence (float 3);
+ *   EF_THIN_KEEP_NEWEST     its time last seen (float 7);
+ *   EF_THIN_KEEP_FIRST      a constant.
+ * Primaries are compared as f32 VALUES with two amendments that make the order total: -0 equals +0, and every NaN counts as -infinity (equal to
+ * -infinity and to every other NaN).  Among the participants of one cell the representative is the one with the greatest primary; among equal
+ * primaries the one with the LOWEST row.  Every other participant of the cell is REMOVED.  Hence every cell that holds a participant has exactly
+ * one representative, the outcome of a row depends only on the participants of its own cell, and thinning twice with the same arguments removes
+ * nothing the second time (the representatives are alone in their cells).
+ *
+ * ef_map_thin_select changes nothing.  It writes the rows named by `what`, EF_THIN_ROWS_REMOVED or EF_THIN_ROWS_REPRESENTATIVES, with
+ * ef_map_select's conventions: the first min(max_rows, total) of them in ASCENDING order, *count = total however small max_rows is, rows may be
+ * NULL with max_rows 0, entries past min(max_rows, total) are left as they were.  The removed list is what ef_map_erase_rows takes; the
+ * representatives list is what ef_map_gather takes (a thinned copy of the map then leaves the device while the map stays as it is; kept
+ * non-participants are not in that list).  The _dev variant takes DEVICE pointers for rows and count and only enqueues on the context's stream,
+ * except for what the selection needs (ID numbering, label alignment, the count after a call that can change the map) and except that it waits
+ * for the device once when the index has to be rebuilt (the map changed, or the index was last built at another cell).
+ *
+ * ef_map_thin removes the removed rows and leaves everything exactly as ef_map_erase_rows(the removed list) would: see "What an erase leaves
+ * behind" above (the map, the context, the index, IDs, labels, the shadow buffer), with the same two synchronisations.  result (HOST memory):
+ * cells = the number of representatives, removed, participants = cells + removed, count_after = the map count the call leaves.
+ *
+ * The index of the queries is built at the thin's cell where needed; a later query at another cell (ef_set_query_cell's) rebuilds it, as after
+ * ef_set_query_cell.  No query result changes.  There is no limit on the cell's size: no box of cells is walked.
+ *
+ * EF_EINVAL, before any GPU work (the arguments are checked before the context, so with a NULL context ef_last_error(NULL) names what is wrong
+ * with them): a NULL context, params, result or count; a cell that is not finite and positive or whose 1 / cell is not finite
+ * (ef_set_query_cell's rule); keep or what outside their values; with among given, everything ef_map_select refuses for a selection;
+ * max_rows > 0 with NULL rows.
+ * EF_ESTATE: the context's stream is being captured; with among given, what ef_map_select answers with EF_ESTATE.  ef_map_thin only: a context
+ * created with close_loops = 1 (the erase's reason; the map is unchanged); ef_map_thin_select works on such contexts. */
+#define EF_THIN_KEEP_MAX_CONF 0   /* primary = confidence (pos_conf.w)            */
+#define EF_THIN_KEEP_NEWEST   1   /* primary = last-seen time (col_time.w)        */
+#define EF_THIN_KEEP_FIRST    2   /* primary = a constant: the lowest row wins    */
+#define EF_THIN_ROWS_REMOVED         0
+#define EF_THIN_ROWS_REPRESENTATIVES 1
+typedef struct ef_thin_params { float cell; int keep; } ef_thin_params;
+typedef struct ef_thin_result { uint32_t participants, cells, removed, count_after; } ef_thin_result;
+/* cell = EF_QUERY_DEFAULT_CELL, keep = EF_THIN_KEEP_MAX_CONF */
+int ef_default_thin_params(ef_ctx* ctx, ef_thin_params* params);
+int ef_map_thin_select(ef_ctx* ctx, const ef_thin_params* params, const ef_map_selection* among_or_null, int what, uint32_t* rows,
+                       uint32_t max_rows, uint32_t* count);
+int ef_map_thin_select_dev(ef_ctx* ctx, const ef_thin_params* params, const ef_map_selection* among_or_null, int what, uint32_t* rows_dev,
+                           uint32_t max_rows, uint32_t* count_dev);
+int ef_map_thin(ef_ctx* ctx, const ef_thin_params* params, const ef_map_selection* among_or_null, ef_thin_result* result);
+
 /* named internal images, copied to HOST (synchronises); for tests and for a front-end's drawing code */
 enum ef_image {
   EF_IMG_DEPTH_FILTERED = 0,      /* u16  */
