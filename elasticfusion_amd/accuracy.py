@@ -72,16 +72,21 @@ def register_to_map(ef: "api.ElasticFusion", surfels_or_points: np.ndarray, T_in
     return T, stages
 
 
-def merge_session(ef: "api.ElasticFusion", surfels: np.ndarray, T_init=None, register: dict | None = None, rows: bool = False, **insert) -> tuple:
+def merge_session(ef: "api.ElasticFusion", surfels: np.ndarray, T_init=None, register: dict | None = None, rows: bool = False, fuse: bool = False,
+                  **insert) -> tuple:
     """Continues ef's map with the surfels of another session ([m, 12] as downloadMap() gives them, in their own frame): register_to_map on
     their positions and normals from T_init (keywords in `register`), then insertSurfels with the pose found (ef_map_insert: the records
     the map does not already hold within min_separation are appended; other keywords are ef_insert_params fields).  A registration whose last
     stage ended TOO_FEW_PAIRS or DEGENERATE inserts nothing.  Returns (T 4 x 4 float64, [per-stage registration results], the insert
-    result or None) — with rows=True the insert result is insertSurfels' (result, new_row, match_row)."""
+    result or None) — with rows=True the insert result is insertSurfels' (result, new_row, match_row).  fuse=True: fuseSurfels(append=1) in
+    insertSurfels' place (ef_map_fuse: the records the map does hold are merged into the surfels they match instead of being thrown away, so
+    confidences rise where both sessions saw the surface; keywords are ef_fuse_params fields, the result is fuseSurfels')."""
     rec = np.ascontiguousarray(surfels, np.float32).reshape(-1, 12)
     T, stages = register_to_map(ef, rec, T_init=T_init, **(register or {}))
     if not stages or stages[-1]["status"] in (api.REG_TOO_FEW_PAIRS, api.REG_DEGENERATE):
         return T, stages, None
+    if fuse:
+        return T, stages, ef.fuseSurfels(rec, T=T, rows=rows, **dict(insert, append=1))
     return T, stages, ef.insertSurfels(rec, T=T, rows=rows, **insert)
 
 

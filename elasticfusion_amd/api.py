@@ -80,6 +80,15 @@ class ef_insert_result(C.Structure):
     _fields_ = [("inserted", c_u32), ("duplicates", c_u32), ("skipped", c_u32), ("count_after", c_u32)]
 
 
+class ef_fuse_params(C.Structure):
+    _fields_ = [("min_separation", c_f), ("min_conf", c_f), ("min_normal_cos", c_f), ("append", c_i), ("init_time", c_i), ("last_time", c_i)]
+
+
+class ef_fuse_result(C.Structure):
+    _fields_ = [("fused", c_u32), ("absorbed", c_u32), ("weightless", c_u32), ("novel", c_u32), ("skipped", c_u32), ("inserted", c_u32),
+                ("count_after", c_u32)]
+
+
 class ef_thin_params(C.Structure):
     _fields_ = [("cell", c_f), ("keep", c_i)]
 
@@ -91,6 +100,7 @@ class ef_thin_result(C.Structure):
 THIN_KEEP_MAX_CONF, THIN_KEEP_NEWEST, THIN_KEEP_FIRST = 0, 1, 2   # EF_THIN_KEEP_* of include/ef_hip.h
 THIN_ROWS_REMOVED, THIN_ROWS_REPRESENTATIVES = 0, 1               # EF_THIN_ROWS_*
 INSERT_KEEP = -1   # EF_INSERT_KEEP of include/ef_hip.h
+FUSE_SKIPPED, FUSE_NOVEL, FUSE_WEIGHTLESS, FUSE_ABSORBED, FUSE_FUSED, FUSE_INSERTED = 0, 1, 2, 3, 4, 5   # EF_FUSE_*: a record's outcome byte
 ROW_NONE = 0xFFFFFFFF
 
 # EF_SEL_* of include/ef_hip.h
@@ -1194,6 +1204,61 @@ class ElasticFusion:
                 e.rc = rc
                 raise
         return (out, new_row, match_row) if rows else out
+
+    # --- fuse surfels into the map (ef_map_fuse) ---
+    def fuseParams(self, **kw) -> ef_fuse_params:
+        """ef_default_fuse_params (the insert's defaults: min_separation 0.01, min_conf -1, min_normal_cos 0.5, both times the tick; append 1)
+        with fields replaced by keyword"""
+        p = ef_fuse_params()
+        _chk(lib().ef_default_fuse_params(self.h, C.byref(p)), self.h)
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise TypeError(f"unknown fuse parameter {k}")
+            setattr(p, k, v)
+        return p
+
+    def fuseSurfels(self, surfels, T=None, params: ef_fuse_params | None = None, rows: bool = False, n: int | None = None, **kw):
+        """merges the records (n x 12 float32 in downloadMap()'s layout, or a DevBuf holding n of them: ef_map_fuse_dev) moved by T (4 x 4,
+        records -> world; None: copied) into the map surfels they match, at most one record per surfel, and with append=1 appends those that
+        match nothing as insertSurfels would: {"fused", "absorbed", "weightless", "novel", "skipped", "inserted", "count_after"}; rows=True:
+        (result, new_row, match_row, outcome), uint32 per record with api.ROW_NONE where there is none and one api.FUSE_* byte per record.
+        A refused fuse (EF_ECAPACITY: nothing changed) raises EFError with the counts in its .result"""
+        if params is None:
+            params = self.fuseParams(**kw)
+        else:
+            assert not kw, "give params or keywords, not both"
+        keep, pT = _pose16(T)
+        res = ef_fuse_result()
+        if isinstance(surfels, DevBuf):
+            n = surfels.nbytes // 48 if n is None else int(n)
+            assert n * 48 <= surfels.nbytes, (n, surfels.nbytes)
+            new_dev = DevBuf(max(n, 1) * 4) if rows else None
+            match_dev = DevBuf(max(n, 1) * 4) if rows else None
+            out_dev = DevBuf(max(n, 1)) if rows else None
+            rc = lib().ef_map_fuse_dev(self.h, surfels.p if n else None, c_u32(n), pT, C.byref(params), C.byref(res),
+                                       new_dev.p if rows else None, match_dev.p if rows else None, out_dev.p if rows else None)
+            new_row = new_dev.to_array(np.uint32, (n,)) if rows and rc == 0 else None
+            match_row = match_dev.to_array(np.uint32, (n,)) if rows and rc == 0 else None
+            outcome = out_dev.to_array(np.uint8, (n,)) if rows and rc == 0 else None
+        else:
+            rec = np.ascontiguousarray(surfels, np.float32).reshape(-1, 12)
+            n = len(rec)
+            new_row = np.full(max(n, 1), ROW_NONE, np.uint32) if rows else None
+            match_row = np.full(max(n, 1), ROW_NONE, np.uint32) if rows else None
+            outcome = np.zeros(max(n, 1), np.uint8) if rows else None
+            rc = lib().ef_map_fuse(self.h, _ptr(rec) if n else None, c_u32(n), pT, C.byref(params), C.byref(res),
+                                   _ptr(new_row) if rows else None, _ptr(match_row) if rows else None, _ptr(outcome) if rows else None)
+            if rows:
+                new_row, match_row, outcome = new_row[:n], match_row[:n], outcome[:n]
+        out = {k: int(getattr(res, k)) for k, _ in ef_fuse_result._fields_}
+        if rc != 0:
+            try:
+                _chk(rc, self.h)
+            except EFError as e:
+                e.result = out
+                e.rc = rc
+                raise
+        return (out, new_row, match_row, outcome) if rows else out
 
     # --- thin the map to one surfel per voxel (ef_map_thin / ef_map_thin_select) ---
     def thinParams(self, **kw) -> ef_thin_params:

@@ -278,6 +278,11 @@ struct ef_ctx {
     DevBuf scratch;                        // chunk counts | chunk offsets | 4 words (totals) | participant bytes | representative bytes
     size_t rows = 0;
   } thin;
+  // fuse (ef_map_fuse; kernels in ef_fuse.inc) beside the insert's scratch, which its gate and append use: the election's keys (one per map row),
+  // match_row and the outcome bytes (one each per record), and the two counts' words.  Grown by the first call, freed with the context
+  struct FuseState {
+    DevBuf scratch;
+  } fuse;
 };
 
 namespace {
@@ -1246,7 +1251,7 @@ void ctx_free(ef_ctx* c) {
   for (auto e : c->ka_stop) (void)hipEventDestroy(e);
   for (auto e : c->ks_start) (void)hipEventDestroy(e);
   for (auto e : c->ks_stop) (void)hipEventDestroy(e);
-  for (DevBuf* b : {&c->stage, &c->render.zbuf, &c->labels.index, &c->query.sorted, &c->query.rows, &c->query.cells, &c->reg.slabs, &c->sel.scratch, &c->ins.scratch, &c->thin.scratch})
+  for (DevBuf* b : {&c->stage, &c->render.zbuf, &c->labels.index, &c->query.sorted, &c->query.rows, &c->query.cells, &c->reg.slabs, &c->sel.scratch, &c->ins.scratch, &c->thin.scratch, &c->fuse.scratch})
     b->release();
   for (int k = 0; k < 2; ++k) {
     if (c->labels.tab[k]) (void)hipFree(c->labels.tab[k]);
@@ -2274,3 +2279,4 @@ int ef_get_splat_timing(ef_ctx* c, ef_kernel_time* out) {
 #include "ef_host_select.inc"
 #include "ef_host_insert.inc"
 #include "ef_host_thin.inc"
+#include "ef_host_fuse.inc"

@@ -347,4 +347,21 @@ void thin_flags(const ThinArgs& a, hipStream_t s);
 // counts, offsets and *total of the rows whose flag differs from `flip` (k_select_count + the scan; n = 0: the scan alone writes 0)
 void thin_count(const SelectScratch& sc, unsigned n, unsigned flip, uint32_t* total, hipStream_t s);
 
+// ---- fuse surfels into the map (ef_fuse.inc; ef_map_fuse of include/ef_hip.h) ----
+constexpr unsigned long long FUSE_KEY_EMPTY = 0xFFFFFFFFFFFFFFFFull;
+constexpr unsigned FUSE_SKIPPED = 0, FUSE_NOVEL = 1, FUSE_WEIGHTLESS = 2, FUSE_ABSORBED = 3, FUSE_FUSED = 4, FUSE_INSERTED = 5;   // EF_FUSE_*
+struct MapFuseArgs {
+  InsertArgs ins;           // what insert_gate was given and wrote: rec, n, the transform, last_time, count_before (= the rows of the old map),
+                            // q.map (the live map), flags, dup and match_row (never null here)
+  unsigned long long* key;  // one per row of the old map, FUSE_KEY_EMPTY before the election: (d2 bits << 32) | record index of the row's winner
+  int append;
+  uint8_t* outcome;         // one byte per record (never null here): FUSE_*
+};
+// the election: key[s] = the minimum over the competitors of row s
+void fuse_pick(const MapFuseArgs& a, hipStream_t s);
+// outcome[] of every record; nothing else is written
+void fuse_outcome(const MapFuseArgs& a, hipStream_t s);
+// the records whose outcome is FUSE_FUSED merged into their rows, in place
+void fuse_apply(const MapFuseArgs& a, hipStream_t s);
+
 }  // namespace efm

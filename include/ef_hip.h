@@ -756,6 +756,91 @@ int ef_map_insert(ef_ctx* ctx, const float* surfels12, uint32_t n, const double*
 int ef_map_insert_dev(ef_ctx* ctx, const float* surfels12_dev, uint32_t n, const double* T16_or_null, const ef_insert_params* params,
                       ef_insert_result* result, uint32_t* new_row_dev_or_null, uint32_t* match_row_dev_or_null);
 
+/* ---- Fuse surfels: transform a set of records, merge those that match a map surfel INTO that surfel (at most one record per surfel and
+ * call), optionally append the others.  What ef_map_insert throws away as a duplicate improves the map here: confidence rises, position, normal,
+ * radius and colour are averaged, as a frame's fusion does for a measurement.  Off until first used: no fuse call, nothing allocated, nothing
+ * run, and no frame kernel knows of it.
+ *
+ * Records, T, the TRANSFORM (p', m') and the arithmetic rules are those of "Insert surfels" above: f32, one rounding per operation, no
+ * contraction, in the written order; comparisons with NaN are false.  The outcome is a pure function of (map, records, T, params): it depends on
+ * no order of evaluation and on no sum.
+ *
+ * 1. MATCH.  Exactly the insert's gate, which is always on: s = the row ef_query_nearest returns for p' with max_dist = min_separation and this
+ * min_conf, on the map AS IT STANDS BEFORE THE CALL.  The record is MATCHED iff s is a hit and (min_normal_cos <= -1 or
+ * ((m'x*nsx + m'y*nsy) + m'z*nsz) >= min_normal_cos), ns the stored normal of s.  A record that is not matched is SKIPPED if p' has a non-finite
+ * coordinate and NOVEL otherwise.  Records never match one another.  match_row[i] = s for a matched record, 0xFFFFFFFF otherwise.
+ *
+ * 2. ELECTION.  A matched record COMPETES iff its confidence a (float 3) satisfies a > 0 && a < +infinity; a matched record that does not (zero,
+ * negative, infinite, NaN) is WEIGHTLESS: counted, and nothing else.  Among the competitors of one map row s the winner is the minimum of
+ * (d2, record index): d2 = ((dx*dx + dy*dy) + dz*dz) with dx = p'x - psx and so on, ps the stored position of s (the query's own f32
+ * expression; finite and non-negative, so comparing the floats is comparing their bits), and among equal d2 the LOWEST index.  The winner is
+ * FUSED; every other competitor of that row is ABSORBED: counted, and nothing else.  So a surfel takes at most one record per call, and which one
+ * depends on the records' order only through the tie-break.
+ *
+ * 3. MERGE of the FUSED record into row s, in place.  c_k = the stored confidence, (px, py, pz), colour, (nx, ny, nz), radius_s the stored
+ * row; a, colour_rec, radius_rec the record's floats 3, 4, 11; p', m' the MOVED position and normal.  With avg(old, new) =
+ * ((c_k*old) + (a*new)) / (c_k + a):
+ *   if radius_rec < (1.0f + 0.5f) * radius_s:
+ *     position  each coordinate = avg(stored, p');                    confidence = c_k + a;
+ *     normal    v = (avg(nx, m'x), avg(ny, m'y), avg(nz, m'z)), dot = (vz*vz) + ((vy*vy) + (vx*vx)), rn = 1.0f / sqrtf(dot), stored normal =
+ *               (vx*rn, vy*rn, vz*rn);                                radius = avg(radius_s, radius_rec);
+ *     colour    a colour float c decodes to three channels: ic = (int)c (toward zero; the device's conversion where c is outside int: saturated,
+ *               NaN gives 0), channel = (float)((ic >> 16) & 0xFF) / 255.0f, likewise >> 8 and >> 0.  Per channel mean = avg(stored channel,
+ *               record channel), q = roundf(mean * 255.0f) (half AWAY from zero), u = (unsigned)(int)q if -2^31 <= q < 2^31, else 0x80000000 (NaN
+ *               included).  rgb = (((ur << 8) + ug) << 8) + ub in 32-bit unsigned arithmetic; the stored colour = (float)(int)rgb;
+ *   else only the confidence (c_k + a) changes;
+ *   in both cases float 7 (time last seen) = (float)last_time, or the record's own float 7 under EF_INSERT_KEEP.
+ * (The update pass of a frame's fusion, on the record instead of a measurement.)  The ID lane and the creation time (floats 5, 6) are never
+ * written: the surfel keeps its stable ID, and its label row still follows it.  A surfel with c_k + a == 0 or a non-finite sum gets what the
+ * expressions give.
+ *
+ * 4. APPEND.  With append = 1 the NOVEL records are appended in input order: the rows, new_row and count are bit for bit what ef_map_insert with
+ * gate = 1 and the same min_separation, min_conf, min_normal_cos, init_time, last_time would append to the old map.  With append = 0 they are
+ * only counted, and every new_row is 0xFFFFFFFF.
+ *
+ * OUTCOME per record i (new_row, match_row: n words each, outcome: n bytes; each may be NULL): outcome[i] is one of the EF_FUSE_* values below;
+ * a NOVEL record reads EF_FUSE_INSERTED when append = 1, EF_FUSE_NOVEL when append = 0.  result (HOST memory in both variants): fused + absorbed
+ * + weightless = the matched records, novel, skipped (the five add up to n), inserted = novel if append else 0, count_after = the map count the
+ * call leaves.
+ *
+ * What a fuse leaves behind: the map as described (rows that are nobody's match_row keep every bit; so do the rows of ABSORBED-only and
+ * WEIGHTLESS-only matches), and everything else as "What an insert leaves behind" says with "old rows ++ inserted rows" read as "the fused old
+ * rows ++ appended rows": IDs (numbered before the call's edits; appended rows are numbered by the next ID-consuming call), the context (the
+ * prediction is renewed from the edited map), the index (stale), labels (old rows keep their floats, appended rows get the prior), the shadow
+ * buffer.  A call that fuses and appends nothing (n = 0, an empty map with append = 0) is valid and still leaves that state.
+ *
+ * CAPACITY.  Every count is known before anything is written.  If append = 1 and count_before + novel > max_surfels the call returns
+ * EF_ECAPACITY and NOTHING has changed, fused rows included: map, count, prediction, the index's validity.  result carries all the counts (those
+ * the call would have had), with inserted = novel and count_after = count_before; nothing is promised about the three arrays.
+ *
+ * Defaults (ef_default_fuse_params): the insert's (min_separation 0.01 m, min_conf -1, min_normal_cos 0.5, both times the tick), append = 1.
+ *
+ * Both variants synchronise before and after.  ef_map_fuse stages its arrays; ef_map_fuse_dev takes DEVICE pointers for the records and the
+ * three arrays; surfels12_dev must be 16-byte aligned and must not lie inside the map.
+ *
+ * EF_EINVAL, before any GPU work: everything ef_map_insert refuses with gate = 1 (NULL context, params or result; n > 0 with NULL records; n above
+ * EF_INSERT_MAX_RECORDS; a non-finite entry of T; a time below EF_INSERT_KEEP; min_separation, min_conf, the ratio to the query cell; a NaN
+ * min_normal_cos; surfels12_dev not 16-byte aligned), and append outside 0 / 1.
+ * EF_ESTATE: as ef_map_insert (a captured stream; a context created with close_loops = 1; a refused ID lane). */
+#define EF_FUSE_SKIPPED    0
+#define EF_FUSE_NOVEL      1
+#define EF_FUSE_WEIGHTLESS 2
+#define EF_FUSE_ABSORBED   3
+#define EF_FUSE_FUSED      4
+#define EF_FUSE_INSERTED   5
+typedef struct ef_fuse_params {
+  float min_separation, min_conf, min_normal_cos;  /* the match: exactly ef_insert_params' gate (the gate is always on) */
+  int   append;      /* 1: records that match nothing are appended exactly as ef_map_insert would; 0: they are only counted */
+  int   init_time;   /* of appended rows, as ef_insert_params */
+  int   last_time;   /* of appended rows AND of fused surfels; EF_INSERT_KEEP: the record's own float 7 */
+} ef_fuse_params;
+typedef struct ef_fuse_result { uint32_t fused, absorbed, weightless, novel, skipped, inserted, count_after; } ef_fuse_result;
+int ef_default_fuse_params(ef_ctx* ctx, ef_fuse_params* params);
+int ef_map_fuse(ef_ctx* ctx, const float* surfels12, uint32_t n, const double* T16_or_null, const ef_fuse_params* params, ef_fuse_result* result,
+                uint32_t* new_row_or_null, uint32_t* match_row_or_null, uint8_t* outcome_or_null);
+int ef_map_fuse_dev(ef_ctx* ctx, const float* surfels12_dev, uint32_t n, const double* T16_or_null, const ef_fuse_params* params,
+                    ef_fuse_result* result, uint32_t* new_row_dev_or_null, uint32_t* match_row_dev_or_null, uint8_t* outcome_dev_or_null);
+
 /* ---- Thin the map: keep one surfel per voxel of a grid, remove the others (the voxel-grid filter).  Off until first used: no thin call,
  * nothing allocated, nothing run, and no frame kernel knows of it.
  *
