@@ -994,11 +994,15 @@ class ElasticFusion:
     # --- rigid registration of a point set against the map (ef_register_step / ef_register_cloud) ---
     def registerParams(self, **kw) -> ef_register_params:
         """ef_default_register_params with fields replaced by keyword"""
-        p = ef_register_params()
-        _chk(lib().ef_default_register_params(self.h, C.byref(p)), self.h)
+        return self._params(ef_register_params, lib().ef_default_register_params, kw, "registration")
+
+    def _params(self, struct_type, default_fn, kw, what):
+        """the library's defaults (default_fn fills a struct_type) with fields replaced by keyword"""
+        p = struct_type()
+        _chk(default_fn(self.h, C.byref(p)), self.h)
         for k, v in kw.items():
             if not hasattr(p, k):
-                raise TypeError(f"unknown registration parameter {k}")
+                raise TypeError(f"unknown {what} parameter {k}")
             setattr(p, k, v)
         return p
 
@@ -1158,13 +1162,7 @@ class ElasticFusion:
     def insertParams(self, **kw) -> ef_insert_params:
         """ef_default_insert_params (gate 1, min_separation 0.01, min_conf -1, min_normal_cos 0.5, both times the tick) with fields replaced
         by keyword"""
-        p = ef_insert_params()
-        _chk(lib().ef_default_insert_params(self.h, C.byref(p)), self.h)
-        for k, v in kw.items():
-            if not hasattr(p, k):
-                raise TypeError(f"unknown insert parameter {k}")
-            setattr(p, k, v)
-        return p
+        return self._params(ef_insert_params, lib().ef_default_insert_params, kw, "insert")
 
     def insertSurfels(self, surfels, T=None, params: ef_insert_params | None = None, rows: bool = False, n: int | None = None, **kw):
         """appends the records (n x 12 float32 in downloadMap()'s layout, or a DevBuf holding n of them: ef_map_insert_dev) moved by T (4 x 4,
@@ -1175,27 +1173,28 @@ class ElasticFusion:
             params = self.insertParams(**kw)
         else:
             assert not kw, "give params or keywords, not both"
+        return self._appendSurfels(lib().ef_map_insert, lib().ef_map_insert_dev, params, ef_insert_result, False, surfels, T, rows, n)
+
+    def _appendSurfels(self, fn_host, fn_dev, params, result_type, with_outcome, surfels, T, rows, n):
+        """insertSurfels / fuseSurfels behind their parameters: the host or the DevBuf tier by the type of surfels, one uint32 array per record
+        for new_row and match_row and (with_outcome) one byte for the outcome when rows is set, the result struct as a dict"""
         keep, pT = _pose16(T)
-        res = ef_insert_result()
+        res = result_type()
+        kinds = [(np.uint32, ROW_NONE), (np.uint32, ROW_NONE)] + ([(np.uint8, 0)] if with_outcome else [])
         if isinstance(surfels, DevBuf):
             n = surfels.nbytes // 48 if n is None else int(n)
             assert n * 48 <= surfels.nbytes, (n, surfels.nbytes)
-            new_dev = DevBuf(max(n, 1) * 4) if rows else None
-            match_dev = DevBuf(max(n, 1) * 4) if rows else None
-            rc = lib().ef_map_insert_dev(self.h, surfels.p if n else None, c_u32(n), pT, C.byref(params), C.byref(res),
-                                         new_dev.p if rows else None, match_dev.p if rows else None)
-            new_row = new_dev.to_array(np.uint32, (n,)) if rows and rc == 0 else None
-            match_row = match_dev.to_array(np.uint32, (n,)) if rows and rc == 0 else None
+            devs = [DevBuf(max(n, 1) * np.dtype(t).itemsize) for t, _ in kinds] if rows else [None] * len(kinds)
+            rc = fn_dev(self.h, surfels.p if n else None, c_u32(n), pT, C.byref(params), C.byref(res), *[d.p if rows else None for d in devs])
+            arrays = [d.to_array(t, (n,)) if rows and rc == 0 else None for d, (t, _) in zip(devs, kinds)]
         else:
             rec = np.ascontiguousarray(surfels, np.float32).reshape(-1, 12)
             n = len(rec)
-            new_row = np.full(max(n, 1), ROW_NONE, np.uint32) if rows else None
-            match_row = np.full(max(n, 1), ROW_NONE, np.uint32) if rows else None
-            rc = lib().ef_map_insert(self.h, _ptr(rec) if n else None, c_u32(n), pT, C.byref(params), C.byref(res),
-                                     _ptr(new_row) if rows else None, _ptr(match_row) if rows else None)
+            arrays = [np.full(max(n, 1), fill, t) if rows else None for t, fill in kinds]
+            rc = fn_host(self.h, _ptr(rec) if n else None, c_u32(n), pT, C.byref(params), C.byref(res), *[_ptr(a) if rows else None for a in arrays])
             if rows:
-                new_row, match_row = new_row[:n], match_row[:n]
-        out = {"inserted": int(res.inserted), "duplicates": int(res.duplicates), "skipped": int(res.skipped), "count_after": int(res.count_after)}
+                arrays = [a[:n] for a in arrays]
+        out = {k: int(getattr(res, k)) for k, _ in result_type._fields_}
         if rc != 0:
             try:
                 _chk(rc, self.h)
@@ -1203,19 +1202,13 @@ class ElasticFusion:
                 e.result = out
                 e.rc = rc
                 raise
-        return (out, new_row, match_row) if rows else out
+        return (out, *arrays) if rows else out
 
     # --- fuse surfels into the map (ef_map_fuse) ---
     def fuseParams(self, **kw) -> ef_fuse_params:
         """ef_default_fuse_params (the insert's defaults: min_separation 0.01, min_conf -1, min_normal_cos 0.5, both times the tick; append 1)
         with fields replaced by keyword"""
-        p = ef_fuse_params()
-        _chk(lib().ef_default_fuse_params(self.h, C.byref(p)), self.h)
-        for k, v in kw.items():
-            if not hasattr(p, k):
-                raise TypeError(f"unknown fuse parameter {k}")
-            setattr(p, k, v)
-        return p
+        return self._params(ef_fuse_params, lib().ef_default_fuse_params, kw, "fuse")
 
     def fuseSurfels(self, surfels, T=None, params: ef_fuse_params | None = None, rows: bool = False, n: int | None = None, **kw):
         """merges the records (n x 12 float32 in downloadMap()'s layout, or a DevBuf holding n of them: ef_map_fuse_dev) moved by T (4 x 4,
@@ -1227,49 +1220,12 @@ class ElasticFusion:
             params = self.fuseParams(**kw)
         else:
             assert not kw, "give params or keywords, not both"
-        keep, pT = _pose16(T)
-        res = ef_fuse_result()
-        if isinstance(surfels, DevBuf):
-            n = surfels.nbytes // 48 if n is None else int(n)
-            assert n * 48 <= surfels.nbytes, (n, surfels.nbytes)
-            new_dev = DevBuf(max(n, 1) * 4) if rows else None
-            match_dev = DevBuf(max(n, 1) * 4) if rows else None
-            out_dev = DevBuf(max(n, 1)) if rows else None
-            rc = lib().ef_map_fuse_dev(self.h, surfels.p if n else None, c_u32(n), pT, C.byref(params), C.byref(res),
-                                       new_dev.p if rows else None, match_dev.p if rows else None, out_dev.p if rows else None)
-            new_row = new_dev.to_array(np.uint32, (n,)) if rows and rc == 0 else None
-            match_row = match_dev.to_array(np.uint32, (n,)) if rows and rc == 0 else None
-            outcome = out_dev.to_array(np.uint8, (n,)) if rows and rc == 0 else None
-        else:
-            rec = np.ascontiguousarray(surfels, np.float32).reshape(-1, 12)
-            n = len(rec)
-            new_row = np.full(max(n, 1), ROW_NONE, np.uint32) if rows else None
-            match_row = np.full(max(n, 1), ROW_NONE, np.uint32) if rows else None
-            outcome = np.zeros(max(n, 1), np.uint8) if rows else None
-            rc = lib().ef_map_fuse(self.h, _ptr(rec) if n else None, c_u32(n), pT, C.byref(params), C.byref(res),
-                                   _ptr(new_row) if rows else None, _ptr(match_row) if rows else None, _ptr(outcome) if rows else None)
-            if rows:
-                new_row, match_row, outcome = new_row[:n], match_row[:n], outcome[:n]
-        out = {k: int(getattr(res, k)) for k, _ in ef_fuse_result._fields_}
-        if rc != 0:
-            try:
-                _chk(rc, self.h)
-            except EFError as e:
-                e.result = out
-                e.rc = rc
-                raise
-        return (out, new_row, match_row, outcome) if rows else out
+        return self._appendSurfels(lib().ef_map_fuse, lib().ef_map_fuse_dev, params, ef_fuse_result, True, surfels, T, rows, n)
 
     # --- thin the map to one surfel per voxel (ef_map_thin / ef_map_thin_select) ---
     def thinParams(self, **kw) -> ef_thin_params:
         """ef_default_thin_params (cell = the default query cell, keep = THIN_KEEP_MAX_CONF) with fields replaced by keyword"""
-        p = ef_thin_params()
-        _chk(lib().ef_default_thin_params(self.h, C.byref(p)), self.h)
-        for k, v in kw.items():
-            if not hasattr(p, k):
-                raise TypeError(f"unknown thin parameter {k}")
-            setattr(p, k, v)
-        return p
+        return self._params(ef_thin_params, lib().ef_default_thin_params, kw, "thin")
 
     def _thinArgs(self, params, among, kw):
         if params is None:

@@ -43,6 +43,29 @@ struct DevBuf {
   template <class T>
   T* as() const { return (T*)p; }
 };
+// Hands out consecutive sub-ranges of a DevBuf from its base on, each aligned to `align` bytes (a power of two; hipMalloc's base is aligned far
+// beyond any used here).  It checks no size: the caller has reserved what it carves.
+struct Carver {
+  uint8_t* at;
+  explicit Carver(const DevBuf& b) : at(b.p) {}
+  template <class T>
+  T* take(size_t count, size_t align = alignof(T)) {
+    at = (uint8_t*)(((uintptr_t)at + align - 1) & ~(uintptr_t)(align - 1));
+    T* r = (T*)at;
+    at += count * sizeof(T);
+    return r;
+  }
+  // {chunk counts | chunk offsets | 4 words} of a SelectScratch for `rows` rows; returns the 4 words (the scan's total).  The flag bytes are
+  // the caller's to place: several sets may share them, or share these words.
+  static size_t chunks(size_t rows) { return (size_t)efm::select_chunks((unsigned)rows) + 1; }
+  static size_t scan_bytes(size_t rows) { return (2 * chunks(rows) + 4) * sizeof(uint32_t); }
+  uint32_t* scan_words(size_t rows, efm::SelectScratch* sc, size_t align = alignof(uint32_t)) {
+    const size_t k = chunks(rows);
+    sc->chunk_count = take<uint32_t>(k, align);
+    sc->chunk_offset = take<uint32_t>(k);
+    return take<uint32_t>(4);
+  }
+};
 
 }  // namespace
 
@@ -279,7 +302,8 @@ struct ef_ctx {
     size_t rows = 0;
   } thin;
   // fuse (ef_map_fuse; kernels in ef_fuse.inc) beside the insert's scratch, which its gate and append use: the election's keys (one per map row),
-  // match_row and the outcome bytes (one each per record), and the two counts' words.  Grown by the first call, freed with the context
+  // match_row and the outcome bytes (one each per record), and the two counts' words (FuseScratch / fuse_scratch in ef_host_insert.inc, beside
+  // append_run, which carves it).  Grown by the first call, freed with the context
   struct FuseState {
     DevBuf scratch;
   } fuse;
@@ -1282,6 +1306,13 @@ void pose_mats(const double* T16, float* Tcw_host, float* pose_host) {
   const efl::SE3 T = efl::se3_from_matrix(T16);
   efl::se3_inverse_matrix_f(T, Tcw_host);
   efl::se3_castf_matrix(T, pose_host);
+}
+// T (row-major 4 x 4 doubles) as the f32 rotation and translation the map kernels take: every entry rounded once
+void pose_Rt(const double* T, float* R, float* t) {
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) R[i * 3 + j] = (float)T[i * 4 + j];
+    t[i] = (float)T[i * 4 + 3];
+  }
 }
 bool finite16(const double* T) {
   for (int i = 0; i < 16; ++i)

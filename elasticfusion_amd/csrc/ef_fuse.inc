@@ -1,6 +1,6 @@
 // Fuse surfels into the map (ef_map_fuse, include/ef_hip.h; DESIGN.md §8g).  Included at the end of ef_map_kernels.hip, after ef_insert.inc, whose
-// gate (k_insert_gate: the match), transform (insert_move_pos / insert_move_nrm) and scatter (the append) it uses unchanged, and after
-// ef_thin.inc, whose thin_count (k_select_count + k_scan_chunks) counts the outcome bytes.  No frame kernel reads or writes anything here.
+// gate (k_insert_gate: the match), transform (insert_move_pos / insert_move_nrm) and scatter (the append) it uses unchanged; the selection's
+// flags_count (ef_select.inc: k_select_count + k_scan_chunks) counts the outcome bytes.  No frame kernel reads or writes anything here.
 //   pick      k_fuse_pick: one lane per record.  A matched record whose confidence competes forms the query's d2 against the stored position of
 //             its row and takes part in the election: atomicMin on key[row] of (d2 bits << 32) | record index, the z-buffer's idiom.  d2 is
 //             finite and non-negative, so its bits order as the floats do; the minimum of a set does not depend on the order of the atomics.

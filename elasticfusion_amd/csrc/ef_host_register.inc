@@ -59,10 +59,7 @@ int register_step_run(ef_ctx* c, const RegisterCall& q, const double* T, ef_regi
   a.q.row = q.row;
   a.q.plane = q.plane;
   a.normals = q.normals;
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) a.R[i * 3 + j] = (float)T[i * 4 + j];
-    a.t[i] = (float)T[i * 4 + 3];
-  }
+  pose_Rt(T, a.R, a.t);
   a.min_normal_cos = q.p->min_normal_cos;
   a.gate = q.normals && q.p->min_normal_cos > -1.0f;
   a.slabs = c->reg.slabs.as<double>();

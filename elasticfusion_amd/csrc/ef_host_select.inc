@@ -42,18 +42,14 @@ int select_scratch(ef_ctx* c, uint32_t n, efm::SelectScratch* sc, uint32_t** tot
   if (n > c->sel.rows || !c->sel.scratch.p) {
     const size_t P = (size_t)c->cam.cols * c->cam.rows;
     const size_t rows = std::min((size_t)c->capacity, (size_t)n + std::max((size_t)n / 4, P));
-    const size_t chunks = efm::select_chunks((unsigned)rows) + 1;
     c->sel.rows = 0;
-    const int r = c->sel.scratch.reserve(c, (2 * chunks + 4) * sizeof(uint32_t) + rows, "selection scratch");
+    const int r = c->sel.scratch.reserve(c, Carver::scan_bytes(rows) + rows, "selection scratch");
     if (r != EF_OK) return r;
     c->sel.rows = rows;
   }
-  const size_t chunks = efm::select_chunks((unsigned)c->sel.rows) + 1;
-  uint32_t* w = c->sel.scratch.as<uint32_t>();
-  sc->chunk_count = w;
-  sc->chunk_offset = w + chunks;
-  *total = w + 2 * chunks;
-  sc->flags = (uint8_t*)(w + 2 * chunks + 4);
+  Carver cv(c->sel.scratch);
+  *total = cv.scan_words(c->sel.rows, sc);
+  sc->flags = cv.take<uint8_t>(c->sel.rows);
   return EF_OK;
 }
 // state refusals, ID numbering and label alignment of a selection, then its device form for the n rows of the map
@@ -72,9 +68,8 @@ int select_prepare(ef_ctx* c, const ef_map_selection* s, const char* fn, efm::Se
   a->n = *n;
   a->tests = s->tests & ~EF_SEL_INVERT;
   a->invert = (s->tests & EF_SEL_INVERT) ? 1u : 0u;
+  pose_Rt(s->T_bw, a->R, a->t);
   for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) a->R[i * 3 + j] = (float)s->T_bw[i * 4 + j];
-    a->t[i] = (float)s->T_bw[i * 4 + 3];
     a->box_min[i] = s->box_min[i];
     a->box_max[i] = s->box_max[i];
   }
@@ -117,10 +112,11 @@ int gather_enqueue(ef_ctx* c, const char* fn, const uint32_t* rows_dev, uint32_t
   EF_HIP(c, hipGetLastError());
   return EF_OK;
 }
-// The erase, after the arguments were checked.  mark(n, sc, total) enqueues the flags, the chunk counts and offsets of the KEPT rows (those whose
-// flag differs from `flip`) and their number into *total.
-template <typename Mark>
-int erase_run(ef_ctx* c, const char* fn, unsigned flip, uint32_t* removed, Mark mark) {
+// ---- The edit frame: the protocol every call that changes the map's rows goes through (DESIGN.md §6).  A verb calls edit_begin, enqueues its
+// own work, reads its counts in one synchronise, refuses what it must while nothing has changed, then bumps map_gen, resolves pending z-buffer
+// keys before it writes rows, and calls edit_commit.  erase_run and append_run (ef_host_insert.inc) are the only callers.
+// Begin: the refusals, the wait for everything in flight, the ID numbering, the map's count.
+int edit_begin(ef_ctx* c, const char* fn, uint32_t* n0) {
   int r = capture_check(c, fn);
   if (r != EF_OK) return r;
   if (c->cfg.close_loops) {
@@ -131,12 +127,40 @@ int erase_run(ef_ctx* c, const char* fn, unsigned flip, uint32_t* removed, Mark 
   // (every frame, every input stage on in_stream that the last frame's events ordered behind it, and every upload has been waited for by what
   // follows a synchronised stream: no new event logic)
   EF_HIP(c, hipStreamSynchronize(c->stream));
-  if (c->labels.ids_on) {   // the new rows are numbered before any of them can go: the counter then stands above every ID handed out
+  // the rows created since the last ID-consuming call are numbered before any row can go or come: the counter then stands above every ID handed
+  // out (an erase), and the zero suffix stays a suffix (an append)
+  if (c->labels.ids_on) {
     r = ids_prepare(c, fn);
     if (r != EF_OK) return r;
   }
+  return select_count(c, n0);
+}
+// Commit: the map now holds `count` rows, and map_gen was bumped since edit_begin.  labels_restart: the label calls' bound of the count (one image
+// of new rows per frame) knows nothing of rows that were appended and restarts from the exact count; an erase leaves it alone (fewer rows: the
+// bound still holds).
+int edit_commit(ef_ctx* c, uint32_t count, bool labels_restart) {
+  c->sel.count = count;
+  c->sel.gen = c->map_gen;
+  if (labels_restart && c->labels.C) {
+    c->labels.known = count;
+    c->labels.known_frames = c->stamps.size();
+    c->labels.ev_pending = false;
+  }
+  if (c->tick > 1 || !c->stamps.empty()) {   // a frame or a restore has run: the next frame is tracked against a prediction of the edited map
+    EF_HIP(c, hipMemsetAsync(&c->st->dense_count, 0, sizeof(unsigned), c->stream));   // (as ef_predict: this prediction's tally replaces the last one's)
+    const int r = do_predict(c);
+    if (r != EF_OK) return r;
+    EF_HIP(c, hipGetLastError());
+  }
+  EF_HIP(c, hipStreamSynchronize(c->stream));
+  return EF_OK;
+}
+// The erase, after the arguments were checked.  mark(n, sc, total) enqueues the flags, the chunk counts and offsets of the KEPT rows (those whose
+// flag differs from `flip`) and their number into *total.
+template <typename Mark>
+int erase_run(ef_ctx* c, const char* fn, unsigned flip, uint32_t* removed, Mark mark) {
   uint32_t n = 0;
-  r = select_count(c, &n);
+  int r = edit_begin(c, fn, &n);
   if (r != EF_OK) return r;
   efm::SelectScratch sc;
   uint32_t* total = nullptr;
@@ -151,23 +175,38 @@ int erase_run(ef_ctx* c, const char* fn, unsigned flip, uint32_t* removed, Mark 
   if (kept > n) { c->err = std::string(fn) + ": internal error (more rows kept than the map holds)"; return EF_EHIP; }
   ++c->map_gen;   // the index of the queries is stale
   if (kept < n) {
-    // after a keyed frame maps[cur ^ 1] is the buffer the kept z-buffer keys name: the four index maps are resolved from it before it is overwritten
+    // after a keyed frame maps[cur ^ 1] is the buffer the kept z-buffer keys name: the four index maps are resolved from it before it is
+    // overwritten, whichever buffer the keys name (unconditionally: the compaction's target is the other buffer, and the swap follows)
     im_materialise(c);
     efm::select_compact(sc, n, flip, c->maps[c->cur], c->maps[c->cur ^ 1], c->stream);
     hipLaunchKernelGGL(k_set_count, dim3(1), dim3(64), 0, c->stream, &c->st->map_counts[c->cur ^ 1], kept);
     EF_HIP(c, hipGetLastError());
     c->cur ^= 1;
   }
-  c->sel.count = kept;
-  c->sel.gen = c->map_gen;
-  if (c->tick > 1 || !c->stamps.empty()) {   // a frame or a restore has run: the next frame is tracked against a prediction of the edited map
-    EF_HIP(c, hipMemsetAsync(&c->st->dense_count, 0, sizeof(unsigned), c->stream));   // (as ef_predict: this prediction's tally replaces the last one's)
-    r = do_predict(c);
-    if (r != EF_OK) return r;
-    EF_HIP(c, hipGetLastError());
-  }
-  EF_HIP(c, hipStreamSynchronize(c->stream));
+  r = edit_commit(c, kept, /*labels_restart=*/false);
+  if (r != EF_OK) return r;
   if (removed) *removed = n - kept;
+  return EF_OK;
+}
+// The "list of rows" host tier of ef_map_select and ef_map_thin_select: enqueue(rows_dev, max_rows, count_dev) is the _dev tier's work into the
+// staging (named `staging` in an allocation error); the count and the first min(count, max_rows) rows are copied out.
+template <typename Enqueue>
+int rows_list_host(ef_ctx* c, const char* staging, uint32_t* rows, uint32_t max_rows, uint32_t* count, Enqueue enqueue) {
+  // (the list is never longer than the map: the staging is sized by the capacity at most)
+  const size_t cap_rows = std::min((size_t)max_rows, (size_t)c->capacity);
+  int r = c->stage.reserve(c, 16 + cap_rows * 4, staging);
+  if (r != EF_OK) return r;
+  uint32_t* d_count = c->stage.as<uint32_t>();
+  uint32_t* d_rows = (uint32_t*)(c->stage.p + 16);
+  r = enqueue(d_rows, (uint32_t)cap_rows, d_count);
+  if (r != EF_OK) return r;
+  EF_HIP(c, hipMemcpyAsync(count, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  EF_HIP(c, hipStreamSynchronize(c->stream));
+  const size_t got = std::min((size_t)*count, cap_rows);
+  if (got) {
+    EF_HIP(c, hipMemcpyAsync(rows, d_rows, got * 4, hipMemcpyDeviceToHost, c->stream));
+    EF_HIP(c, hipStreamSynchronize(c->stream));
+  }
   return EF_OK;
 }
 }  // namespace
@@ -209,22 +248,9 @@ int ef_map_select(ef_ctx* c, const ef_map_selection* s, uint32_t* rows, uint32_t
   DeviceGuard dg_(c);
   r = capture_check(c, "ef_map_select");
   if (r != EF_OK) return r;
-  // (the list is never longer than the map: the staging is sized by the capacity at most)
-  const size_t cap_rows = std::min((size_t)max_rows, (size_t)c->capacity);
-  r = c->stage.reserve(c, 16 + cap_rows * 4, "selection staging");
-  if (r != EF_OK) return r;
-  uint32_t* d_count = c->stage.as<uint32_t>();
-  uint32_t* d_rows = (uint32_t*)(c->stage.p + 16);
-  r = select_enqueue(c, s, "ef_map_select", d_rows, (uint32_t)cap_rows, d_count);
-  if (r != EF_OK) return r;
-  EF_HIP(c, hipMemcpyAsync(count, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  const size_t got = std::min((size_t)*count, cap_rows);
-  if (got) {
-    EF_HIP(c, hipMemcpyAsync(rows, d_rows, got * 4, hipMemcpyDeviceToHost, c->stream));
-    EF_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  return EF_OK;
+  return rows_list_host(c, "selection staging", rows, max_rows, count, [&](uint32_t* d_rows, uint32_t cap_rows, uint32_t* d_count) {
+    return select_enqueue(c, s, "ef_map_select", d_rows, cap_rows, d_count);
+  });
 }
 
 int ef_map_gather_dev(ef_ctx* c, const uint32_t* rows_dev, uint32_t n, float* out_dev) {

@@ -33,19 +33,16 @@ int thin_select_check(ef_ctx* c, const char* fn, const ef_thin_params* p, const 
 int thin_scratch(ef_ctx* c, uint32_t n, efm::SelectScratch* part, efm::SelectScratch* rep, uint32_t** total) {
   if (n > c->thin.rows || !c->thin.scratch.p) {
     const size_t rows = std::min((size_t)c->capacity, (size_t)n + (size_t)n / 4 + 1024);
-    const size_t chunks = efm::select_chunks((unsigned)rows) + 1;
     c->thin.rows = 0;
-    const int r = c->thin.scratch.reserve(c, (2 * chunks + 4) * sizeof(uint32_t) + 2 * rows, "thin scratch");
+    const int r = c->thin.scratch.reserve(c, Carver::scan_bytes(rows) + 2 * rows, "thin scratch");
     if (r != EF_OK) return r;
     c->thin.rows = rows;
   }
-  const size_t rows = c->thin.rows, chunks = efm::select_chunks((unsigned)rows) + 1;
-  uint32_t* w = c->thin.scratch.as<uint32_t>();
-  part->chunk_count = rep->chunk_count = w;
-  part->chunk_offset = rep->chunk_offset = w + chunks;
-  *total = w + 2 * chunks;
-  part->flags = (uint8_t*)(w + 2 * chunks + 4);
-  rep->flags = part->flags + rows;
+  Carver cv(c->thin.scratch);
+  *total = cv.scan_words(c->thin.rows, part);
+  part->flags = cv.take<uint8_t>(c->thin.rows);
+  *rep = *part;   // (the shared counts and offsets)
+  rep->flags = cv.take<uint8_t>(c->thin.rows);
   return EF_OK;
 }
 // Enqueues the bytes of the n rows of the map: removed[row] = 1 for every removed row and rep[row] = 1 for every representative (either may
@@ -91,7 +88,7 @@ int thin_select_enqueue(ef_ctx* c, const char* fn, const ef_thin_params* p, cons
   if (r != EF_OK) return r;
   r = thin_mark(c, fn, p, among, n, what == EF_THIN_ROWS_REMOVED ? sc.flags : nullptr, what == EF_THIN_ROWS_REPRESENTATIVES ? sc.flags : nullptr);
   if (r != EF_OK) return r;
-  efm::thin_count(sc, n, 0u, count_dev, c->stream);
+  efm::flags_count(sc, n, 0u, count_dev, c->stream);
   efm::select_rows(sc, n, rows_dev, max_rows, c->stream);
   EF_HIP(c, hipGetLastError());
   return EF_OK;
@@ -125,22 +122,9 @@ int ef_map_thin_select(ef_ctx* c, const ef_thin_params* p, const ef_map_selectio
   DeviceGuard dg_(c);
   r = capture_check(c, "ef_map_thin_select");
   if (r != EF_OK) return r;
-  // (the list is never longer than the map: the staging is sized by the capacity at most)
-  const size_t cap_rows = std::min((size_t)max_rows, (size_t)c->capacity);
-  r = c->stage.reserve(c, 16 + cap_rows * 4, "thin staging");
-  if (r != EF_OK) return r;
-  uint32_t* d_count = c->stage.as<uint32_t>();
-  uint32_t* d_rows = (uint32_t*)(c->stage.p + 16);
-  r = thin_select_enqueue(c, "ef_map_thin_select", p, among, what, d_rows, (uint32_t)cap_rows, d_count);
-  if (r != EF_OK) return r;
-  EF_HIP(c, hipMemcpyAsync(count, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  const size_t got = std::min((size_t)*count, cap_rows);
-  if (got) {
-    EF_HIP(c, hipMemcpyAsync(rows, d_rows, got * 4, hipMemcpyDeviceToHost, c->stream));
-    EF_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  return EF_OK;
+  return rows_list_host(c, "thin staging", rows, max_rows, count, [&](uint32_t* d_rows, uint32_t cap_rows, uint32_t* d_count) {
+    return thin_select_enqueue(c, "ef_map_thin_select", p, among, what, d_rows, cap_rows, d_count);
+  });
 }
 
 int ef_map_thin(ef_ctx* c, const ef_thin_params* p, const ef_map_selection* among, ef_thin_result* res) {
@@ -160,9 +144,9 @@ int ef_map_thin(ef_ctx* c, const ef_thin_params* p, const ef_map_selection* amon
     if (rm != EF_OK) return rm;
     rm = thin_mark(c, "ef_map_thin", p, among, n, sc.flags, rep.flags);
     if (rm != EF_OK) return rm;
-    efm::thin_count(sc, n, 1u, total, c->stream);
+    efm::flags_count(sc, n, 1u, total, c->stream);
     rep_total = tot + 1;
-    efm::thin_count(rep, n, 0u, rep_total, c->stream);   // the representatives are only counted
+    efm::flags_count(rep, n, 0u, rep_total, c->stream);   // the representatives are only counted
     return (int)EF_OK;
   });
   if (r != EF_OK) return r;

@@ -106,12 +106,11 @@ void insert_gate(const InsertArgs& a, const SelectScratch& sc, uint32_t* total, 
     } else {
       hipLaunchKernelGGL(k_insert_finite, dim3((a.n + BLK - 1) / BLK), dim3(BLK), 0, s, a);
     }
-    hipLaunchKernelGGL(k_select_count, dim3(select_chunks(a.n)), dim3(BLK), 0, s, (const uint8_t*)a.flags, a.n, 0u, sc.chunk_count);
   }
-  select_scan(sc, a.n, total, nullptr, 0u, s);   // (n = 0: the scan alone writes the total 0)
-  // the duplicates are only counted (the result's three numbers are known before anything is written); gate off: there are none
-  if (a.n && a.gate) hipLaunchKernelGGL(k_select_count, dim3(select_chunks(a.n)), dim3(BLK), 0, s, (const uint8_t*)a.dup, a.n, 0u, dup_sc.chunk_count);
-  if (a.gate) select_scan(dup_sc, a.n, dup_total, nullptr, 0u, s);
+  flags_count(sc, a.n, 0u, total, s);   // (sc.flags = a.flags)
+  // the duplicates (dup_sc.flags = a.dup) are only counted: the result's three numbers are known before anything is written.  Gate off: there
+  // are none, and dup_sc is not touched
+  if (a.gate) flags_count(dup_sc, a.n, 0u, dup_total, s);
 }
 void insert_scatter(const InsertArgs& a, SurfelSoA dst, hipStream_t s) {
   static_assert(SELECT_ROW == BLK, "one rank lane per record of a chunk");

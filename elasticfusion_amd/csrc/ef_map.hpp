@@ -299,6 +299,8 @@ struct SelectScratch {
 unsigned select_chunks(unsigned n);
 // flags of the selected rows, their per-chunk counts and offsets; *total = the number selected
 void select_flags(const SelectArgs& a, const SelectScratch& sc, uint32_t* total, hipStream_t s);
+// counts, offsets and *total of the rows whose flag in sc.flags differs from `flip` (k_select_count + the scan; n = 0: the scan alone writes 0)
+void flags_count(const SelectScratch& sc, unsigned n, unsigned flip, uint32_t* total, hipStream_t s);
 // flags = 1 for the named rows (< n; duplicates harmless); counts, offsets and *total of the rows whose flag differs from `flip`
 void select_mark_rows(const uint32_t* rows, unsigned n_rows, unsigned n, unsigned flip, const SelectScratch& sc, uint32_t* total, hipStream_t s);
 // the flagged rows in ascending order, the first max_rows of them
@@ -344,8 +346,6 @@ struct ThinArgs {
 };
 // one wave per bucket of the index: nothing is launched for an empty index
 void thin_flags(const ThinArgs& a, hipStream_t s);
-// counts, offsets and *total of the rows whose flag differs from `flip` (k_select_count + the scan; n = 0: the scan alone writes 0)
-void thin_count(const SelectScratch& sc, unsigned n, unsigned flip, uint32_t* total, hipStream_t s);
 
 // ---- fuse surfels into the map (ef_fuse.inc; ef_map_fuse of include/ef_hip.h) ----
 constexpr unsigned long long FUSE_KEY_EMPTY = 0xFFFFFFFFFFFFFFFFull;

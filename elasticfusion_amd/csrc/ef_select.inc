@@ -178,14 +178,17 @@ void select_flags(const SelectArgs& a, const SelectScratch& sc, uint32_t* total,
   if (a.n) hipLaunchKernelGGL(k_select_flags, dim3(select_chunks(a.n)), dim3(BLK), 0, s, a, sc.flags, sc.chunk_count);
   select_scan(sc, a.n, total, nullptr, 0u, s);
 }
+void flags_count(const SelectScratch& sc, unsigned n, unsigned flip, uint32_t* total, hipStream_t s) {
+  if (n) hipLaunchKernelGGL(k_select_count, dim3(select_chunks(n)), dim3(BLK), 0, s, (const uint8_t*)sc.flags, n, flip, sc.chunk_count);
+  select_scan(sc, n, total, nullptr, 0u, s);
+}
 void select_mark_rows(const uint32_t* rows, unsigned n_rows, unsigned n, unsigned flip, const SelectScratch& sc, uint32_t* total, hipStream_t s) {
   if (n) {
     (void)hipMemsetAsync(sc.flags, 0, n, s);
     const unsigned g = (unsigned)min(((size_t)n_rows + BLK - 1) / BLK, (size_t)8192);
     if (n_rows) hipLaunchKernelGGL(k_select_mark_rows, dim3(g), dim3(BLK), 0, s, rows, n_rows, n, sc.flags);
-    hipLaunchKernelGGL(k_select_count, dim3(select_chunks(n)), dim3(BLK), 0, s, (const uint8_t*)sc.flags, n, flip, sc.chunk_count);
   }
-  select_scan(sc, n, total, nullptr, 0u, s);
+  flags_count(sc, n, flip, total, s);
 }
 void select_rows(const SelectScratch& sc, unsigned n, uint32_t* rows, unsigned max_rows, hipStream_t s) {
   if (n && max_rows)

@@ -6,7 +6,7 @@
 //             ascending (x, y, z) order, one per round: a sweep in strides of 64 forms the key (primary as a monotone uint32, ~row) of every
 //             participant of the round's cell and the wave takes the maximum; a second sweep stores one byte per participant of that cell
 //             (representative or removed) and finds the next cell, the lowest above the round's.
-//   counts    k_select_count + k_scan_chunks over the bytes (thin_count), as the insert does; lists and the erase are the selection's.
+//   counts    k_select_count + k_scan_chunks over the bytes (flags_count of ef_select.inc), as the insert does; lists and the erase are the selection's.
 // Work: a bucket of L records and D distinct cells costs 1 + 2 D sweeps of ceil(L / 64) steps: linear in a cell's occupancy.  Every loop is
 // bounded by the bucket's length (sweeps) or its number of distinct cells (rounds: the round's cell strictly ascends).  No workgroup reads
 // what another writes (the index, the participant bytes and the map are read, the two byte arrays are written), and there are no atomics.
@@ -117,8 +117,4 @@ void thin_flags(const ThinArgs& a, hipStream_t s) {
   static_assert(BLK % THIN_G == 0 && QUERY_SCAN_TILE % (BLK / THIN_G) == 0, "the buckets (a multiple of the scan's tile) are whole workgroups of waves");
   if (!a.n || !a.q.n_sorted) return;
   hipLaunchKernelGGL(k_thin_flags, dim3((a.q.mask + 1) / (BLK / THIN_G)), dim3(BLK), 0, s, a);
-}
-void thin_count(const SelectScratch& sc, unsigned n, unsigned flip, uint32_t* total, hipStream_t s) {
-  if (n) hipLaunchKernelGGL(k_select_count, dim3(select_chunks(n)), dim3(BLK), 0, s, (const uint8_t*)sc.flags, n, flip, sc.chunk_count);
-  select_scan(sc, n, total, nullptr, 0u, s);
 }
