@@ -1,4 +1,6 @@
-// libefusion_hip: context, per-frame driver and the C ABI of include/ef_hip.h.
+// libefusion_hip: the context and the C ABI of include/ef_hip.h.  This file holds struct ef_ctx, what every part of the host code shares,
+// the translation unit's kernels, create / destroy and the setters; the frame, its loop closures and the getters are included below
+// (ef_host_closures.inc, ef_host_frame.inc, ef_host_inspect.inc), the map operations at the end.
 // The frame script follows ElasticFusion::processFrame (Core/ElasticFusion.cpp:270-607) for the open-loop
 // configuration; every stage is only ENQUEUED on the context's stream — pose, surfel count, fill-in
 // decision and fusion weight all live in a device-resident state block, so a frame costs zero
@@ -19,6 +21,9 @@
 #include "ef_map.hpp"
 #include "ef_deform_solver.hpp"
 #include "ef_track.hpp"
+
+// (the time-stamp log's push_back, kept out of line: the library has always exported this name, and its exported names are compared commit to commit)
+template void std::vector<int64_t>::push_back(const int64_t&);
 
 namespace {
 
@@ -67,6 +72,31 @@ struct Carver {
   }
 };
 
+// The five images of one frame.  A context holds two sets (ef_ctx::img / img_alt) and swaps them at the head of every frame.
+struct FrameImages {
+  uint8_t* rgb = nullptr;
+  uint16_t *depth_raw = nullptr, *depth_filtered = nullptr;
+  float *depth_metric = nullptr, *depth_metric_filtered = nullptr;
+};
+// One slot of the host-pointer frames' ring (ef_process_frame): a pinned staging pair, its device landing pair, the upload's event
+struct RingSlot {
+  uint8_t *h_rgb = nullptr, *d_rgb = nullptr;
+  uint16_t *h_depth = nullptr, *d_depth = nullptr;
+  hipEvent_t ev_h2d = nullptr;
+};
+// HIP-event sampling of one kernel (ef_kernel_timing): the start / stop events the launch code records through `probe`, created on first use
+struct KernelSampler {
+  std::vector<hipEvent_t> start, stop;
+  eft::KernelProbe probe{nullptr, nullptr, 0, 0};
+  int create(ef_ctx* c, int capacity);           // nothing when the events exist
+  int average_us(ef_ctx* c, float* us) const;    // waits for the stream; over probe.used samples, 0 when there is none
+  void release() {
+    for (auto e : start) (void)hipEventDestroy(e);
+    for (auto e : stop) (void)hipEventDestroy(e);
+    *this = KernelSampler{};
+  }
+};
+
 }  // namespace
 
 struct ef_ctx {
@@ -77,19 +107,9 @@ struct ef_ctx {
   efm::Cam cam;
   eft::Intr intr;
   const float maxDepthProcessed = 20.0f;  // ElasticFusion.cpp:83
-  // frame images
-  uint8_t* rgb = nullptr;
-  uint16_t* depth_raw = nullptr;
-  uint16_t* depth_filtered = nullptr;
-  float* depth_metric = nullptr;
-  float* depth_metric_filtered = nullptr;
-  // second set of the five frame images: frame k+1's input stage (copy, bilateral filter, frame pyramids) runs on
+  // frame images, and a second set of the five: frame k+1's input stage (copy, bilateral filter, frame pyramids) runs on
   // in_stream while frame k is still being fused on `stream`, so the two frames must not share these buffers
-  uint8_t* rgb_alt = nullptr;
-  uint16_t* depth_raw_alt = nullptr;
-  uint16_t* depth_filtered_alt = nullptr;
-  float* depth_metric_alt = nullptr;
-  float* depth_metric_filtered_alt = nullptr;
+  FrameImages img, img_alt;
   hipStream_t in_stream = nullptr;
   hipEvent_t ev_input_done = nullptr, ev_track_done = nullptr;
   hipEvent_t ev_frame_done[2] = {nullptr, nullptr};   // end of the frame that last used each set of frame images
@@ -100,11 +120,7 @@ struct ef_ctx {
   // host-pointer frames (ef_process_frame, the reference's processFrame signature): a ring of pinned staging pairs and device landing pairs; the
   // upload runs on copy_stream, the frame script reads the landing pair in place (round 6)
   static constexpr int RING = 3;
-  uint8_t* h_rgb_ring[RING] = {};
-  uint16_t* h_depth_ring[RING] = {};
-  uint8_t* d_rgb_ring[RING] = {};
-  uint16_t* d_depth_ring[RING] = {};
-  hipEvent_t ev_h2d[RING] = {};
+  RingSlot ring[RING];
   hipStream_t copy_stream = nullptr;
   unsigned host_seq = 0;           // host-pointer frames submitted so far
   unsigned mark_value = 0;         // what this frame's prediction writes into *h_consumed (host_seq + 1; 0: nothing)
@@ -228,15 +244,10 @@ struct ef_ctx {
                                  // 2 = (reference-order builds) round 3's launch of the small levels on 128 workgroups
   struct TrackGraph { hipGraphExec_t exec = nullptr; const void* key = nullptr; eft::TrackParams tp{}; eft::TrackTail tail{}; };
   TrackGraph tgraph[2];
-  // HIP-event sampling of the dominant kernel (ef_kernel_timing)
+  // HIP-event sampling (ef_kernel_timing) of the dominant kernel (level 0 of the launch-per-step script), of the IndexMap point splat
+  // (k_index_splat of the first predictIndices of a frame) and of the persistent tracker launch
   int ktime_every = 0;
-  std::vector<hipEvent_t> kt_start, kt_stop;
-  eft::KernelProbe probe{nullptr, nullptr, 0, 0};
-  // second sampled kernel: the IndexMap point splat (k_index_splat of the first predictIndices of a frame)
-  std::vector<hipEvent_t> ks_start, ks_stop;
-  eft::KernelProbe probe_splat{nullptr, nullptr, 0, 0};
-  std::vector<hipEvent_t> ka_start, ka_stop;   // the persistent tracker launch (fast order)
-  eft::KernelProbe probe_all{nullptr, nullptr, 0, 0};
+  KernelSampler sample_step, sample_splat, sample_all;
   hipStream_t debug_stream = nullptr;          // ef_debug_occupy
   // Host-pointer entry points of the map operations (ef_host_*.inc): the ONE device landing area their host arguments are staged through, grown
   // on demand, freed by ef_destroy.  Each call lays its own bytes out in it.  What makes one area enough:
@@ -358,6 +369,7 @@ int dev_alloc(ef_ctx* c, T** p, size_t n, int fill = 0) {
     int _r = dev_alloc((c), &(p), (size_t)(n), ##__VA_ARGS__);   \
     if (_r != EF_OK) return _r;                                  \
   } while (0)
+#define EF_TRY(call) do { const int _r = (call); if (_r != EF_OK) return _r; } while (0)
 // Nothing when `need` bytes are there; else the stream is waited for (work still queued may use the old buffer), the old buffer freed and a
 // new one allocated, its contents undefined.  A failed allocation leaves the buffer empty.
 int DevBuf::reserve(ef_ctx* c, size_t need, const char* what, bool* grew) {
@@ -463,668 +475,120 @@ int grow_trajectory(ef_ctx* c) {
   return EF_OK;
 }
 
-int do_predict(ef_ctx* c, bool count_dense = true) {
-  // ElasticFusion::predict(), ElasticFusion.cpp:621-653: combinedPredict(ACTIVE) + FillIn (fused into the resolve).  Right after a
-  // relocalisation the whole model is rendered (time = 0: no surfel is too old); while the camera is lost the fill-in passes the raw
-  // frame through (a second, plain fill-in pass over the fused one: the rare path)
-  // (a host-pointer frame: this launch, behind every reader of the frame's landing buffers, tells the host that their ring slot is free again)
-  efm::combined_predict(c->cam, c->st->T_cw, c->maps[c->cur], &c->st->map_counts[c->cur], c->maxDepthProcessed, c->cfg.confidence,
-                        c->last_frame_recovery ? 0 : c->tick, c->tick, c->cfg.time_delta, c->zbuf, c->pm, c->fm, c->depth_filtered, c->rgb,
-                        c->cfg.frame_to_frame_rgb != 0, (count_dense && !c->tally_by_consumer) ? &c->st->dense_count : nullptr, c->stream, nullptr, 0u,
-                        (count_dense && c->mark_value) ? c->d_consumed : nullptr, c->mark_value, c->rays);
-  if (count_dense) c->mark_value = 0;
-  if (count_dense && c->tally_by_consumer) c->tally_pending = true;   // (the next tracked frame's model maps count the samples of this prediction)
-  if (c->lost) efm::fill_in(c->cam, c->pm, c->depth_filtered, c->rgb, true, true, c->fm, c->stream);
-  return EF_OK;
-}
 
-// RGBDOdometry::getCovariance of the frame-to-model tracker against the gate of ElasticFusion.cpp:330-337,348-355
-bool reloc_covariance_ok(const eft::TrackState& h) {
-  double cov[36];
-  efl::lu_inverse<double, 6>(h.lastA, cov);
-  for (int i = 0; i < 6; ++i)
-    if (cov[i * 6 + i] > 1e-04) return false;
-  return true;
-}
-
-// The 1/8-resolution views of the fill-in maps (Ferns.cpp:91-93,178-180: Resize::image / Resize::vertex x2) into a pinned buffer
-// (image | vertices | normals); enqueued only, the caller synchronises
-int enqueue_fern_view(ef_ctx* c, uint8_t* h_dst) {
-  hipStream_t s = c->stream;
-  const int W = c->cam.cols, dw = c->fern_w, dh = c->fern_h, n = dw * dh;
-  const dim3 g((unsigned)((n + 255) / 256));
-  hipLaunchKernelGGL(k_resize_nearest<uint32_t>, g, dim3(256), 0, s, (const uint32_t*)c->fm.image, W, dw, dh, 8, (uint32_t*)c->view_img_dev);
-  hipLaunchKernelGGL(k_resize_nearest<float4>, g, dim3(256), 0, s, (const float4*)c->fm.vertex, W, dw, dh, 8, c->view_vert_dev);
-  hipLaunchKernelGGL(k_resize_nearest<float4>, g, dim3(256), 0, s, (const float4*)c->fm.normal, W, dw, dh, 8, c->view_norm_dev);
-  EF_HIP(c, hipMemcpyAsync(h_dst, c->view_img_dev, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-  EF_HIP(c, hipMemcpyAsync(h_dst + (size_t)n * 4, c->view_vert_dev, (size_t)n * 16, hipMemcpyDeviceToHost, s));
-  EF_HIP(c, hipMemcpyAsync(h_dst + (size_t)n * 20, c->view_norm_dev, (size_t)n * 16, hipMemcpyDeviceToHost, s));
-  return EF_OK;
-}
-// the fern codes of the current fill-in maps (k_fern_codes) into a pinned buffer; enqueued only
-int enqueue_fern_codes(ef_ctx* c, uint8_t* h_dst) {
-  hipStream_t s = c->stream;
-  ef_ferns* F = ef_closure_ferns(c->closure);
-  if (ef_ferns_table_version(F) != c->fern_table_version) {   // first use, or ef_ferns_set_table since: (rare) synchronous upload
-    std::vector<int> t((size_t)c->fern_num * 6);
-    if (ef_ferns_get_table(F, t.data()) != EF_OK) { c->err = "ef_ferns_get_table failed"; return EF_EINVAL; }
-    EF_HIP(c, hipStreamSynchronize(s));
-    EF_HIP(c, hipMemcpy(c->fern_table_dev, t.data(), t.size() * sizeof(int), hipMemcpyHostToDevice));
-    c->fern_table_version = ef_ferns_table_version(F);
-  }
-  hipLaunchKernelGGL(k_fern_codes, dim3(1), dim3(FERN_CODES_PAD), 0, s, (const uchar4*)c->fm.image, (const float4*)c->fm.vertex, c->cam.cols, 8,
-                     (const int*)c->fern_table_dev, c->fern_num, c->fern_codes_dev);
-  EF_HIP(c, hipMemcpyAsync(h_dst, c->fern_codes_dev, FERN_CODES_BYTES, hipMemcpyDeviceToHost, s));
-  return EF_OK;
-}
 void pose_of_state(const eft::TrackState& h, double* T16) {
   efl::SE3 T;
   for (int i = 0; i < 4; ++i) T.q[i] = h.q[i];
   for (int i = 0; i < 3; ++i) T.t[i] = h.t[i];
   efl::se3_matrix(T, T16);
 }
-// ef_view_fetch of the mid-frame view: Ferns::findFrame asks for it only when a keyframe passed the code gates (one more synchronisation,
-// in those frames only); the fill-in maps still hold the mid-frame prediction
-int fetch_mid_view(void* user, const uint8_t** rgb, int* ch, const float** verts, const float** norms) {
-  ef_ctx* c = (ef_ctx*)user;
-  const int r = enqueue_fern_view(c, c->h_view);
-  if (r != EF_OK) return r;
+// a tracker instance's state as it stands once everything enqueued so far has run: one copy, one synchronisation
+int read_state(ef_ctx* c, const eft::TrackState* dev, eft::TrackState* h) {
+  EF_HIP(c, hipMemcpyAsync(h, dev, sizeof(*h), hipMemcpyDeviceToHost, c->stream));
   EF_HIP(c, hipStreamSynchronize(c->stream));
-  const size_t n = (size_t)c->fern_w * c->fern_h;
-  *rgb = c->h_view; *ch = 4; *verts = (const float*)(c->h_view + n * 4); *norms = (const float*)(c->h_view + n * 20);
   return EF_OK;
 }
-// ... and of the end-of-frame view, which was copied with the end-of-frame record
-int fetch_end_view(void* user, const uint8_t** rgb, int* ch, const float** verts, const float** norms) {
-  ef_ctx* c = (ef_ctx*)user;
-  const size_t n = (size_t)c->fern_w * c->fern_h;
-  *rgb = c->h_view_end; *ch = 4; *verts = (const float*)(c->h_view_end + n * 4); *norms = (const float*)(c->h_view_end + n * 20);
-  return EF_OK;
-}
-// End of a frame (ElasticFusion.cpp:588-589, 593, 609-618) — ENQUEUED: fern codes and 1/8 view of the final fill-in maps, the pose, a
-// fresh sample of the graph nodes, all into pinned memory behind one event.  Nothing waits for them here.
-int enqueue_end_record(ef_ctx* c) {
-  hipStream_t s = c->stream;
-  int r = enqueue_fern_codes(c, c->h_codes_end);
-  if (r != EF_OK) return r;
-  if (!c->lost) {   // a lost camera stores no keyframe (:601-604): its view is never asked for
-    r = enqueue_fern_view(c, c->h_view_end);
-    if (r != EF_OK) return r;
-  }
-  EF_HIP(c, hipMemcpyAsync(&c->h_states[2], c->st, sizeof(eft::TrackState), hipMemcpyDeviceToHost, s));
-  unsigned* n_dev = (unsigned*)(c->nodes_dev + (size_t)1024 * 4);   // Deformation::sampleGraphModel (:593): every 5000th surfel of the new map
-  efm::sample_graph(c->maps[c->cur], &c->st->map_counts[c->cur], 5000, 1023, c->nodes_dev, n_dev, s);
-  EF_HIP(c, hipMemcpyAsync(c->h_nodes_pinned, c->nodes_dev, ((size_t)1024 * 4 + 1) * sizeof(float), hipMemcpyDeviceToHost, s));
-  EF_HIP(c, hipEventRecord(c->ev_end_record, s));
-  c->end_pending = true;
-  c->end_lost = c->lost;
-  c->end_tick = c->tick;
-  return EF_OK;
-}
-// ... and looked at: pose -> trajectory, codes (+ view, if the frame is kept) -> Ferns::addFrame, the node count.  Called at the next
-// point where the host waits for the stream anyway (the next frame's closures) and by every getter that shows closure state.
-int flush_end_record(ef_ctx* c) {
-  if (!c->closure || !c->end_pending) return EF_OK;
-  EF_HIP(c, hipEventSynchronize(c->ev_end_record));
-  c->end_pending = false;
-  double T[16];
-  pose_of_state(c->h_states[2], T);
-  int good = 0;
-  memcpy(&good, c->h_codes_end + FERN_CODES_PAD, sizeof(int));
-  const int r = c->end_lost ? ef_closure_log_pose(c->closure, T, c->end_tick)
-                            : ef_closure_end_frame_coded(c->closure, c->h_codes_end, good, &fetch_end_view, c, T, c->end_tick);
-  unsigned nn = 0;
-  memcpy(&nn, c->h_nodes_pinned + (size_t)1024 * 4, sizeof(unsigned));
-  c->n_nodes_host = (int)nn;
-  if (r < 0) { c->err = "ef_closure_end_frame failed"; return r; }
-  return EF_OK;
-}
-
-// Ferns.cpp:243-258 on the device: the stored keyframe is the model (initICPModel with its pose), the current view the frame
-// (initICP(vertices, normals)); getIncrementalTransformation(T, rgbOnly = false, icpWeight = 100, pyramid = false, fastOdom = false,
-// so3 = false) = ten ICP-only iterations at the 1/8 resolution itself.  One synchronisation (pose + statistics back).
-void fern_tracker_device(void* user, const float* fv, const float* fn, const double* Tf, const float* cv, const float* cn, double* T_io, float* err,
-                         float* cnt) {
-  ef_ctx* c = (ef_ctx*)user;
-  hipStream_t s = c->stream;
-  const size_t n = (size_t)c->fern_w * c->fern_h;
-  float4* d_fv = c->fern_maps_dev;
-  float4* d_fn = d_fv + n;
-  float4* d_cv = d_fn + n;
-  float4* d_cn = d_cv + n;
-  const uint8_t* zero_image = (const uint8_t*)(d_cn + n);
-  // a failed copy or launch must not hand a stale pose and inlier count to Ferns::findFrame's gates: the first HIP error is kept in the
-  // context (global_loop_closure returns EF_EHIP for it) and the candidate is rejected (error = +inf, count = 0)
-  hipError_t e = hipMemcpyAsync(d_fv, fv, n * 16, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_fn, fn, n * 16, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_cv, cv, n * 16, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_cn, cn, n * 16, hipMemcpyHostToDevice, s);
-  (void)Tf;   // the caller hands T_io = T_wc_fern in (Ferns.cpp:250); the model maps are transformed with it
-  eft::pose_injected(c->st3, T_io, false, 1.0f, false, nullptr, 0, s);
-  eft::init_icp_model(c->pyr3, (const float*)d_fv, (const float*)d_fn, (const float*)d_fv, (const float*)d_fn, c->st3, 6.0f, s);
-  eft::init_icp_maps(c->pyr3, (const float*)d_cv, (const float*)d_cn, zero_image, c->st3, 6.0f, s);
+// what every tracker call of a context shares; the caller sets rgbOnly, pyramid, fastOdom, so3 and icpWeight (and the empty-model pair)
+eft::TrackParams track_params(const ef_ctx* c) {
   eft::TrackParams tp;
-  tp.rgbOnly = false; tp.pyramid = false; tp.fastOdom = false; tp.so3 = false; tp.icpWeight = 100.f;
   tp.persistent = c->persistent;
   tp.fused_step = c->fused_step ? 1 : 0;
   tp.no_resident = c->no_resident ? 1 : 0;
-  tp.distThres = 0.10f;
-  tp.angleThres = sinf(20.f * 3.14159254f / 180.f);
-  const eft::TrackTail tail = eft::track(c->pyr3, c->st3, c->intr3, tp, s, nullptr);
-  eft::track_end(c->st3, tail, false, 1.0f, nullptr, -1, s, eft::tracker_abort_word(c->pyr3), c->d_abort + 2);
-  if (e == hipSuccess) e = hipMemcpyAsync(&c->h_states[1], c->st3, sizeof(eft::TrackState), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) {
-    if (c->fern_tracker_error.empty()) c->fern_tracker_error = std::string("fern-to-view registration: ") + hipGetErrorString(e);
-    *err = std::numeric_limits<float>::infinity();
-    *cnt = 0.f;
-    c->gloop.icp_error = *err;
-    c->gloop.icp_count = 0.f;
-    return;
-  }
-  const eft::TrackState& h = c->h_states[1];
-  efl::SE3 T;
-  for (int i = 0; i < 4; ++i) T.q[i] = h.q[i];
-  for (int i = 0; i < 3; ++i) T.t[i] = h.t[i];
-  efl::se3_matrix(T, T_io);
-  *err = h.lastICPError;
-  *cnt = h.lastICPCount;
-  c->gloop.icp_error = h.lastICPError;
-  c->gloop.icp_count = h.lastICPCount;
+  tp.distThres = 0.10f;                                   // RGBDOdometry.h:41
+  tp.angleThres = sinf(20.f * 3.14159254f / 180.f);       // RGBDOdometry.h:42
+  return tp;
 }
-
-// ElasticFusion.cpp:392-445; *accepted_with_graph = 1 when a fern was matched AND the global deformation accepted with a graph.  A lost
-// camera (relocalisation) takes the matched keyframe's registration as its pose instead (:411-413).
-int global_loop_closure(ef_ctx* c, int log_slot, int* accepted_with_graph) {
-  *accepted_with_graph = 0;
-  ef_global_loop& G = c->gloop;
-  memset(&G, 0, sizeof(G));
-  G.attempted = 1;
-  G.closest = -1;
-  for (int i = 0; i < 16; ++i) G.T_wc_recovery[i] = (i % 5 == 0) ? 1.0 : 0.0;   // Sophus::SE3d T_wc_est; (Ferns.cpp:236)
-  ef_ferns* F = ef_closure_ferns(c->closure);
-  // Ferns::findFrame only considers keyframes stored more than 300 ticks ago (Ferns.cpp:218).  While there is none — the host knows: it
-  // keeps the database — the answer is -1 whatever the view shows, and nothing has to come back from the device: no synchronisation.
-  if (!ef_closure_candidate_possible(c->closure, c->tick)) return EF_OK;
-  // otherwise: the view's fern codes, computed on the device, + the pose — one small read-back (0.5 KB + the state)
-  int r0 = enqueue_fern_codes(c, c->h_codes);
-  if (r0 != EF_OK) return r0;
-  EF_HIP(c, hipMemcpyAsync(&c->h_states[0], c->st, sizeof(eft::TrackState), hipMemcpyDeviceToHost, c->stream));
+// the captured tracker graphs hold the script and the knobs they were captured with
+void drop_track_graphs(ef_ctx* c) {
+  for (auto& g : c->tgraph)
+    if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
+}
+// a deformation graph (nodes x 16 floats, host) into graph_dev, waited for: the source is free on return; graph_nodes / graph_is_fern are the caller's
+int upload_graph(ef_ctx* c, const float* graph16, int nodes) {
+  EF_HIP(c, hipMemcpyAsync(c->graph_dev, graph16, (size_t)nodes * 16 * sizeof(float), hipMemcpyHostToDevice, c->stream));
   EF_HIP(c, hipStreamSynchronize(c->stream));
-  r0 = flush_end_record(c);   // the previous frame's keyframe decision first: the database findFrame walks must be complete
-  if (r0 != EF_OK) return r0;
-  pose_of_state(c->h_states[0], c->h_pose);
-  int good = 0;
-  memcpy(&good, c->h_codes + FERN_CODES_PAD, sizeof(int));
-  if (c->lost) {
-    const int r = ef_closure_relocalise_coded(c->closure, c->h_codes, good, &fetch_mid_view, c, c->h_pose, c->tick, &fern_tracker_device, c, G.T_wc_recovery);
-    if (!c->fern_tracker_error.empty()) { c->err = c->fern_tracker_error; c->fern_tracker_error.clear(); return EF_EHIP; }
-    if (r < 0) { c->err = "ef_closure_relocalise failed"; return r; }
-    G.closest = ef_ferns_last_closest(F);
-    if (r == 1) {
-      eft::pose_injected(c->st, G.T_wc_recovery, false, 1.0f, false, log_slot >= 0 ? c->traj : nullptr, log_slot, c->stream);
-      c->last_frame_recovery = true;
-    }
-    return EF_OK;
+  return EF_OK;
+}
+// one RGBDOdometry instance's buffers (zero-filled: the stale y/z planes of quirk Q3 are then deterministic), `partials` last.  The
+// frame-to-model tracker's nextDepth IS its lastDepth (quirk Q1); the model-to-model and the fern tracker have one of their own.
+int alloc_pyramid(ef_ctx* c, eft::Pyramid& p, int w, int h, bool alias_next_depth) {
+  p.width = w;
+  p.height = h;
+  for (int i = 0; i < eft::NUM_PYRS; ++i) {
+    const size_t n = (size_t)(w >> i) * (h >> i);
+    EF_ALLOC(c, p.depth_tmp[i], n);
+    EF_ALLOC(c, p.vmap_curr[i], 3 * n);
+    EF_ALLOC(c, p.nmap_curr[i], 3 * n);
+    EF_ALLOC(c, p.vmap_g_prev[i], 3 * n);
+    EF_ALLOC(c, p.nmap_g_prev[i], 3 * n);
+    EF_ALLOC(c, p.lastDepth[i], n);
+    if (alias_next_depth) p.nextDepth[i] = p.lastDepth[i];
+    else EF_ALLOC(c, p.nextDepth[i], n);
+    EF_ALLOC(c, p.lastImage[i], n);
+    EF_ALLOC(c, p.nextImage[i], n);
+    EF_ALLOC(c, p.lastNextImage[i], n);
+    EF_ALLOC(c, p.dIdx[i], n);
+    EF_ALLOC(c, p.dIdy[i], n);
+    EF_ALLOC(c, p.corres[i], n);
+    EF_ALLOC(c, p.rgbMask[i], n);
   }
-  c->loop_graph.assign((size_t)1024 * 16, 0.f);
-  int nodes = 0;
-  const int r = ef_closure_global_coded(c->closure, c->h_codes, good, &fetch_mid_view, c, c->h_pose, c->tick, &fern_tracker_device, c, c->h_nodes_pinned,
-                                        c->n_nodes_host, G.T_wc_recovery, c->loop_graph.data(), &nodes);
-  if (!c->fern_tracker_error.empty()) { c->err = c->fern_tracker_error; c->fern_tracker_error.clear(); return EF_EHIP; }
-  if (r < 0) { c->err = "ef_closure_global failed"; return r; }
-  G.closest = ef_ferns_last_closest(ef_closure_ferns(c->closure));   // Ferns::lastClosest: -1 unless a keyframe passed every gate
-  if (G.closest >= 0) {   // the rows handed to the optimiser: two per fern constraint (the constraint and its pin) + the kept relative ones
-    const int rows = ef_closure_last_rows(c->closure, nullptr, 0, nullptr, nullptr), rel = ef_closure_relative(c->closure, nullptr, 0);
-    G.n_constraints = rows > rel ? (rows - rel) / 2 : 0;
+  EF_ALLOC(c, p.partials, (size_t)eft::PARTIAL_ALLOC_FLOATS);
+  return EF_OK;
+}
+int KernelSampler::create(ef_ctx* c, int capacity) {
+  if (!start.empty()) return EF_OK;
+  start.resize(capacity);
+  stop.resize(capacity);
+  for (int i = 0; i < capacity; ++i) {
+    EF_HIP(c, hipEventCreate(&start[i]));
+    EF_HIP(c, hipEventCreate(&stop[i]));
   }
-  if (r != 1) return EF_OK;
-  if (nodes < 0 || nodes >= 1024) { c->err = "global closure: 0..1023 graph nodes (GlobalModel::MAX_NODES)"; return EF_EINVAL; }
-  G.accepted = 1;
-  G.graph_nodes = nodes;
-  // T_wc := the recovered pose (:429); the frame's logged pose follows (:588); the velocity weighting of :369-383 stays
-  eft::pose_injected(c->st, G.T_wc_recovery, false, 1.0f, false, log_slot >= 0 ? c->traj : nullptr, log_slot, c->stream);
-  if (nodes > 0) {
-    EF_HIP(c, hipMemcpyAsync(c->graph_dev, c->loop_graph.data(), (size_t)nodes * 16 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    EF_HIP(c, hipStreamSynchronize(c->stream));
-    c->graph_nodes = nodes;
-    c->graph_is_fern = 1;                                                                            // fernAccepted, :441,584
-    *accepted_with_graph = 1;
+  probe = eft::KernelProbe{start.data(), stop.data(), capacity, 0};
+  return EF_OK;
+}
+int KernelSampler::average_us(ef_ctx* c, float* us) const {
+  EF_HIP(c, hipStreamSynchronize(c->stream));
+  double total_ms = 0;
+  for (int i = 0; i < probe.used; ++i) {
+    float ms = 0;
+    EF_HIP(c, hipEventElapsedTime(&ms, start[i], stop[i]));
+    total_ms += ms;
   }
+  *us = probe.used ? (float)(1e3 * total_ms / probe.used) : 0.f;
   return EF_OK;
 }
 
-// ElasticFusion.cpp:447-527.  The optimisation is the registered solver's, the built-in one's, or — with the global closure enabled —
-// the closure object's (keyframe poses follow, relative constraints are kept).  Synchronises once, where the reference reads the
-// constraint buffers back (Resize.cpp:108,146).  have_active: the ACTIVE prediction at the new pose (predict() of :387) was already made.
-int local_loop_closure(ef_ctx* c, int log_slot, bool have_active) {
-  hipStream_t s = c->stream;
-  const int W = c->cam.cols, H = c->cam.rows, step = 20 /* consSample, ElasticFusion.cpp:62 */;
-  const int cw = W / step, ch = H / step;
-  const efm::FillMaps none{nullptr, nullptr, nullptr};
-  const unsigned* count = &c->st->map_counts[c->cur];
-  // predict() of :387: the ACTIVE view at the pose just estimated (its fill-in only feeds the fern database: made by the caller then)
-  if (!have_active)
-    efm::combined_predict(c->cam, c->st->T_cw, c->maps[c->cur], count, c->maxDepthProcessed, c->cfg.confidence, c->tick, c->tick, c->cfg.time_delta,
-                          c->zbuf, c->pm, none, nullptr, nullptr, false, nullptr, s, nullptr, 0u, nullptr, 0u, c->rays);
-  // :451-459, IndexMap::INACTIVE: surfels last seen at or before tick - timeDelta
-  // (the prediction stamps st2->model_view_stamp with this frame's value when it shows at least one surfel: the model-to-model tracker's
-  // persistent launch leaves at once otherwise — nothing can be registered against an empty view, and the reference's tracker, which runs
-  // all the same, ends on zero sums: the stamp only says which frames those are)
-  const unsigned view_stamp = (unsigned)c->tick * 2u + 1u;
-  efm::combined_predict(c->cam, c->st->T_cw, c->maps[c->cur], count, c->maxDepthProcessed, c->cfg.confidence, 0, c->tick - c->cfg.time_delta,
-                        c->cfg.time_delta, c->zbuf, c->old, none, nullptr, nullptr, false, nullptr, s, &c->st2->model_view_stamp, view_stamp, nullptr, 0u,
-                        c->rays);
-  eft::copy_pose(c->st2, c->st, s);                                                              // :469
-  const float maxDepthRGB = 6.0f;                                                                // RGBDOdometry.cpp:42
-  // :463 initICPModel(inactive view) + :464 initRGBModel(its image) + :466-467 initICP / initRGB(active view), fused (eft::init_model_pair)
-  eft::init_model_pair(c->pyr2, (const float*)c->old.vertex, (const float*)c->old.normal, (const uint8_t*)c->old.image, (const float*)c->pm.vertex,
-                       (const float*)c->pm.normal, (const uint8_t*)c->pm.image, c->st2, maxDepthRGB, s);
-  eft::init_rgb_sobel(c->pyr2, s);
-  eft::TrackParams tp;
-  tp.rgbOnly = false; tp.pyramid = c->cfg.pyramid != 0; tp.fastOdom = c->cfg.fast_odom != 0; tp.so3 = false; tp.icpWeight = 10.f;   // :471
-  tp.persistent = c->persistent;
-  tp.fused_step = c->fused_step ? 1 : 0;
-  tp.no_resident = c->no_resident ? 1 : 0;
-  tp.distThres = 0.10f;
-  tp.angleThres = sinf(20.f * 3.14159254f / 180.f);
-  tp.empty_model_flag = &c->st2->model_view_stamp;
-  tp.empty_model_value = view_stamp;
-  const eft::TrackTail tail2 = eft::track(c->pyr2, c->st2, c->intr, tp, s, nullptr);
-  eft::track_end(c->st2, tail2, true, 1.0f, nullptr, -1, s, eft::tracker_abort_word(c->pyr2), c->d_abort + 1);
-  eft::sample_constraints((const float*)c->pm.vertex, c->old.time, W, H, step, c->cons_dev, s);  // :485-486
-  EF_HIP(c, hipMemcpyAsync(&c->h_states[0], c->st, sizeof(eft::TrackState), hipMemcpyDeviceToHost, s));
-  EF_HIP(c, hipMemcpyAsync(&c->h_states[1], c->st2, sizeof(eft::TrackState), hipMemcpyDeviceToHost, s));
-  EF_HIP(c, hipMemcpyAsync(c->h_cons, c->cons_dev, (size_t)cw * ch * 4 * sizeof(float), hipMemcpyDeviceToHost, s));
-  EF_HIP(c, hipStreamSynchronize(s));
-  {
-    const int rf = flush_end_record(c);   // the previous frame's end-of-frame record (keyframe decision, graph nodes) has landed by now
-    if (rf != EF_OK) return rf;
-  }
-  ef_local_loop& L = c->loop;
-  memset(&L, 0, sizeof(L));
-  c->loop_constraints.clear();
-  L.attempted = 1;
-  L.graph_capacity = 1023;   // GlobalModel::MAX_NODES - 1 (GlobalModel.cpp:24): rows of loop_graph / graph_dev
-  const eft::TrackState& hc = c->h_states[0];
-  const eft::TrackState& he = c->h_states[1];
-  efl::SE3 Tc, Te;
-  for (int i = 0; i < 4; ++i) { Tc.q[i] = hc.q[i]; Te.q[i] = he.q[i]; }
-  for (int i = 0; i < 3; ++i) { Tc.t[i] = hc.t[i]; Te.t[i] = he.t[i]; }
-  efl::se3_matrix(Tc, L.T_wc_curr);
-  efl::se3_matrix(Te, L.T_wc_est);
-  L.stats[0] = he.lastICPError; L.stats[1] = he.lastICPCount; L.stats[2] = he.lastRGBError;
-  L.stats[3] = he.lastRGBCount; L.stats[4] = he.lastSO3Error; L.stats[5] = he.lastSO3Count;
-  double cov[36];
-  efl::lu_inverse<double, 6>(he.lastA, cov);                                                     // :473, getCovariance
-  bool covOk = true;
-  for (int i = 0; i < 6; ++i) {
-    L.cov_diag[i] = cov[i * 6 + i];
-    if (cov[i * 6 + i] > (double)c->cov_thresh) { covOk = false; break; }
-  }
-  L.cov_ok = covOk;
-  L.gates_ok = covOk && he.lastICPCount > (float)c->icp_count_thresh && he.lastICPError < c->icp_err_thresh;   // :483-484
-  if (!L.gates_ok) return EF_OK;
-  const double* M = L.T_wc_curr;
-  const double* E = L.T_wc_est;
-  for (int i = 0; i < cw; ++i)
-    for (int j = 0; j < ch; ++j) {
-      const float* v = c->h_cons + (size_t)(i * ch + j) * 4;
-      const unsigned tm = (unsigned)v[3];
-      if (v[2] > 0 && v[2] < c->maxDepthProcessed && tm > 0) {                                     // :490-492
-        double row[8];
-        for (int r = 0; r < 3; ++r) {   // T * Vector4d(x, y, z, 1), a 4x4 matrix product evaluated left to right
-          row[r] = ((M[r * 4] * (double)v[0] + M[r * 4 + 1] * (double)v[1]) + M[r * 4 + 2] * (double)v[2]) + M[r * 4 + 3] * 1.0;
-          row[3 + r] = ((E[r * 4] * (double)v[0] + E[r * 4 + 1] * (double)v[1]) + E[r * 4 + 2] * (double)v[2]) + E[r * 4 + 3] * 1.0;
-        }
-        row[6] = (double)tm;
-        row[7] = c->deforms == 0 ? 1.0 : 0.0;                                                      // :507-508 pinConstraints
-        c->loop_constraints.insert(c->loop_constraints.end(), row, row + 8);
-      }
-    }
-  L.n_constraints = (int)(c->loop_constraints.size() / 8);
-  if (!c->solver && !c->builtin_solver) return EF_OK;
-  c->loop_graph.assign((size_t)1024 * 16, 0.f);
-  int nodes = 0;
-  bool accepted = false;
-  if (c->solver) {
-    accepted = c->solver(c->solver_user, &L, c->loop_constraints.data(), L.n_constraints, c->loop_graph.data(), &nodes) != 0;   // :513-514
-  } else if (c->closure) {
-    // Deformation::constrain in full (:511-526): graph sampled at the end of the previous frame, keyframe poses deformed along,
-    // a third of the new relative constraints kept for later global closures
-    const int r = ef_closure_local(c->closure, c->loop_constraints.data(), L.n_constraints, c->tick, c->h_nodes_pinned, c->n_nodes_host,
-                                   c->loop_graph.data(), &nodes);
-    if (r < 0) { c->err = "ef_closure_local failed"; return r; }
-    accepted = r == 1;
-  } else {
-    // the built-in optimiser on the graph Deformation::sampleGraphModel would have sampled at the end of the previous frame
-    // (ElasticFusion.cpp:593): every 5000th surfel of the map as it stands now
-    const int max_nodes = 1023;
-    unsigned* n_dev = (unsigned*)(c->nodes_dev + (size_t)1024 * 4);
-    efm::sample_graph(c->maps[c->cur], count, 5000, max_nodes, c->nodes_dev, n_dev, s);
-    c->h_nodes.resize((size_t)1024 * 4 + 4);
-    EF_HIP(c, hipMemcpyAsync(c->h_nodes.data(), c->nodes_dev, ((size_t)1024 * 4 + 1) * sizeof(float), hipMemcpyDeviceToHost, s));
-    EF_HIP(c, hipStreamSynchronize(s));
-    unsigned n_nodes = 0;
-    memcpy(&n_nodes, &c->h_nodes[(size_t)1024 * 4], sizeof(unsigned));
-    const efd::Result r = efd::solve_local(c->h_nodes.data(), (int)n_nodes, c->loop_constraints.data(), L.n_constraints, (uint64_t)c->tick,
-                                           (uint64_t)c->last_deform_time, c->loop_graph.data());
-    accepted = r.ok;
-    nodes = r.ok ? (int)n_nodes : 0;
-    if (r.ok) c->last_deform_time = c->tick;   // Deformation.cpp:199-201
-  }
-  if (accepted) {
-    if (nodes < 0 || nodes >= 1024) { c->err = "loop solver: 0..1023 graph nodes (GlobalModel::MAX_NODES)"; return EF_EINVAL; }
-    L.applied = 1;
-    L.graph_nodes = nodes;
-    c->deforms += nodes > 0;                                                                       // :523
-    eft::adopt_pose(c->st, c->st2, log_slot >= 0 ? c->traj : nullptr, log_slot, s);                // :525
-    if (nodes > 0) {
-      EF_HIP(c, hipMemcpyAsync(c->graph_dev, c->loop_graph.data(), (size_t)nodes * 16 * sizeof(float), hipMemcpyHostToDevice, s));
-      EF_HIP(c, hipStreamSynchronize(s));
-    }
-    c->graph_nodes = nodes;
-    c->graph_is_fern = 0;
-  }
-  return EF_OK;
-}
+}  // namespace
 
-// rgb_src / depth_src: host (pinned staging) or device pointers, `kind` says which
-int process_frame(ef_ctx* c, const uint8_t* rgb_src, const uint16_t* depth_src, hipMemcpyKind kind, int64_t timestamp,
-                  float weightMultiplier, const double* in_T_wc, hipEvent_t images_ready = nullptr) {
-  hipStream_t s = c->stream;
-  const int W = c->cam.cols, H = c->cam.rows;
-  ++c->map_gen;   // fusion, clean and deformations change rows and positions: a spatial index built before this frame is stale
-  // a persistent tracker launch of an EARLIER frame gave up waiting after admission (a protocol failure, sticky: every later launch of that
-  // instance returns at once): k_track_end has copied the flag into host-mapped memory; reported here, where the front end calls
-  // (class ElasticFusion::processFrame throws), without synchronising — ef_synchronize reports the same condition for the frames in flight
-  if ((c->h_abort && (c->h_abort[0] | c->h_abort[1] | c->h_abort[2])) || c->pyr.sticky_abort || c->pyr2.sticky_abort || c->pyr3.sticky_abort) {
-    c->err = "a persistent tracker launch of an earlier frame timed out waiting for another workgroup after its whole grid had reported in (a protocol "
-             "failure, not a busy chip: that case runs on one workgroup, ef_get_tracker_fallbacks): the poses and the map since then are invalid; "
-             "recreate the context (ef_set_persistent_tracker(ctx, 0) selects the launch-per-step script)";
-    return EF_EHIP;
-  }
-  // Input stage: everything that needs nothing but the new frame.  With overlap on it is enqueued on in_stream and
-  // waits only for the previous frame's TRACKER (the last reader of the frame-side pyramids); it then runs concurrently
-  // with the previous frame's fusion + prediction on `stream`, which read the other set of frame images.
-  const bool overlap = c->overlap && !c->timing && c->in_stream != nullptr;
-  hipStream_t sb = overlap ? c->in_stream : s;
-  // Round 6: the events the second stream waits for are recorded only while the overlap is on — an event record between two kernels of a stream is
-  // a barrier packet, measured as a 6 us bubble each (three per frame: profiles/r06f_timeline_single_stream.txt).  The first overlapped frame
-  // after a frame that recorded none joins the streams on the host instead.
-  const bool want_events = c->overlap && c->in_stream != nullptr;
-  if (overlap && !c->events_live) EF_HIP(c, hipStreamSynchronize(s));
-  std::swap(c->rgb, c->rgb_alt);
-  std::swap(c->depth_raw, c->depth_raw_alt);
-  std::swap(c->depth_filtered, c->depth_filtered_alt);
-  std::swap(c->depth_metric, c->depth_metric_alt);
-  std::swap(c->depth_metric_filtered, c->depth_metric_filtered_alt);
-  const bool track_this = c->tick > 1 && !in_T_wc;
-  c->frame_parity ^= 1;
-  // (mode 2 would put the bilateral filter on the chip WHILE the persistent tracker launch wants all of its CUs: its admission would fail and the
-  // frame would run on the one-workgroup fallback — mode 1 is what such a context gets)
-  const int overlap_mode = (c->overlap_mode == 2 && c->persistent == 1 && !c->use_graph) ? 1 : c->overlap_mode;
-  if (overlap) EF_HIP(c, hipStreamWaitEvent(sb, overlap_mode == 2 ? c->ev_frame_done[c->frame_parity] : c->ev_track_done, 0));
-  if (images_ready) EF_HIP(c, hipStreamWaitEvent(sb, images_ready, 0));   // (the upload of a host-pointer frame, on copy_stream)
-  // the frame images are referenced by later stages of this frame and by the next frame's tracker
-  // (fill-in / predict read depth_filtered + rgb), so they are copied into context-owned buffers
-  // Frames that are already in HBM are not copied by separate launches in the single-stream script: the bilateral filter
-  // reads the caller's depth directly (nothing later needs the raw image) and the RGB copy rides on the intensity kernel.
-  const bool fold_copies = kind == hipMemcpyDeviceToDevice && track_this;
-  const uint16_t* depth_in = c->depth_raw;
-  if (fold_copies) {
-    depth_in = depth_src;
-  } else {
-    EF_HIP(c, hipMemcpyAsync(c->rgb, rgb_src, (size_t)W * H * 3, kind, sb));
-    EF_HIP(c, hipMemcpyAsync(c->depth_raw, depth_src, (size_t)W * H * 2, kind, sb));
-  }
-  timer_begin(c, "Preprocess");
-  // (a tracked frame: the level-0 intensity image of the frame and — folded copies — the context's copy of the colours ride on this launch)
-  const uint8_t* rgb_in = fold_copies ? rgb_src : c->rgb;
-  // Round 6: in the single-stream script of a tracked frame the pre-processing and the tracker's model-side maps are ONE launch (k_frame_inputs,
-  // at init_icp_model below): two independent kernels, one bound by LDS look-ups, the other by HBM.
-  const bool joint_inputs = track_this && !overlap && !c->timing;
-  if (!joint_inputs && !efm::preprocess_depth(depth_in, W, H, c->cfg.depth_cut, c->depth_filtered, c->depth_metric, c->depth_metric_filtered, sb, 0u,
-                             track_this ? rgb_in : nullptr, c->pyr.nextImage[0], fold_copies ? c->rgb : nullptr, c->bil_table)) {
-    c->err = "bilateral weight table missing on this device";
-    return EF_EHIP;
-  }
-  timer_end(c, "Preprocess");
-  if (overlap && overlap_mode == 2) EF_HIP(c, hipStreamWaitEvent(sb, c->ev_track_done, 0));
-  if (track_this && overlap)   // the single-stream script builds all pyramids together below (eft::build_pyramids)
-    eft::build_pyramids_frame_side(c->pyr, c->depth_filtered, c->intr, c->maxDepthProcessed, nullptr, sb, nullptr);
-  if (overlap) EF_HIP(c, hipEventRecord(c->ev_input_done, sb));
+// What a frame runs: its loop closures, then the frame itself (each may use what stands above it)
+#include "ef_host_closures.inc"
+#include "ef_host_frame.inc"
 
-  const bool rgbOnly = c->cfg.rgb_only != 0;
-  // t_T_wc.push_back / poseLogTimes.push_back, ElasticFusion.cpp:588-589: the pose is logged by the kernel that produces it
-  if ((int)c->stamps.size() >= c->traj_cap) {   // t_T_wc grows without bound in the reference: double the device log (rare: every 2^16+ frames)
-    const int r = grow_trajectory(c);
-    if (r != EF_OK) return r;
-  }
-  const int log_slot = (int)c->stamps.size();
-  c->stamps.push_back(timestamp);
-  if (c->tick == 1) {  // ElasticFusion.cpp:290-296
-    if (overlap) EF_HIP(c, hipStreamWaitEvent(s, c->ev_input_done, 0));
-    timer_begin(c, "feedbackBuffers");
-    efm::seed_map(c->cam, c->rgb, c->depth_metric, c->depth_metric_filtered, c->tick, c->maxDepthProcessed, c->maps[c->cur],
-                  &c->st->map_counts[c->cur], c->cs, s);
-    eft::init_first_rgb(c->pyr, c->rgb, s);
-    if (log_slot >= 0) eft::log_pose(c->st, c->traj, log_slot, s);
-    if (want_events) EF_HIP(c, hipEventRecord(c->ev_track_done, s));
-    timer_end(c, "feedbackBuffers");
-  } else {
-    if (!in_T_wc) {
-      eft::TrackParams tp;
-      tp.rgbOnly = rgbOnly;
-      tp.pyramid = c->cfg.pyramid != 0;
-      tp.fastOdom = c->cfg.fast_odom != 0;
-      tp.so3 = c->cfg.so3 != 0;
-      tp.icpWeight = c->cfg.icp_weight;
-      tp.persistent = c->persistent;
-      tp.fused_step = c->fused_step ? 1 : 0;
-  tp.no_resident = c->no_resident ? 1 : 0;
-      tp.distThres = 0.10f;                                   // RGBDOdometry.h:41
-      tp.angleThres = sinf(20.f * 3.14159254f / 180.f);       // RGBDOdometry.h:42
-      const bool rgb = tp.rgbOnly || tp.icpWeight < 100;
-      timer_begin(c, "odomInit");
-      const eft::FramePreprocess fp{depth_in, c->cfg.depth_cut, c->bil_table, c->depth_filtered, c->depth_metric, c->depth_metric_filtered, rgb_in,
-                                    fold_copies ? c->rgb : nullptr};
-      eft::init_icp_model(c->pyr, (const float*)c->pm.vertex, (const float*)c->pm.normal, (const float*)c->fm.vertex,
-                          (const float*)c->fm.normal, c->st, 6.0f /* maxDepthRGB, RGBDOdometry.cpp:42 */, s, (const uint8_t*)c->pm.image,
-                          (const uint8_t*)c->fm.image, c->cfg.frame_to_frame_rgb != 0, joint_inputs ? &fp : nullptr, c->tally_pending);
-      c->tally_pending = false;
-      if (overlap) {
-        eft::build_pyramids_model_side(c->pyr, nullptr, nullptr, false, c->st, s);
-        EF_HIP(c, hipStreamWaitEvent(s, c->ev_input_done, 0));
-      } else {
-        eft::build_pyramids(c->pyr, c->depth_filtered, c->intr, c->maxDepthProcessed, nullptr, nullptr, false, nullptr, c->st, s, nullptr, rgb);
-      }
-      if (rgb && overlap) eft::init_rgb_sobel(c->pyr, s);
-      timer_end(c, "odomInit");
-      timer_begin(c, "odom");
-      const bool sample = c->ktime_every > 0 && (c->tick % c->ktime_every) == 0;
-      // BASELINE configs[4] is the hipGraph-captured launch-per-step script; the persistent launch takes a fresh exchange epoch
-      // per launch as a kernel argument, which a replayed graph cannot give it
-      if (c->use_graph && !sample && !c->timing) tp.persistent = 0;
-      eft::TrackTail tail{};
-      if (c->use_graph && !sample && !c->timing) {
-        // key: which of the two intensity pyramids is "next" this frame + the knobs baked into the launch arguments
-        const void* key = c->pyr.nextImage[0];
-        ef_ctx::TrackGraph* g = nullptr;
-        for (auto& cand : c->tgraph)
-          if (cand.exec && cand.key == key && !memcmp(&cand.tp, &tp, sizeof(tp))) g = &cand;
-        if (!g) {
-          g = (c->tgraph[0].exec && c->tgraph[0].key != key) ? &c->tgraph[1] : &c->tgraph[0];
-          if (g->exec) { (void)hipGraphExecDestroy(g->exec); g->exec = nullptr; }
-          eft::track_prepare(c->pyr, tp, s);   // (a script switch clears the exchange areas: outside the capture, not replayed with it — ADVICE r5)
-          eft::Pyramid pyr_copy = c->pyr;   // track() swaps the copy's pointers; the real swap is done below
-          hipGraph_t graph = nullptr;
-          EF_HIP(c, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-          g->tail = eft::track(pyr_copy, c->st, c->intr, tp, s, nullptr);
-          hipError_t ce = hipStreamEndCapture(s, &graph);   // always ends the capture, whatever was recorded
-          if (ce == hipSuccess) ce = hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0);
-          if (graph) (void)hipGraphDestroy(graph);
-          if (ce != hipSuccess) {
-            g->exec = nullptr;
-            c->err = std::string("hipGraph capture of the tracker: ") + hipGetErrorString(ce);
-            return EF_EHIP;
-          }
-          g->key = key;
-          memcpy(&g->tp, &tp, sizeof(tp));
-        }
-        EF_HIP(c, hipGraphLaunch(g->exec, s));
-        eft::track_swap(c->pyr, tp);
-        tail = g->tail;
-      } else {
-        tail = eft::track(c->pyr, c->st, c->intr, tp, s, sample ? &c->probe : nullptr, sample && c->probe_all.start ? &c->probe_all : nullptr);
-      }
-      eft::track_end(c->st, tail, rgb, weightMultiplier, log_slot >= 0 ? c->traj : nullptr, log_slot, s, eft::tracker_abort_word(c->pyr), c->d_abort);
-      timer_end(c, "odom");
-      c->tracking_ok = true;
-      if (c->reloc) {   // :326-366: the tracker's verdict on itself, read back where the reference reads lastICPError / getCovariance()
-        EF_HIP(c, hipMemcpyAsync(&c->h_reloc, c->st, sizeof(eft::TrackState), hipMemcpyDeviceToHost, s));
-        EF_HIP(c, hipStreamSynchronize(s));
-        c->tracking_ok = c->h_reloc.lastICPError < 1e-04;
-        if (!c->lost) {
-          if (!reloc_covariance_ok(c->h_reloc)) c->tracking_ok = false;
-          if (!c->tracking_ok) {
-            if (++c->tracking_count > 10) c->lost = true;
-          } else {
-            c->tracking_count = 0;
-          }
-        } else if (c->last_frame_recovery) {
-          if (!reloc_covariance_ok(c->h_reloc)) c->tracking_ok = false;
-          if (c->tracking_ok) {
-            c->lost = false;
-            c->tracking_count = 0;
-          }
-          c->last_frame_recovery = false;
-        }
-      }
-    } else {
-      c->tracking_ok = true;   // :300: an injected pose is never judged
-      if (overlap) EF_HIP(c, hipStreamWaitEvent(s, c->ev_input_done, 0));
-      eft::pose_injected(c->st, in_T_wc, true, weightMultiplier, true, log_slot >= 0 ? c->traj : nullptr, log_slot, s);
-    }
-    // from here on nothing of this frame reads the frame-side pyramids: the next frame's input stage may start
-    if (want_events) EF_HIP(c, hipEventRecord(c->ev_track_done, s));
-    // mid-frame predict() of ElasticFusion.cpp:387 is dead work without loop closure: skipped
-    if (c->cfg.close_loops) {
-      int fern_graph = 0;
-      if (c->closure) {   // :387-445: predict() with its fill-in at the new pose, then the fern database
-        timer_begin(c, "globalLoop");
-        do_predict(c, false);
-        c->last_frame_recovery = false;                                                           // :393
-        const int r = global_loop_closure(c, log_slot, &fern_graph);
-        timer_end(c, "globalLoop");
-        if (r != EF_OK) return r;
-      }
-      if (c->lost) {       // :447: a lost camera closes no local loop
-        memset(&c->loop, 0, sizeof(c->loop));
-      } else if (!fern_graph) {   // :447: rawGraph.size() == 0
-        timer_begin(c, "localLoop");
-        const int r = local_loop_closure(c, log_slot, c->closure != nullptr);
-        timer_end(c, "localLoop");
-        if (r != EF_OK) return r;
-      } else {
-        memset(&c->loop, 0, sizeof(c->loop));
-      }
-    }
-    if (!rgbOnly && c->tracking_ok && !c->lost && !c->track_only) {  // ElasticFusion.cpp:536-585
-      timer_begin(c, "indexMap");
-      const bool sample_splat = c->ktime_every > 0 && (c->tick % c->ktime_every) == 0 && c->probe_splat.start;
-      efm::IndexMaps im_assoc = c->im;   // what the association taps: no colour / time stream (the second predictIndices below writes all four maps)
-      im_assoc.color_time = nullptr;
-      // Round 9: neither predictIndices is resolved — their consumers tap the keys (ef_ctx::zbuf_assoc).  Not with stage timers (the update pass is
-      // a launch of its own between the two), the reference's download buffer, or a context that closes loops (a deformation's clean(), the
-      // predictions that share c->zbuf): those run the resolve launches as before.
-#ifdef EF_KEEP_INDEX_RESOLVE   // (A/B build "resolve": rounds 1-8's two resolve launches per frame)
-      const bool keyed = false;
-#else
-      const bool keyed = !c->timing && !c->reference_download && !c->cfg.close_loops;
-#endif
-      const efm::KeyedIndex key_assoc{c->zbuf_assoc, c->st->T_cw, c->maps[c->cur]}, key_clean{c->zbuf_clean, c->st->T_cw, c->maps[c->cur]};
-      efm::predict_indices(c->cam, c->st->T_cw, c->tick, c->maps[c->cur], &c->st->map_counts[c->cur], c->maxDepthProcessed, c->cfg.time_delta,
-                           keyed ? c->zbuf_assoc : c->zbuf, im_assoc, s, sample_splat ? &c->probe_splat : nullptr, nullptr, nullptr, !keyed);
-      timer_end(c, "indexMap");
-      timer_begin(c, "Fuse::Data+Update");
-      // (the update pass — k_merge — rides on the splat of the second predictIndices: one launch less; with stage timers on it stays a launch of
-      // its own so that the reference's TICK / TOCK stages keep their meaning)
-      const bool defer_merge = !c->timing;
-      efm::fuse(c->cam, c->st->pose_f, c->tick, c->rgb, c->depth_metric, c->depth_metric_filtered, c->im, c->maxDepthProcessed,
-                &c->st->weighting, c->maps[c->cur], &c->st->map_counts[c->cur], c->cand, c->winner, s, defer_merge,
-                keyed ? &key_assoc : nullptr, keyed ? c->zbuf_clean : nullptr);
-      if (c->reference_download && !defer_merge) efm::copy_map(c->maps[c->cur], &c->st->map_counts[c->cur], c->shadow, s);
-      timer_end(c, "Fuse::Data+Update");
-      timer_begin(c, "indexMap2");
-      efm::predict_indices(c->cam, c->st->T_cw, c->tick, c->maps[c->cur], &c->st->map_counts[c->cur], c->maxDepthProcessed, c->cfg.time_delta,
-                           keyed ? c->zbuf_clean : c->zbuf, c->im, s, nullptr, defer_merge ? &c->cand : nullptr, c->winner, !keyed);
-      // (`im` now is what this frame's second predictIndices wrote, or — keyed — is still to be resolved from zbuf_clean when somebody asks)
-      c->im_pending = keyed;
-      c->im_map = c->cur;
-      if (c->reference_download && defer_merge) efm::copy_map(c->maps[c->cur], &c->st->map_counts[c->cur], c->shadow, s);
-      timer_end(c, "indexMap2");
-      // a pending deformation (ElasticFusion.cpp:558-585): re-predict the depth of the surfels outside the time window, then let
-      // clean() move every kept surfel with the graph
-      efm::Deformation def{c->graph_dev, c->graph_nodes, c->synth_depth, c->graph_is_fern, c->maxDepthProcessed};
-      if (c->graph_nodes > 0 && !c->graph_is_fern)
-        efm::synthesize_depth(c->cam, c->st->T_cw, c->maps[c->cur], &c->st->map_counts[c->cur], c->maxDepthProcessed, c->cfg.confidence, c->tick,
-                              c->tick - c->cfg.time_delta, 65535, c->zbuf, c->synth_depth, s, c->rays);
-      timer_begin(c, "Fuse::Copy");
-      efm::clean(c->cam, c->st->T_cw, c->tick, c->im, c->cfg.confidence, c->cfg.time_delta, c->maps[c->cur], &c->st->map_counts[c->cur], c->cand,
-                 c->winner, c->maps[c->cur ^ 1], &c->st->map_counts[c->cur ^ 1], c->capacity, c->cs, c->overflow, s,
-                 c->graph_nodes > 0 ? &def : nullptr, keyed ? &key_clean : nullptr, keyed ? c->zbuf_assoc : nullptr, keyed ? c->im_T16 : nullptr);
-      c->graph_nodes = 0;
-      c->cur ^= 1;
-      timer_end(c, "Fuse::Copy");
-    } else {
-      c->graph_nodes = 0;   // rawGraph is a local of processFrame: a deformation accepted in a frame that does not fuse is never applied
-    }
-  }
-  timer_begin(c, "IndexMap::ACTIVE");
-  do_predict(c);  // ElasticFusion.cpp:599
-  timer_end(c, "IndexMap::ACTIVE");
-  if (c->closure) {   // :588-589, 593, 609-618: pose -> trajectory, graph nodes re-sampled, final fill-in view -> Ferns::addFrame
-    timer_begin(c, "ferns");
-    int r = flush_end_record(c);           // (normally long done: the frame's closures synchronised)
-    if (r == EF_OK) r = enqueue_end_record(c);   // no synchronisation: looked at when the next frame first waits for the stream
-    timer_end(c, "ferns");
-    if (r != EF_OK) return r;
-  }
-  if (want_events && c->overlap_mode == 2) EF_HIP(c, hipEventRecord(c->ev_frame_done[c->frame_parity], s));
-  c->events_live = want_events;
-  if (!c->lost) c->tick++;   // :601-604
-  EF_HIP(c, hipGetLastError());
-  return EF_OK;
-}
+namespace {
 
 int ctx_init(ef_ctx* c) {
   const ef_config& g = c->cfg;
   const int W = g.width, H = g.height;
   const size_t P = (size_t)W * H;
   hipStream_t s = c->stream;
-  EF_ALLOC(c, c->rgb, P * 3);
-  EF_ALLOC(c, c->depth_raw, P);
-  EF_ALLOC(c, c->depth_filtered, P);
-  EF_ALLOC(c, c->depth_metric, P);
-  EF_ALLOC(c, c->depth_metric_filtered, P);
-  EF_ALLOC(c, c->rgb_alt, P * 3);
-  EF_ALLOC(c, c->depth_raw_alt, P);
-  EF_ALLOC(c, c->depth_filtered_alt, P);
-  EF_ALLOC(c, c->depth_metric_alt, P);
-  EF_ALLOC(c, c->depth_metric_filtered_alt, P);
+  for (FrameImages* f : {&c->img, &c->img_alt}) {
+    EF_ALLOC(c, f->rgb, P * 3);
+    EF_ALLOC(c, f->depth_raw, P);
+    EF_ALLOC(c, f->depth_filtered, P);
+    EF_ALLOC(c, f->depth_metric, P);
+    EF_ALLOC(c, f->depth_metric_filtered, P);
+  }
   EF_HIP(c, hipStreamCreateWithFlags(&c->in_stream, hipStreamNonBlocking));
   for (auto& e : c->ev_frame_done) EF_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
   EF_HIP(c, hipEventCreateWithFlags(&c->ev_input_done, hipEventDisableTiming));
   EF_HIP(c, hipEventCreateWithFlags(&c->ev_track_done, hipEventDisableTiming));
   EF_HIP(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-  for (int i = 0; i < ef_ctx::RING; ++i) {
-    EF_HIP(c, hipEventCreateWithFlags(&c->ev_h2d[i], hipEventDisableTiming));
-    EF_HIP(c, hipHostMalloc((void**)&c->h_rgb_ring[i], P * 3));
-    EF_HIP(c, hipHostMalloc((void**)&c->h_depth_ring[i], P * 2));
-    EF_ALLOC(c, c->d_rgb_ring[i], P * 3);
-    EF_ALLOC(c, c->d_depth_ring[i], P);
+  for (RingSlot& r : c->ring) {
+    EF_HIP(c, hipEventCreateWithFlags(&r.ev_h2d, hipEventDisableTiming));
+    EF_HIP(c, hipHostMalloc((void**)&r.h_rgb, P * 3));
+    EF_HIP(c, hipHostMalloc((void**)&r.h_depth, P * 2));
+    EF_ALLOC(c, r.d_rgb, P * 3);
+    EF_ALLOC(c, r.d_depth, P);
   }
   EF_HIP(c, hipHostMalloc((void**)&c->h_consumed, sizeof(unsigned), hipHostMallocMapped));
   *c->h_consumed = 0u;
@@ -1133,26 +597,7 @@ int ctx_init(ef_ctx* c) {
   memset(c->h_abort, 0, 4 * sizeof(unsigned));
   EF_HIP(c, hipHostGetDevicePointer((void**)&c->d_abort, c->h_abort, 0));
   // tracker pyramids (zero-filled: the stale y/z planes of quirk Q3 are then deterministic)
-  c->pyr.width = W;
-  c->pyr.height = H;
-  for (int i = 0; i < eft::NUM_PYRS; ++i) {
-    const size_t n = (size_t)(W >> i) * (H >> i);
-    EF_ALLOC(c, c->pyr.depth_tmp[i], n);
-    EF_ALLOC(c, c->pyr.vmap_curr[i], 3 * n);
-    EF_ALLOC(c, c->pyr.nmap_curr[i], 3 * n);
-    EF_ALLOC(c, c->pyr.vmap_g_prev[i], 3 * n);
-    EF_ALLOC(c, c->pyr.nmap_g_prev[i], 3 * n);
-    EF_ALLOC(c, c->pyr.lastDepth[i], n);
-    c->pyr.nextDepth[i] = c->pyr.lastDepth[i];   // quirk Q1
-    EF_ALLOC(c, c->pyr.lastImage[i], n);
-    EF_ALLOC(c, c->pyr.nextImage[i], n);
-    EF_ALLOC(c, c->pyr.lastNextImage[i], n);
-    EF_ALLOC(c, c->pyr.dIdx[i], n);
-    EF_ALLOC(c, c->pyr.dIdy[i], n);
-    EF_ALLOC(c, c->pyr.corres[i], n);
-    EF_ALLOC(c, c->pyr.rgbMask[i], n);
-  }
-  EF_ALLOC(c, c->pyr.partials, (size_t)eft::PARTIAL_ALLOC_FLOATS);
+  EF_TRY(alloc_pyramid(c, c->pyr, W, H, true));
   EF_ALLOC(c, c->st, 1);
   // prediction images
   EF_ALLOC(c, c->im.index, P);
@@ -1196,26 +641,7 @@ int ctx_init(ef_ctx* c) {
   c->cs.max_groups = c->cs.max_chunks / efm::CLEAN_GROUP + 2;
   EF_ALLOC(c, c->cs.group_sum, 2 * (size_t)c->cs.max_groups * efm::CLEAN_GSTRIDE);   // (zero-filled: what the first clean() expects of its half)
   if (g.close_loops) {
-    c->pyr2.width = W;
-    c->pyr2.height = H;
-    for (int i = 0; i < eft::NUM_PYRS; ++i) {
-      const size_t n = (size_t)(W >> i) * (H >> i);
-      EF_ALLOC(c, c->pyr2.depth_tmp[i], n);
-      EF_ALLOC(c, c->pyr2.vmap_curr[i], 3 * n);
-      EF_ALLOC(c, c->pyr2.nmap_curr[i], 3 * n);
-      EF_ALLOC(c, c->pyr2.vmap_g_prev[i], 3 * n);
-      EF_ALLOC(c, c->pyr2.nmap_g_prev[i], 3 * n);
-      EF_ALLOC(c, c->pyr2.lastDepth[i], n);
-      EF_ALLOC(c, c->pyr2.nextDepth[i], n);
-      EF_ALLOC(c, c->pyr2.lastImage[i], n);
-      EF_ALLOC(c, c->pyr2.nextImage[i], n);
-      EF_ALLOC(c, c->pyr2.lastNextImage[i], n);
-      EF_ALLOC(c, c->pyr2.dIdx[i], n);
-      EF_ALLOC(c, c->pyr2.dIdy[i], n);
-      EF_ALLOC(c, c->pyr2.corres[i], n);
-      EF_ALLOC(c, c->pyr2.rgbMask[i], n);
-    }
-    EF_ALLOC(c, c->pyr2.partials, (size_t)eft::PARTIAL_ALLOC_FLOATS);
+    EF_TRY(alloc_pyramid(c, c->pyr2, W, H, false));
     EF_ALLOC(c, c->st2, 1);
     EF_ALLOC(c, c->old.image, P);
     EF_ALLOC(c, c->old.vertex, P);
@@ -1250,31 +676,20 @@ void ctx_free(ef_ctx* c) {
   for (void* p : c->allocs) (void)hipFree(p);
   if (c->h_abort) (void)hipHostFree(c->h_abort);
   if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
-  for (int i = 0; i < ef_ctx::RING; ++i) {
-    if (c->ev_h2d[i]) (void)hipEventDestroy(c->ev_h2d[i]);
-    if (c->h_rgb_ring[i]) (void)hipHostFree(c->h_rgb_ring[i]);
-    if (c->h_depth_ring[i]) (void)hipHostFree(c->h_depth_ring[i]);
+  for (RingSlot& r : c->ring) {
+    if (r.ev_h2d) (void)hipEventDestroy(r.ev_h2d);
+    if (r.h_rgb) (void)hipHostFree(r.h_rgb);
+    if (r.h_depth) (void)hipHostFree(r.h_depth);
   }
-  if (c->h_consumed) (void)hipHostFree(c->h_consumed);
-  if (c->h_cons) (void)hipHostFree(c->h_cons);
-  if (c->h_states) (void)hipHostFree(c->h_states);
-  if (c->h_view) (void)hipHostFree(c->h_view);
-  if (c->h_view_end) (void)hipHostFree(c->h_view_end);
-  if (c->h_codes) (void)hipHostFree(c->h_codes);
-  if (c->h_codes_end) (void)hipHostFree(c->h_codes_end);
+  for (void* p : {(void*)c->h_consumed, (void*)c->h_cons, (void*)c->h_states, (void*)c->h_view, (void*)c->h_view_end, (void*)c->h_codes, (void*)c->h_codes_end})
+    if (p) (void)hipHostFree(p);
   if (c->ev_end_record) (void)hipEventDestroy(c->ev_end_record);
   if (c->h_nodes_pinned) (void)hipHostFree(c->h_nodes_pinned);
   if (c->closure) ef_closure_destroy(c->closure);
   for (auto& t : c->timers) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
-  for (auto e : c->kt_start) (void)hipEventDestroy(e);
-  for (auto e : c->kt_stop) (void)hipEventDestroy(e);
-  for (auto& g : c->tgraph)
-    if (g.exec) (void)hipGraphExecDestroy(g.exec);
+  for (KernelSampler* k : {&c->sample_step, &c->sample_all, &c->sample_splat}) k->release();
+  drop_track_graphs(c);
   if (c->debug_stream) { (void)hipStreamSynchronize(c->debug_stream); (void)hipStreamDestroy(c->debug_stream); }
-  for (auto e : c->ka_start) (void)hipEventDestroy(e);
-  for (auto e : c->ka_stop) (void)hipEventDestroy(e);
-  for (auto e : c->ks_start) (void)hipEventDestroy(e);
-  for (auto e : c->ks_stop) (void)hipEventDestroy(e);
   for (DevBuf* b : {&c->stage, &c->render.zbuf, &c->labels.index, &c->query.sorted, &c->query.rows, &c->query.cells, &c->reg.slabs, &c->sel.scratch, &c->ins.scratch, &c->thin.scratch, &c->fuse.scratch})
     b->release();
   for (int k = 0; k < 2; ++k) {
@@ -1464,44 +879,6 @@ int ef_synchronize(ef_ctx* c) {
   return check_capacity(c);
 }
 
-int ef_process_frame(ef_ctx* c, const uint8_t* rgb, const uint16_t* depth, int64_t timestamp, float wm, const double* T) {
-  if (!c || !rgb || !depth) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  const size_t P = (size_t)c->cam.cols * c->cam.rows;
-  // The reference uploads inside processFrame (ElasticFusion.cpp:278-280: three texture uploads, blocking).  Here (round 6): the caller's images go
-  // into slot r of a ring of pinned staging pairs, are uploaded on copy_stream into the ring's device landing pair — beside the previous
-  // frames' kernels — and the frame script reads the landing pair IN PLACE (the bilateral filter reads the depth, the intensity kernel reads the
-  // colours and keeps the context's copy: no device-side copy, exactly the device-pointer script).  The compute stream waits for the upload
-  // (one barrier packet); nothing waits on the host unless the caller is a whole ring ahead of the GPU: slot r is free once the frame that used
-  // it last has been read, which that frame's prediction launch reports through a host-mapped word (no event on the compute stream: an event
-  // record there costs a 6 us bubble, profiles/r06f_timeline_single_stream.txt).
-  const int r = (int)(c->host_seq % ef_ctx::RING);
-  if (c->host_seq >= (unsigned)ef_ctx::RING) {
-    const unsigned need = c->host_seq - ef_ctx::RING + 1u;   // the marker the last user of slot r leaves
-    volatile unsigned* seen = c->h_consumed;
-    int spins = 0;
-    while ((int)(*seen - need) < 0) {
-      if (++spins > 20000) {   // (~ms: that frame ended early on an error path, or the marker is not visible: join the streams instead)
-        EF_HIP(c, hipStreamSynchronize(c->stream));
-        break;
-      }
-      if (spins > 64) std::this_thread::yield();
-    }
-  }
-  memcpy(c->h_rgb_ring[r], rgb, P * 3);
-  memcpy(c->h_depth_ring[r], depth, P * 2);
-  EF_HIP(c, hipMemcpyAsync(c->d_depth_ring[r], c->h_depth_ring[r], P * 2, hipMemcpyHostToDevice, c->copy_stream));
-  EF_HIP(c, hipMemcpyAsync(c->d_rgb_ring[r], c->h_rgb_ring[r], P * 3, hipMemcpyHostToDevice, c->copy_stream));
-  EF_HIP(c, hipEventRecord(c->ev_h2d[r], c->copy_stream));
-  c->mark_value = c->host_seq + 1u;
-  c->host_seq++;
-  return process_frame(c, c->d_rgb_ring[r], c->d_depth_ring[r], hipMemcpyDeviceToDevice, timestamp, wm, T, c->ev_h2d[r]);
-}
-int ef_process_frame_dev(ef_ctx* c, const uint8_t* rgb_dev, const uint16_t* depth_dev, int64_t timestamp, float wm, const double* T) {
-  if (!c || !rgb_dev || !depth_dev) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  return process_frame(c, rgb_dev, depth_dev, hipMemcpyDeviceToDevice, timestamp, wm, T);
-}
 // The input stream restricted to every n-th CU (hipExtStreamCreateWithCUMask; n <= 1: the whole chip): the next frame's bilateral filter —
 // the one ALU-bound kernel of a frame — then runs beside the previous frame's fusion and prediction on a quarter of the chip instead of
 // flooding every CU the latency-bound map kernels are trying to run on.
@@ -1532,8 +909,7 @@ int ef_set_deformation(ef_ctx* c, const float* graph, int nodes, int is_fern) {
   if (!c || nodes < 0 || (nodes > 0 && !graph)) return EF_EINVAL;
   DeviceGuard dg_(c);
   if (nodes >= 1024) { c->err = "ef_set_deformation: at most 1023 nodes (GlobalModel::MAX_NODES)"; return EF_EINVAL; }
-  if (nodes > 0) EF_HIP(c, hipMemcpyAsync(c->graph_dev, graph, (size_t)nodes * 16 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  if (nodes > 0) EF_HIP(c, hipStreamSynchronize(c->stream));   // the caller's buffer is borrowed for the call only
+  if (nodes > 0) EF_TRY(upload_graph(c, graph, nodes));   // (waited for: the caller's buffer is borrowed for the call only)
   c->graph_nodes = nodes;
   c->graph_is_fern = is_fern != 0;
   return EF_OK;
@@ -1621,26 +997,7 @@ int ef_enable_global_closure(ef_ctx* c, int num_ferns, float photo_thresh, float
   EF_HIP(c, hipHostMalloc((void**)&c->h_nodes_pinned, ((size_t)1024 * 4 + 4) * sizeof(float)));
   memset(c->h_nodes_pinned, 0, ((size_t)1024 * 4 + 4) * sizeof(float));
   c->intr3 = eft::Intr{c->cfg.fx / 8, c->cfg.fy / 8, c->cfg.cx / 8, c->cfg.cy / 8};   // Ferns.cpp:31-36
-  c->pyr3.width = c->fern_w;
-  c->pyr3.height = c->fern_h;
-  for (int i = 0; i < eft::NUM_PYRS; ++i) {
-    const size_t m = (size_t)(c->fern_w >> i) * (c->fern_h >> i);
-    EF_ALLOC(c, c->pyr3.depth_tmp[i], m);
-    EF_ALLOC(c, c->pyr3.vmap_curr[i], 3 * m);
-    EF_ALLOC(c, c->pyr3.nmap_curr[i], 3 * m);
-    EF_ALLOC(c, c->pyr3.vmap_g_prev[i], 3 * m);
-    EF_ALLOC(c, c->pyr3.nmap_g_prev[i], 3 * m);
-    EF_ALLOC(c, c->pyr3.lastDepth[i], m);
-    EF_ALLOC(c, c->pyr3.nextDepth[i], m);
-    EF_ALLOC(c, c->pyr3.lastImage[i], m);
-    EF_ALLOC(c, c->pyr3.nextImage[i], m);
-    EF_ALLOC(c, c->pyr3.lastNextImage[i], m);
-    EF_ALLOC(c, c->pyr3.dIdx[i], m);
-    EF_ALLOC(c, c->pyr3.dIdy[i], m);
-    EF_ALLOC(c, c->pyr3.corres[i], m);
-    EF_ALLOC(c, c->pyr3.rgbMask[i], m);
-  }
-  EF_ALLOC(c, c->pyr3.partials, (size_t)eft::PARTIAL_ALLOC_FLOATS);
+  EF_TRY(alloc_pyramid(c, c->pyr3, c->fern_w, c->fern_h, false));
   EF_ALLOC(c, c->st3, 1);
   hipLaunchKernelGGL(k_init_state, dim3(1), dim3(64), 0, c->stream, c->st3, 1, c->fern_w * c->fern_h);
   EF_HIP(c, hipStreamSynchronize(c->stream));
@@ -1656,53 +1013,11 @@ int ef_set_relocalisation(ef_ctx* c, int on) {
   if (!c->reloc) { c->lost = false; c->last_frame_recovery = false; c->tracking_count = 0; c->tracking_ok = true; }
   return EF_OK;
 }
-int ef_get_relocalisation(ef_ctx* c, ef_reloc_state* out) {
-  if (!c || !out) return EF_EINVAL;
-  out->lost = c->lost; out->tracking_ok = c->tracking_ok; out->tracking_count = c->tracking_count; out->last_frame_recovery = c->last_frame_recovery;
-  return EF_OK;
-}
-int ef_get_global_loop(ef_ctx* c, ef_global_loop* info) {
-  if (!c || !info) return EF_EINVAL;
-  *info = c->gloop;
-  return EF_OK;
-}
-ef_closure* ef_get_closure(ef_ctx* c) {
-  if (!c) return nullptr;
-  DeviceGuard dg_(c);
-  (void)flush_end_record(c);   // the last frame's keyframe decision and trajectory entry are part of what the caller will look at
-  return c->closure;
-}
-int ef_get_local_loop(ef_ctx* c, ef_local_loop* info, double* constraints, int max_constraints, int* n_out) {
-  if (!c || !info) return EF_EINVAL;
-  *info = c->loop;
-  int n = c->loop.n_constraints < max_constraints ? c->loop.n_constraints : max_constraints;
-  if (!constraints) n = 0;
-  if (n > 0) memcpy(constraints, c->loop_constraints.data(), (size_t)n * 8 * sizeof(double));
-  if (n_out) *n_out = n;
-  return EF_OK;
-}
-int ef_sample_graph(ef_ctx* c, float* nodes4, int max_nodes, int* n_out) {
-  if (!c || !nodes4 || !n_out || max_nodes <= 0) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  float* dev = nullptr;
-  EF_HIP(c, hipMalloc((void**)&dev, ((size_t)max_nodes * 4 + 4) * sizeof(float)));
-  unsigned* n_dev = (unsigned*)(dev + (size_t)max_nodes * 4);
-  efm::sample_graph(c->maps[c->cur], &c->st->map_counts[c->cur], 5000, max_nodes, dev, n_dev, c->stream);
-  unsigned n = 0;
-  hipError_t e = hipMemcpyAsync(&n, n_dev, sizeof(n), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess && n > 0) e = hipMemcpy(nodes4, dev, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost);
-  (void)hipFree(dev);
-  EF_HIP(c, e);
-  *n_out = (int)n;
-  return EF_OK;
-}
 int ef_set_graph_replay(ef_ctx* c, int on) { if (!c) return EF_EINVAL; c->use_graph = on != 0; return EF_OK; }
 int ef_set_fused_step(ef_ctx* c, int on) {
   if (!c) return EF_EINVAL;
   c->fused_step = on != 0;
-  for (auto& g : c->tgraph)
-    if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
+  drop_track_graphs(c);
   return EF_OK;
 }
 int ef_set_track_only(ef_ctx* c, int on) { if (!c) return EF_EINVAL; c->track_only = on != 0; return EF_OK; }
@@ -1713,63 +1028,10 @@ int ef_set_persistent_tracker(ef_ctx* c, int on) {
 #ifdef EF_FAST_ORDER
   if (c->persistent == 2) c->persistent = 1;   // (the fast order has no launch of the small levels: 2 means 1 there, also to process_frame's overlap rule)
 #endif
-  for (auto& g : c->tgraph)   // captured tracker graphs hold the other script
-    if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
+  drop_track_graphs(c);   // they hold the other script
   return EF_OK;
 }
-int ef_predict(ef_ctx* c) {
-  if (!c) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  EF_HIP(c, hipMemsetAsync(&c->st->dense_count, 0, sizeof(unsigned), c->stream));
-  return do_predict(c);
-}
-int ef_get_pose(ef_ctx* c, double* T16) {
-  if (!c || !T16) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  eft::TrackState h;
-  EF_HIP(c, hipMemcpyAsync(&h, c->st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  efl::SE3 T;
-  for (int i = 0; i < 4; ++i) T.q[i] = h.q[i];
-  for (int i = 0; i < 3; ++i) T.t[i] = h.t[i];
-  efl::se3_matrix(T, T16);
-  return EF_OK;
-}
-int ef_get_tick(ef_ctx* c, int* tick) { if (!c || !tick) return EF_EINVAL; *tick = c->tick; return EF_OK; }
 int ef_set_tick(ef_ctx* c, int tick) { if (!c) return EF_EINVAL; c->tick = tick; return EF_OK; }
-int ef_get_tracking_stats(ef_ctx* c, float* out6, double* A36, double* b6) {
-  if (!c || !out6) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  eft::TrackState h;
-  EF_HIP(c, hipMemcpyAsync(&h, c->st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  out6[0] = h.lastICPError; out6[1] = h.lastICPCount; out6[2] = h.lastRGBError;
-  out6[3] = h.lastRGBCount; out6[4] = h.lastSO3Error; out6[5] = h.lastSO3Count;
-  if (A36) memcpy(A36, h.lastA, sizeof(h.lastA));
-  if (b6) memcpy(b6, h.lastb, sizeof(h.lastb));
-  return EF_OK;
-}
-int ef_get_covariance(ef_ctx* c, double* cov36) {
-  if (!c || !cov36) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  eft::TrackState h;
-  EF_HIP(c, hipMemcpyAsync(&h, c->st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  efl::lu_inverse<double, 6>(h.lastA, cov36);   // host side, like the reference (Eigen on the CPU)
-  return EF_OK;
-}
-int ef_get_tracker_fallbacks(ef_ctx* c, int* count) {
-  if (!c || !count) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  int total = 0;
-  for (const eft::Pyramid* p : {&c->pyr, &c->pyr2, &c->pyr3}) {
-    const int n = eft::tracker_fallbacks(*p, c->stream);
-    if (n < 0) { c->err = "reading the tracker's fallback counter failed"; return EF_EHIP; }
-    total += n;
-  }
-  *count = total;
-  return EF_OK;
-}
 // developer instrumentation (tests/test_gpu_fallback.py): `workgroups` workgroups of 1024 threads and 128 registers per lane — each fills the
 // register file of a whole CU — spin for `microseconds` on a stream of their own: the chip is partly taken, as by another process
 __global__ void __launch_bounds__(1024) k_debug_occupy(unsigned long long ticks, unsigned* started) {
@@ -1800,59 +1062,6 @@ int ef_debug_occupy(ef_ctx* c, int workgroups, int microseconds) {
   if (*started < (unsigned)workgroups) { c->err = "ef_debug_occupy: the spinners did not become resident"; return EF_EHIP; }
   return EF_OK;
 }
-// test hook: raises the sticky abort flag of the frame tracker's persistent launches, as a wait that timed out would
-int ef_debug_inject_tracker_abort(ef_ctx* c) {
-  if (!c) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  unsigned* w = eft::tracker_abort_word(c->pyr);
-  if (!w) return EF_EINVAL;
-  const unsigned one = 1u;
-  EF_HIP(c, hipMemcpyAsync(w, &one, sizeof(one), hipMemcpyHostToDevice, c->stream));
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  return EF_OK;
-}
-// developer instrumentation: per-phase clocks of the persistent small-level launch (-DEF_STAGE_CLOCKS builds; tools/small_clocks.py)
-int ef_debug_small_clocks(ef_ctx* c, unsigned long long* out32) {
-  if (!c || !out32) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  return eft::tracker_small_clocks(c->pyr, out32, c->stream) == 0 ? EF_OK : EF_EHIP;
-}
-int ef_debug_clocks(ef_ctx* c, unsigned long long* out16) {
-  if (!c || !out16) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  eft::TrackState h;
-  EF_HIP(c, hipMemcpyAsync(&h, c->st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  memcpy(out16, h.dbg_clock, sizeof(h.dbg_clock));
-  return EF_OK;
-}
-int ef_get_trajectory(ef_ctx* c, double* T16s, int64_t* stamps, int max_frames, int* n_frames) {
-  if (!c || !n_frames) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  int n = (int)c->stamps.size();
-  if (n > max_frames) n = max_frames;
-  if (T16s && n) {
-    const int rf = flush_end_record(c);
-    if (rf != EF_OK) return rf;
-    EF_HIP(c, hipMemcpyAsync(T16s, c->traj, (size_t)n * 16 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    EF_HIP(c, hipStreamSynchronize(c->stream));
-    // "Output deformed pose graph" (ElasticFusion.cpp:107-139): every accepted Deformation::constrain moves the poses logged so far
-    // (DeformationGraph::applyGraphToPoses), so with loop closures on the log to hand out is the closure object's copy of t_T_wc — the
-    // device log holds each frame's pose as it was when the frame ended.  The closure object logs one pose per frame from the frame
-    // ef_enable_global_closure was called before: it covers the LAST `m` frames.
-    if (c->closure) {
-      const int total = (int)c->stamps.size(), m = ef_closure_trajectory(c->closure, nullptr, 0), first = total - m;
-      if (m > 0 && first >= 0 && first < n) {
-        std::vector<double> P((size_t)m * 16);
-        ef_closure_trajectory(c->closure, P.data(), m);
-        memcpy(T16s + (size_t)first * 16, P.data(), (size_t)(n - first) * 16 * sizeof(double));
-      }
-    }
-  }
-  if (stamps) for (int i = 0; i < n; ++i) stamps[i] = c->stamps[i];
-  *n_frames = n;
-  return EF_OK;
-}
 // clean() clamps the new surfel count to the capacity and raises a device flag (the reference's fixed 3072 x 3072 vertex
 // buffer simply overflows, GlobalModel.cpp:22-24).  The flag is a WARNING: ef_synchronize reports it once (EF_ECAPACITY) and
 // clears it; the clamped map stays readable (ef_map_count / ef_map_download / ef_save_ply proceed with the clamped count).
@@ -1865,37 +1074,6 @@ static int check_capacity(ef_ctx* c) {
     c->err = "surfel capacity exceeded (ef_config.max_surfels = " + std::to_string(c->capacity) + "): the newest surfels were dropped";
     return EF_ECAPACITY;
   }
-  return EF_OK;
-}
-int ef_map_count(ef_ctx* c, uint32_t* count) {
-  if (!c || !count) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  EF_HIP(c, hipMemcpyAsync(count, &c->st->map_counts[c->cur], sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  return EF_OK;
-}
-int ef_map_download(ef_ctx* c, float* surfels, uint32_t max_surfels, uint32_t* count) {
-  if (!c || !count) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  if (c->labels.ids_on) {   // rows created since the last ID-consuming call get theirs first
-    const int ri = ids_prepare(c, "ef_map_download");
-    if (ri != EF_OK) return ri;
-  }
-  uint32_t n = 0;
-  int r = ef_map_count(c, &n);
-  if (r != EF_OK) return r;
-  if (n > max_surfels) n = max_surfels;
-  *count = n;
-  if (!surfels || !n) return EF_OK;
-  // The reference's downloadMap() reads the buffer its update pass wrote — the map BEFORE clean — truncated to the count AFTER
-  // clean (quirk Q14); by default this returns model(), the map as it stands; ef_set_reference_download selects the reference's.
-  float* tmp = nullptr;
-  EF_HIP(c, hipMalloc((void**)&tmp, (size_t)n * 48));
-  efm::soa_to_aos(c->reference_download ? c->shadow : c->maps[c->cur], n, tmp, c->stream);
-  hipError_t e = hipMemcpyAsync(surfels, tmp, (size_t)n * 48, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(tmp);
-  EF_HIP(c, e);
   return EF_OK;
 }
 int ef_set_reference_download(ef_ctx* c, int on) {
@@ -1929,16 +1107,6 @@ int ef_map_upload(ef_ctx* c, const float* surfels, uint32_t count) {
   if (c->labels.ids_on) return ids_uploaded(c, count);
   return EF_OK;
 }
-int ef_get_pose_qt(ef_ctx* c, double* q4_t3) {
-  if (!c || !q4_t3) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  eft::TrackState h;
-  EF_HIP(c, hipMemcpyAsync(&h, c->st, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  for (int i = 0; i < 4; ++i) q4_t3[i] = h.q[i];
-  for (int i = 0; i < 3; ++i) q4_t3[4 + i] = h.t[i];
-  return EF_OK;
-}
 // Resume from a checkpoint (include/ef_hip.h): the end-of-frame state of the frame `rgb_prev` / `depth_prev` was, on the uploaded map
 int ef_restore_state(ef_ctx* c, int tick, const double* q4_t3, const uint8_t* rgb_prev, const uint16_t* depth_prev) {
   if (!c || !q4_t3 || !rgb_prev || !depth_prev || tick < 2) return EF_EINVAL;
@@ -1952,17 +1120,17 @@ int ef_restore_state(ef_ctx* c, int tick, const double* q4_t3, const uint8_t* rg
     const int fr = flush_end_record(c);
     if (fr != EF_OK) return fr;
   }
-  EF_HIP(c, hipMemcpyAsync(c->rgb, rgb_prev, (size_t)W * H * 3, hipMemcpyHostToDevice, s));
-  EF_HIP(c, hipMemcpyAsync(c->depth_raw, depth_prev, (size_t)W * H * 2, hipMemcpyHostToDevice, s));
+  EF_HIP(c, hipMemcpyAsync(c->img.rgb, rgb_prev, (size_t)W * H * 3, hipMemcpyHostToDevice, s));
+  EF_HIP(c, hipMemcpyAsync(c->img.depth_raw, depth_prev, (size_t)W * H * 2, hipMemcpyHostToDevice, s));
   EF_HIP(c, hipStreamSynchronize(s));   // the caller's buffers are pageable and only borrowed
-  if (!efm::preprocess_depth(c->depth_raw, W, H, c->cfg.depth_cut, c->depth_filtered, c->depth_metric, c->depth_metric_filtered, s, 0u, nullptr,
+  if (!efm::preprocess_depth(c->img.depth_raw, W, H, c->cfg.depth_cut, c->img.depth_filtered, c->img.depth_metric, c->img.depth_metric_filtered, s, 0u, nullptr,
                              nullptr, nullptr, c->bil_table)) {
     c->err = "bilateral weight table missing on this device";
     return EF_EHIP;
   }
   // the frame's intensity pyramid where the next frame's SO(3) pre-alignment looks for it (lastNextImage: initFirstRGB's target and,
   // after every tracked frame, the swapped-in nextImage, RGBDOdometry.cpp:246-257,284-288)
-  eft::init_first_rgb(c->pyr, c->rgb, s);
+  eft::init_first_rgb(c->pyr, c->img.rgb, s);
   efl::SE3 T;
   for (int i = 0; i < 4; ++i) T.q[i] = q4_t3[i];
   for (int i = 0; i < 3; ++i) T.t[i] = q4_t3[4 + i];
@@ -1976,69 +1144,6 @@ int ef_restore_state(ef_ctx* c, int tick, const double* q4_t3, const uint8_t* rg
   EF_HIP(c, hipGetLastError());
   return r;
 }
-// Host-only writers (no context, no GPU): the two dumps of the reference, byte for byte.
-//   trajectory: ~ElasticFusion, ElasticFusion.cpp:112-139 — "timestamp tx ty tz qx qy qz qw" per pose, the timestamp as microseconds / 1e6
-//     with six decimals, the seven numbers as an ostream prints a double by default (six significant digits, %g);
-//   map: ElasticFusion::savePly, :684-781 — binary little-endian PLY of the surfels with confidence above the threshold:
-//     x y z, r g b unpacked from the colour float, the NEGATED normal (:741-743), the radius.
-int ef_write_freiburg(const char* path, const double* T_wc16_array, const int64_t* timestamps, int n) {
-  if (!path || (n > 0 && (!T_wc16_array || !timestamps))) return EF_EINVAL;
-  FILE* f = fopen(path, "w");
-  if (!f) return EF_EINVAL;
-  for (int i = 0; i < n; ++i) {
-    const efl::SE3 S = efl::se3_from_matrix(T_wc16_array + (size_t)i * 16);
-    fprintf(f, "%.6f %g %g %g %g %g %g %g\n", (double)timestamps[i] / 1000000.0, S.t[0], S.t[1], S.t[2], S.q[0], S.q[1], S.q[2], S.q[3]);
-  }
-  fclose(f);
-  return EF_OK;
-}
-int ef_write_ply(const char* path, const float* surfels, uint32_t count, float confidence_threshold) {
-  if (!path || (count > 0 && !surfels)) return EF_EINVAL;
-  uint32_t valid = 0;
-  for (uint32_t i = 0; i < count; ++i) valid += surfels[(size_t)i * 12 + 3] > confidence_threshold;
-  FILE* f = fopen(path, "wb");
-  if (!f) return EF_EINVAL;
-  fprintf(f, "ply\nformat binary_little_endian 1.0\nelement vertex %u\nproperty float x\nproperty float y\nproperty float z\n"
-             "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty float nx\nproperty float ny\nproperty float nz\n"
-             "property float radius\nend_header\n", valid);
-  for (uint32_t i = 0; i < count; ++i) {
-    const float* s = surfels + (size_t)i * 12;
-    if (!(s[3] > confidence_threshold)) continue;
-    const int col = (int)s[4];
-    const unsigned char rgbc[3] = {(unsigned char)((col >> 16) & 0xFF), (unsigned char)((col >> 8) & 0xFF), (unsigned char)(col & 0xFF)};
-    const float nr[4] = {s[8] * -1, s[9] * -1, s[10] * -1, s[11]};
-    fwrite(s, sizeof(float), 3, f);
-    fwrite(rgbc, 1, 3, f);
-    fwrite(nr, sizeof(float), 4, f);
-  }
-  fclose(f);
-  return EF_OK;
-}
-int ef_save_freiburg(ef_ctx* c, const char* path) {
-  if (!c || !path) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  const int n = (int)c->stamps.size();
-  std::vector<double> T((size_t)n * 16);
-  int got = 0;
-  int r = ef_get_trajectory(c, T.data(), nullptr, n, &got);
-  if (r != EF_OK) return r;
-  r = ef_write_freiburg(path, T.data(), c->stamps.data(), got);
-  if (r != EF_OK) c->err = std::string("cannot open ") + path;
-  return r;
-}
-int ef_save_ply(ef_ctx* c, const char* path) {
-  if (!c || !path) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  uint32_t n = 0;
-  int r = ef_map_count(c, &n);
-  if (r != EF_OK) return r;
-  std::vector<float> m((size_t)n * 12);
-  r = ef_map_download(c, m.data(), n, &n);
-  if (r != EF_OK) return r;
-  r = ef_write_ply(path, m.data(), n, c->cfg.confidence);
-  if (r != EF_OK) c->err = std::string("cannot open ") + path;
-  return r;
-}
 int ef_set_rgb_only(ef_ctx* c, int v) { if (!c) return EF_EINVAL; c->cfg.rgb_only = v; return EF_OK; }
 int ef_set_icp_weight(ef_ctx* c, float v) { if (!c) return EF_EINVAL; c->cfg.icp_weight = v; return EF_OK; }
 int ef_set_pyramid(ef_ctx* c, int v) { if (!c) return EF_EINVAL; c->cfg.pyramid = v; return EF_OK; }
@@ -2048,258 +1153,11 @@ int ef_set_frame_to_frame_rgb(ef_ctx* c, int v) { if (!c) return EF_EINVAL; c->c
 int ef_set_confidence_threshold(ef_ctx* c, float v) { if (!c) return EF_EINVAL; c->cfg.confidence = v; return EF_OK; }
 int ef_set_depth_cutoff(ef_ctx* c, float v) { if (!c) return EF_EINVAL; c->cfg.depth_cut = v; return EF_OK; }
 
-// the four index maps of the last fusing frame, resolved now from the keys its second predictIndices left (ef_ctx::zbuf_clean)
-static void im_materialise(ef_ctx* c) {
-  if (!c->im_pending) return;
-  efm::resolve_indices(c->cam, c->im_T16, c->maps[c->im_map], c->zbuf_clean, c->im, c->stream);
-  c->im_pending = false;
-}
-int ef_get_image(ef_ctx* c, int which, void* dst, size_t bytes) {
-  if (!c || !dst) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  const size_t P = (size_t)c->cam.cols * c->cam.rows;
-  if (which >= EF_IMG_INDEX && which <= EF_IMG_NORM_RAD) im_materialise(c);
-  const void* src = nullptr;
-  size_t need = 0;
-  switch (which) {
-    case EF_IMG_DEPTH_FILTERED: src = c->depth_filtered; need = P * 2; break;
-    case EF_IMG_DEPTH_METRIC: src = c->depth_metric; need = P * 4; break;
-    case EF_IMG_DEPTH_METRIC_FILTERED: src = c->depth_metric_filtered; need = P * 4; break;
-    case EF_IMG_PREDICT_IMAGE: src = c->pm.image; need = P * 4; break;
-    case EF_IMG_PREDICT_VERTEX: src = c->pm.vertex; need = P * 16; break;
-    case EF_IMG_PREDICT_NORMAL: src = c->pm.normal; need = P * 16; break;
-    case EF_IMG_PREDICT_TIME: src = c->pm.time; need = P * 2; break;
-    case EF_IMG_FILL_IMAGE: src = c->fm.image; need = P * 4; break;
-    case EF_IMG_FILL_VERTEX: src = c->fm.vertex; need = P * 16; break;
-    case EF_IMG_FILL_NORMAL: src = c->fm.normal; need = P * 16; break;
-    case EF_IMG_INDEX: src = c->im.index; need = P * 4; break;
-    case EF_IMG_VERT_CONF: src = c->im.vert_conf; need = P * 16; break;
-    case EF_IMG_COLOR_TIME: src = c->im.color_time; need = P * 16; break;
-    case EF_IMG_NORM_RAD: src = c->im.norm_rad; need = P * 16; break;
-    case EF_IMG_OLD_IMAGE: src = c->old.image; need = P * 4; break;
-    case EF_IMG_OLD_VERTEX: src = c->old.vertex; need = P * 16; break;
-    case EF_IMG_OLD_NORMAL: src = c->old.normal; need = P * 16; break;
-    case EF_IMG_OLD_TIME: src = c->old.time; need = P * 2; break;
-    default: c->err = "ef_get_image: unknown image"; return EF_EINVAL;
-  }
-  if (!src) { c->err = "ef_get_image: this image only exists in a close_loops context"; return EF_ESTATE; }
-  if (bytes < need) { c->err = "ef_get_image: destination too small"; return EF_EINVAL; }
-  void* tmp = nullptr;
-  if (c->im.colmajor && which >= EF_IMG_INDEX && which <= EF_IMG_NORM_RAD) {
-    EF_HIP(c, hipMalloc(&tmp, need));
-    const int W = c->cam.cols, H = c->cam.rows;
-    const dim3 g((unsigned)((P + 255) / 256));
-    if (which == EF_IMG_INDEX) hipLaunchKernelGGL(k_to_rowmajor<uint32_t>, g, dim3(256), 0, c->stream, (const uint32_t*)src, W, H, (uint32_t*)tmp);
-    else hipLaunchKernelGGL(k_to_rowmajor<float4>, g, dim3(256), 0, c->stream, (const float4*)src, W, H, (float4*)tmp);
-    src = tmp;
-  }
-  hipError_t e = hipMemcpyAsync(dst, src, need, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (tmp) (void)hipFree(tmp);
-  EF_HIP(c, e);
-  return EF_OK;
-}
-int ef_get_image_resized(ef_ctx* c, int which, int factor, void* dst, size_t bytes) {
-  if (!c || !dst || factor < 1) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  const int W = c->cam.cols, H = c->cam.rows, dw = W / factor, dh = H / factor;
-  const void* src = nullptr;
-  int elem = 0;
-  switch (which) {
-    case EF_IMG_PREDICT_IMAGE: src = c->pm.image; elem = 4; break;
-    case EF_IMG_PREDICT_VERTEX: src = c->pm.vertex; elem = 16; break;
-    case EF_IMG_PREDICT_NORMAL: src = c->pm.normal; elem = 16; break;
-    case EF_IMG_PREDICT_TIME: src = c->pm.time; elem = 2; break;
-    case EF_IMG_FILL_IMAGE: src = c->fm.image; elem = 4; break;
-    case EF_IMG_FILL_VERTEX: src = c->fm.vertex; elem = 16; break;
-    case EF_IMG_FILL_NORMAL: src = c->fm.normal; elem = 16; break;
-    case EF_IMG_OLD_IMAGE: src = c->old.image; elem = 4; break;
-    case EF_IMG_OLD_VERTEX: src = c->old.vertex; elem = 16; break;
-    case EF_IMG_OLD_NORMAL: src = c->old.normal; elem = 16; break;
-    case EF_IMG_OLD_TIME: src = c->old.time; elem = 2; break;
-    default: c->err = "ef_get_image_resized: a predicted, fill-in or inactive-prediction image"; return EF_EINVAL;
-  }
-  if (!src) { c->err = "ef_get_image_resized: this image only exists in a close_loops context"; return EF_ESTATE; }
-  const size_t need = (size_t)dw * dh * elem;
-  if (dw == 0 || dh == 0 || bytes < need) { c->err = "ef_get_image_resized: destination too small"; return EF_EINVAL; }
-  void* tmp = nullptr;
-  EF_HIP(c, hipMalloc(&tmp, need));
-  const dim3 g((unsigned)((dw * dh + 255) / 256));
-  if (elem == 16) hipLaunchKernelGGL(k_resize_nearest<float4>, g, dim3(256), 0, c->stream, (const float4*)src, W, dw, dh, factor, (float4*)tmp);
-  else if (elem == 4) hipLaunchKernelGGL(k_resize_nearest<uint32_t>, g, dim3(256), 0, c->stream, (const uint32_t*)src, W, dw, dh, factor, (uint32_t*)tmp);
-  else hipLaunchKernelGGL(k_resize_nearest<uint16_t>, g, dim3(256), 0, c->stream, (const uint16_t*)src, W, dw, dh, factor, (uint16_t*)tmp);
-  hipError_t e = hipMemcpyAsync(dst, tmp, need, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(tmp);
-  EF_HIP(c, e);
-  return EF_OK;
-}
-int ef_get_tracker_buffer(ef_ctx* c, int which, int level, void* dst, size_t bytes) {
-  if (!c || !dst || level < 0 || level >= eft::NUM_PYRS) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  const size_t n = (size_t)(c->cam.cols >> level) * (c->cam.rows >> level);
-  const void* src = nullptr;
-  size_t need = 0;
-  const eft::Pyramid& p = c->pyr;
-  switch (which) {
-    case 0: src = p.vmap_curr[level]; need = n * 12; break;
-    case 1: src = p.nmap_curr[level]; need = n * 12; break;
-    case 2: src = p.vmap_g_prev[level]; need = n * 12; break;
-    case 3: src = p.nmap_g_prev[level]; need = n * 12; break;
-    case 4: case 5: src = p.lastDepth[level]; need = n * 4; break;
-    case 6: src = p.lastImage[level]; need = n; break;
-    case 7: src = p.nextImage[level]; need = n; break;
-    case 8: src = p.lastNextImage[level]; need = n; break;
-    case 9: src = p.dIdx[level]; need = n * 2; break;
-    case 10: src = p.dIdy[level]; need = n * 2; break;
-    case 11: src = level == 0 ? c->depth_filtered : p.depth_tmp[level]; need = n * 2; break;
-    default: c->err = "ef_get_tracker_buffer: unknown buffer"; return EF_EINVAL;
-  }
-  if (bytes < need) { c->err = "ef_get_tracker_buffer: destination too small"; return EF_EINVAL; }
-  EF_HIP(c, hipMemcpyAsync(dst, src, need, hipMemcpyDeviceToHost, c->stream));
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  return EF_OK;
-}
-
-int ef_enable_timing(ef_ctx* c, int on) { if (!c) return EF_EINVAL; c->timing = on != 0; return EF_OK; }
-int ef_get_timings(ef_ctx* c, ef_timing* out, int max, int* n) {
-  if (!c || !n) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  int k = 0;
-  for (auto& t : c->timers) {
-    if (!t.used || k >= max) continue;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, t.a, t.b) != hipSuccess) ms = -1.f;
-    if (out) { out[k].name = t.name; out[k].ms = ms; }
-    ++k;
-  }
-  *n = k;
-  return EF_OK;
-}
-
-// ---- device helpers ----
-int ef_kernel_timing(ef_ctx* c, int every_n_frames) {
-  if (!c || every_n_frames < 0) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  c->ktime_every = every_n_frames;
-  c->probe.used = 0;
-  c->probe_splat.used = 0;
-  c->probe_all.used = 0;
-  if (every_n_frames > 0 && c->ka_start.empty()) {
-    const int cap = 1024;
-    c->ka_start.resize(cap);
-    c->ka_stop.resize(cap);
-    for (int i = 0; i < cap; ++i) {
-      EF_HIP(c, hipEventCreate(&c->ka_start[i]));
-      EF_HIP(c, hipEventCreate(&c->ka_stop[i]));
-    }
-    c->probe_all = eft::KernelProbe{c->ka_start.data(), c->ka_stop.data(), cap, 0};
-  }
-  if (every_n_frames > 0 && c->ks_start.empty()) {
-    const int cap = 1024;
-    c->ks_start.resize(cap);
-    c->ks_stop.resize(cap);
-    for (int i = 0; i < cap; ++i) {
-      EF_HIP(c, hipEventCreate(&c->ks_start[i]));
-      EF_HIP(c, hipEventCreate(&c->ks_stop[i]));
-    }
-    c->probe_splat = eft::KernelProbe{c->ks_start.data(), c->ks_stop.data(), cap, 0};
-  }
-  if (every_n_frames > 0 && c->kt_start.empty()) {
-    const int cap = 4096;
-    c->kt_start.resize(cap);
-    c->kt_stop.resize(cap);
-    for (int i = 0; i < cap; ++i) {
-      EF_HIP(c, hipEventCreate(&c->kt_start[i]));
-      EF_HIP(c, hipEventCreate(&c->kt_stop[i]));
-    }
-    c->probe.start = c->kt_start.data();
-    c->probe.stop = c->kt_stop.data();
-    c->probe.capacity = cap;
-  }
-  return EF_OK;
-}
-int ef_get_kernel_timing(ef_ctx* c, ef_kernel_time* out) {
-  if (!c || !out) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  double total_ms = 0;
-  for (int i = 0; i < c->probe.used; ++i) {
-    float ms = 0;
-    EF_HIP(c, hipEventElapsedTime(&ms, c->kt_start[i], c->kt_stop[i]));
-    total_ms += ms;
-  }
-  const bool icp = !c->cfg.rgb_only && c->cfg.icp_weight > 0, rgb = c->cfg.rgb_only || c->cfg.icp_weight < 100;
-#ifdef EF_FAST_ORDER
-  out->name = "k_se3_accum_fast (level 0 of the launch-per-step script: icpStep + rgbStep Jacobian rows + fast-order sums)";
-#else
-  out->name = "k_se3_accum (level 0: icpStep + rgbStep Jacobian rows + reference-order sums)";
-#endif
-  out->launches = c->probe.used;
-  out->avg_us = c->probe.used ? (float)(1e3 * total_ms / c->probe.used) : 0.f;
-  // algorithmic bytes of ONE launch of this kernel (DESIGN.md "Roofline accounting"): icpStep 48 B per pixel-visit
-  // (4 planar float3 maps); rgbStep reads the 4-byte packed correspondence of every pixel — the
-  // reference's 16-byte DataTerm + 12-byte cloud are gone, so they are not counted — the ~10 % valid pixels' gathers
-  // (depth + 2 gradients) are left out (data dependent): a lower bound, which can only understate `achieved`
-  out->bytes_per_launch = (double)c->cam.cols * c->cam.rows * ((icp ? 48.0 : 0.0) + (rgb ? 4.0 : 0.0));
-  out->bytes_per_launch_survey = (double)c->cam.cols * c->cam.rows * (icp ? 48.0 : 0.0);   // the ICP reduction alone
-  return EF_OK;
-}
-
-// the persistent tracker launch (k_track_fast: SO(3) loop + every Gauss-Newton iteration of every level + their update steps)
-int ef_get_tracker_timing(ef_ctx* c, ef_kernel_time* out) {
-  if (!c || !out) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  double total_ms = 0;
-  for (int i = 0; i < c->probe_all.used; ++i) {
-    float ms = 0;
-    EF_HIP(c, hipEventElapsedTime(&ms, c->ka_start[i], c->ka_stop[i]));
-    total_ms += ms;
-  }
-  const bool icp = !c->cfg.rgb_only && c->cfg.icp_weight > 0, rgb = c->cfg.rgb_only || c->cfg.icp_weight < 100;
-#ifdef EF_FAST_ORDER
-  out->name = "k_track_fast (the whole tracker as one persistent launch: SO(3) loop + every ICP+RGB iteration of every level + the update steps)";
-#else
-  out->name = "k_track_ref (the whole tracker as one persistent launch, reference summation order: SO(3) loop + every ICP+RGB iteration of every level + the update steps)";
-#endif
-  out->launches = c->probe_all.used;
-  out->avg_us = c->probe_all.used ? (float)(1e3 * total_ms / c->probe_all.used) : 0.f;
-  // algorithmic bytes of one launch: every iteration visits every pixel of its level once (48 B icpStep + 4 B packed correspondence, as
-  // ef_get_kernel_timing counts one level-0 launch); the SO(3) loop's two u8 images are left out (a lower bound)
-  const int its[3] = {c->cfg.fast_odom ? 3 : 10, c->cfg.pyramid ? 5 : 0, c->cfg.pyramid ? 4 : 0};
-  double visits = 0;
-  for (int l = 0; l < 3; ++l) visits += (double)its[l] * (double)(c->cam.cols >> l) * (double)(c->cam.rows >> l);
-  out->bytes_per_launch = visits * ((icp ? 48.0 : 0.0) + (rgb ? 4.0 : 0.0));
-  out->bytes_per_launch_survey = visits * (icp ? 48.0 : 0.0);
-  return EF_OK;
-}
-
-int ef_get_splat_timing(ef_ctx* c, ef_kernel_time* out) {
-  if (!c || !out) return EF_EINVAL;
-  DeviceGuard dg_(c);
-  EF_HIP(c, hipStreamSynchronize(c->stream));
-  double total_ms = 0;
-  for (int i = 0; i < c->probe_splat.used; ++i) {
-    float ms = 0;
-    EF_HIP(c, hipEventElapsedTime(&ms, c->ks_start[i], c->ks_stop[i]));
-    total_ms += ms;
-  }
-  unsigned count = 0;
-  EF_HIP(c, hipMemcpy(&count, &c->st->map_counts[c->cur], sizeof(count), hipMemcpyDeviceToHost));
-  out->name = "k_index_splat (IndexMap::predictIndices: per-surfel transform + project + 64-bit atomicMin z-buffer)";
-  out->launches = c->probe_splat.used;
-  out->avg_us = c->probe_splat.used ? (float)(1e3 * total_ms / c->probe_splat.used) : 0.f;
-  // algorithmic bytes: the two float4 streams the pass needs (position+confidence, colour+times: 32 B / surfel; the
-  // reference's vertex shader fetches all 48) + one 8-byte z-buffer update per surfel (an upper bound: culled surfels issue none)
-  out->bytes_per_launch = 40.0 * (double)count;
-  out->bytes_per_launch_survey = 48.0 * (double)count;   // 48 B per surfel read by the reference's vertex shader
-  return EF_OK;
-}
-
 }  // extern "C"
+
+// Looking at a context: getters, timers, kernel sampling, debug hooks
+#include "ef_host_inspect.inc"
+
 
 // The map operations' host code, one file beside each kernel file of ef_map_kernels.hip, in dependency order (each may use what the ones before it define)
 #include "ef_host_ops.inc"
