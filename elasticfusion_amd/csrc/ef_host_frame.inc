@@ -92,7 +92,7 @@ int input_stage(ef_ctx* c, const FramePlan& f, const uint8_t* rgb_src, const uin
   timer_end(c, "Preprocess");
   if (f.overlap && f.overlap_mode == 2) EF_HIP(c, hipStreamWaitEvent(sb, c->ev_track_done, 0));
   if (f.track_this && f.overlap)   // the single-stream script builds all pyramids together (eft::build_pyramids, track_frame)
-    eft::build_pyramids_frame_side(c->pyr, c->img.depth_filtered, c->intr, c->maxDepthProcessed, nullptr, sb, nullptr);
+    eft::build_pyramids_frame_side(c->pyr, c->img.depth_filtered, c->intr, c->maxDepthProcessed, sb);
   if (f.overlap) EF_HIP(c, hipEventRecord(c->ev_input_done, sb));
   return EF_OK;
 }
@@ -155,10 +155,10 @@ int track_frame(ef_ctx* c, const FramePlan& f, const eft::FramePreprocess& fp, f
                       (const uint8_t*)c->fm.image, c->cfg.frame_to_frame_rgb != 0, f.joint_inputs ? &fp : nullptr, c->tally_pending);
   c->tally_pending = false;
   if (f.overlap) {
-    eft::build_pyramids_model_side(c->pyr, nullptr, nullptr, false, c->st, s);
+    eft::build_pyramids_model_side(c->pyr, s);
     EF_HIP(c, hipStreamWaitEvent(s, c->ev_input_done, 0));
   } else {
-    eft::build_pyramids(c->pyr, c->img.depth_filtered, c->intr, c->maxDepthProcessed, nullptr, nullptr, false, nullptr, c->st, s, nullptr, rgb);
+    eft::build_pyramids(c->pyr, c->img.depth_filtered, c->intr, c->maxDepthProcessed, s, rgb);
   }
   if (rgb && f.overlap) eft::init_rgb_sobel(c->pyr, s);
   timer_end(c, "odomInit");

@@ -200,8 +200,6 @@ void so3_step_op(const So3Args& a, const uint8_t* lastImage, const uint8_t* next
                  float* out11_dev, hipStream_t s);
 
 // ---- frame-tier launchers (device-resident state; nothing here synchronises) ----
-// RGBDOdometry::initICP(filteredDepth, cutoff): u16 pyramid + vertex/normal maps, RGBDOdometry.cpp:121-147
-void init_icp(const Pyramid& p, const uint16_t* depth_filtered, Intr k, float cutoff, hipStream_t s);
 // initICPModel + initRGBModel's depth half: predicted (or fill-in, chosen by the dense_count tally) float4 maps ->
 // world-frame planar pyramids + model depth L0.  RGBDOdometry.cpp:171-210, :217
 // (pred_image_rgba / fill_image_rgba given: the model's level-0 intensity image — populateRGBDData(model) — is written by the same launch)
@@ -221,33 +219,25 @@ void init_icp_model(const Pyramid& p, const float* pred_vertex, const float* pre
                     const float* fill_normal, const TrackState* st, float maxDepthRGB, hipStream_t s, const uint8_t* pred_image_rgba = nullptr,
                     const uint8_t* fill_image_rgba = nullptr, bool frameToFrameRGB = false, const FramePreprocess* with = nullptr,
                     bool tally = false /* take denseEnough()'s tally from pred_image_rgba first (ModelMapsArgs::tally_image) */);
-// the rest of populateRGBDData (RGBDOdometry.cpp:212-244, :275-279) in three independently enqueueable parts, so that
-// the part that only needs the new frame can run on the input stream while the previous frame is still being fused:
-//   model ("last"): Gaussian depth pyramid + intensity pyramid of the predicted (or fill-in) image
-//   frame ("next"): intensity pyramid of the camera image
-//   sobel: derivative images of the "next" pyramid + the iteration-invariant photometric gates (needs both)
-void init_rgb_model(const Pyramid& p, const uint8_t* pred_image_rgba, const uint8_t* fill_image_rgba, bool frameToFrameRGB,
-                    const TrackState* st, hipStream_t s);
-void init_rgb_frame(const Pyramid& p, const uint8_t* rgb3, hipStream_t s);
 // initICP(predictedVertices, predictedNormals) + initRGB(predictedImage), RGBDOdometry.cpp:149-169,241-244: the "current" side of
 // model-to-model tracking from a model prediction (camera-frame maps, nextDepth from the same vertices, intensity of the image)
 void init_icp_maps(const Pyramid& p, const float* vertex4, const float* normal4, const uint8_t* image_rgba, const TrackState* st,
                    float maxDepthRGB, hipStream_t s);
+// The rest of initICP(filteredDepth, cutoff) and populateRGBDData (RGBDOdometry.cpp:121-147, :212-244, :275-279) behind init_icp_model and the
+// pre-processing launch, which leave both level-0 intensity images and the model's level-0 depth: the pyramids of the frame's u16 depth, the model's
+// depth and both intensity images, the frame's vertex / normal maps of every level, and the derivative images of the frame's intensity pyramid with
+// the iteration-invariant photometric gates (init_rgb_sobel: needs both sides).
+// build_pyramids: all of it in three launches (single-stream frame script); with_sobel: init_rgb_sobel's work in the same launch as the maps
+void build_pyramids(const Pyramid& p, const uint16_t* depth_filtered, Intr k, float cutoff, hipStream_t s, bool with_sobel);
+// the two-stream frame script: the half that reads nothing but the new frame (it can run on the input stream while the previous frame is still
+// being fused) / the half that reads the model prediction; init_rgb_sobel follows their join
+void build_pyramids_frame_side(const Pyramid& p, const uint16_t* depth_filtered, Intr k, float cutoff, hipStream_t s);
+void build_pyramids_model_side(const Pyramid& p, hipStream_t s);
 void init_rgb_sobel(const Pyramid& p, hipStream_t s);
-// build_pyramids for the two-stream frame script: the half that reads nothing but the new frame / the half that reads the model prediction
-void build_pyramids_frame_side(const Pyramid& p, const uint16_t* depth_filtered, Intr k, float cutoff, const uint8_t* rgb3, hipStream_t s,
-                               uint8_t* rgb_keep);
-void build_pyramids_model_side(const Pyramid& p, const uint8_t* pred_image_rgba, const uint8_t* fill_image_rgba, bool frameToFrameRGB,
-                               const TrackState* st, hipStream_t s);
-// init_icp_model + init_rgb_model (model view, its own image, no fill-in) + init_icp_maps (current view) of a model-to-model tracker in five launches
+// initICPModel + initRGBModel (model view, its own image, no fill-in) + init_icp_maps (current view) of a model-to-model tracker in five launches
 void init_model_pair(const Pyramid& p, const float* model_vertex4, const float* model_normal4, const uint8_t* model_image_rgba,
                      const float* cur_vertex4, const float* cur_normal4, const uint8_t* cur_image_rgba, const TrackState* st, float maxDepthRGB,
                      hipStream_t s);
-// init_icp + init_rgb_model + init_rgb_frame in three launches (single-stream frame script; needs init_icp_model first)
-void build_pyramids(const Pyramid& p, const uint16_t* depth_filtered, Intr k, float cutoff, const uint8_t* pred_image_rgba,
-                    const uint8_t* fill_image_rgba, bool frameToFrameRGB, const uint8_t* rgb3, const TrackState* st, hipStream_t s,
-                    uint8_t* rgb_keep = nullptr,    // rgb_keep: also store the frame's RGB there (the caller's buffer is only borrowed)
-                    bool with_sobel = false);       // with_sobel: init_rgb_sobel's work in the same launch as the vertex / normal maps
 // initFirstRGB, RGBDOdometry.cpp:246-257
 void init_first_rgb(const Pyramid& p, const uint8_t* rgb3, hipStream_t s);
 // getIncrementalTransformation, RGBDOdometry.cpp:259-571, entirely enqueued.  The update step of an iteration is evaluated at the head of the
@@ -279,7 +269,7 @@ void track_prepare(Pyramid& p, const TrackParams& tp, hipStream_t s);
 int tracker_fallbacks(const Pyramid& p, hipStream_t s);
 // a stream that launched persistent trackers is about to be destroyed (or synchronised for good): the per-device chain must not record on it
 void persistent_chain_forget(hipStream_t s);
-int tracker_small_clocks(const Pyramid& p, unsigned long long* out32, hipStream_t s);   // developer instrumentation (-DEF_STAGE_CLOCKS)
+int tracker_small_clocks(const Pyramid& p, unsigned long long* out32, hipStream_t s);   // developer instrumentation (-DEF_STAGE_CLOCKS): the clock sums of the script run last, read and reset
 void track_swap(Pyramid& p, const TrackParams& tp);   // the pointer swap track() ends with (for hipGraph replay)
 // tail of getIncrementalTransformation (0.3 m guard, SVD re-orthonormalisation, RGBDOdometry.cpp:555-570) +
 // velocity weighting (ElasticFusion.cpp:369-383) + the float matrices of the map passes

@@ -11,7 +11,9 @@
 #include "ef_linalg_dev.hpp"
 #include "ef_solve_dev.hpp"
 #include <stddef.h>
+#include <initializer_list>
 #include <mutex>
+#include <type_traits>
 #include <hip/hip_ext.h>
 #include "ef_track.hpp"
 
@@ -330,6 +332,24 @@ __global__ void k_bgr_to_intensity(const uint8_t* __restrict__ src, int n, uint8
   const uint8_t* s = src + (size_t)i * CH;
   dst[i] = intensity_of((float)s[0], (float)s[1], (float)s[2]);
 }
+__device__ __forceinline__ bool use_fill_in(const TrackState* __restrict__ st);   // (with the model-side maps below)
+// model intensity L0 comes from the predicted image unless the device-side flag says fill-in
+__global__ void k_model_intensity(const uint8_t* __restrict__ pred, const uint8_t* __restrict__ fill, bool force_fill,
+                                  const TrackState* __restrict__ st, int n, uint8_t* __restrict__ dst) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t* src = (force_fill || use_fill_in(st)) ? fill : pred;
+  const uchar4 c = ((const uchar4*)src)[i];
+  dst[i] = intensity_of((float)c.x, (float)c.y, (float)c.z);
+}
+// level-0 intensity of two RGBA images in one launch: blockIdx.y 0 = the model image ("last"), 1 = the current side's ("next")
+__global__ void k_rgba_intensity_pair(const uint8_t* __restrict__ last_rgba, const uint8_t* __restrict__ next_rgba, int n, uint8_t* __restrict__ last0,
+                                      uint8_t* __restrict__ next0) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uchar4 c = ((const uchar4*)(blockIdx.y == 0 ? last_rgba : next_rgba))[i];
+  (blockIdx.y == 0 ? last0 : next0)[i] = intensity_of((float)c.x, (float)c.y, (float)c.z);
+}
 
 // applyKernel, cudafuncs.cu:612-637 (quirk Q6 kept: the kernel index k counts down over the taps the clipped loops VISIT, so it shifts
 // at the image border).  Round 5: the nine taps come preloaded (v[dj + 1][di + 1], anything where the tap is outside the image) and the
@@ -493,7 +513,7 @@ struct ModelMapsArgs {
   int cols, rows;
   float maxDepthRGB;
   bool camera_frame;   // initICP(predictedVertices, predictedNormals): copyMaps + resize only, no tranformMaps
-  // optional (round 6): the model's level-0 intensity image rides along (k_intensity_both's model half: the same texels are in flight here)
+  // optional (round 6): the model's level-0 intensity image rides along (the same texels are in flight here)
   const uint8_t* pred_image;
   const uint8_t* fill_image;
   bool force_fill_image;
@@ -3009,818 +3029,11 @@ __global__ void __launch_bounds__(256) k_frame_inputs(const PreArgs P, const Mod
 #include "ef_track_ref_persistent.inc"
 #endif
 
-inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
-
 }  // namespace
 
-// ------------------------------------------------------------------------------------------
-// launchers
-// ------------------------------------------------------------------------------------------
-void pyr_down_u16(const uint16_t* src, int scols, int srows, uint16_t* dst, hipStream_t s) {
-  hipLaunchKernelGGL(k_pyr_down_u16, tile_grid(scols / 2, srows / 2), tile_block(), 0, s, src, scols, srows, dst);
-}
-void create_vmap(const uint16_t* depth, int cols, int rows, Intr k, float cutoff, float* vmap, hipStream_t s) {
-  hipLaunchKernelGGL(k_create_vmap, tile_grid(cols, rows), tile_block(), 0, s, depth, cols, rows, 1.f / k.fx, 1.f / k.fy, k.cx, k.cy, cutoff, vmap);
-}
-void create_nmap(const float* vmap, int cols, int rows, float* nmap, hipStream_t s) {
-  hipLaunchKernelGGL(k_create_nmap, tile_grid(cols, rows), tile_block(), 0, s, vmap, cols, rows, nmap);
-}
-void transform_maps(const float* vsrc, const float* nsrc, int cols, int rows, const float* R9_dev, const float* t3_dev, float* vdst,
-                    float* ndst, hipStream_t s) {
-  hipLaunchKernelGGL(k_transform_maps, tile_grid(cols, rows), tile_block(), 0, s, vsrc, nsrc, cols, rows, R9_dev, t3_dev, vdst, ndst);
-}
-void copy_maps(const float* vtex, const float* ntex, int cols, int rows, float* vmaps_tmp, float* vmap, float* nmap, hipStream_t s) {
-  hipLaunchKernelGGL(k_copy_maps, tile_grid(cols, rows), tile_block(), 0, s, (const float4*)vtex, (const float4*)ntex, cols, rows,
-                     (float4*)vmaps_tmp, vmap, nmap);
-}
-void resize_map(const float* in, int scols, int srows, float* out, bool normalize, hipStream_t s) {
-  if (normalize) hipLaunchKernelGGL(k_resize_map<true>, tile_grid(scols / 2, srows / 2), tile_block(), 0, s, in, scols, srows, out);
-  else hipLaunchKernelGGL(k_resize_map<false>, tile_grid(scols / 2, srows / 2), tile_block(), 0, s, in, scols, srows, out);
-}
-void pyr_down_gauss_f(const float* src, int scols, int srows, float* dst, hipStream_t s) {
-  hipLaunchKernelGGL(k_pyr_down_gauss_f, tile_grid(scols / 2, srows / 2), tile_block(), 0, s, src, scols, srows, dst);
-}
-void pyr_down_uchar_gauss(const uint8_t* src, int scols, int srows, uint8_t* dst, hipStream_t s) {
-  hipLaunchKernelGGL(k_pyr_down_uchar_gauss, tile_grid(scols / 2, srows / 2), tile_block(), 0, s, src, scols, srows, dst);
-}
-void vertices_to_depth(const float* vmaps_tmp, int cols, int rows, float cutoff, float* dst, hipStream_t s) {
-  hipLaunchKernelGGL(k_vertices_to_depth, tile_grid(cols, rows), tile_block(), 0, s, (const float4*)vmaps_tmp, cols, rows, cutoff, dst);
-}
-void bgr_to_intensity(const uint8_t* src, int channels, int cols, int rows, uint8_t* dst, hipStream_t s) {
-  const int n = cols * rows;
-  if (channels == 4) hipLaunchKernelGGL(k_bgr_to_intensity<4>, dim3(ceil_div(n, 256)), dim3(256), 0, s, src, n, dst);
-  else hipLaunchKernelGGL(k_bgr_to_intensity<3>, dim3(ceil_div(n, 256)), dim3(256), 0, s, src, n, dst);
-}
-void derivative_images(const uint8_t* src, int cols, int rows, int16_t* dx, int16_t* dy, hipStream_t s) {
-  hipLaunchKernelGGL(k_sobel, tile_grid(cols, rows), tile_block(), 0, s, src, cols, rows, dx, dy);
-}
-void project_to_point_cloud(const float* depth, int cols, int rows, Intr k, float* cloud, hipStream_t s) {
-  hipLaunchKernelGGL(k_project_points, tile_grid(cols, rows), tile_block(), 0, s, depth, cols, rows, 1.0f / k.fx, 1.0f / k.fy, k.cx, k.cy, cloud);
-}
-
-namespace {
-// one normal-equation accumulation launch (either tier); start / stop: optional events that receive the kernel's own begin / end
-// timestamps (hipExtLaunchKernelGGL: what rocprofv3 --kernel-trace reports as the dispatch's duration)
-template <bool HAS_ICP, bool HAS_RGB, bool PACKED>
-void launch_accum(const IcpView& IV, const RgbView& RV, const Se3Inputs& in, int N, const Se3Out& out, hipStream_t s, hipEvent_t start = nullptr,
-                  hipEvent_t stop = nullptr) {
-#ifdef EF_FAST_ORDER
-  {   // one workgroup per group of four tasks, four wavefronts per term (ef_track_fast.inc)
-    const FastPlan fp = fast_plan(N);
-    const dim3 fgrid(in.xcd_swizzle ? 8 * fast_groups_per_xcd(fp.NG) : fp.NG), fblock(256 * ((HAS_ICP && HAS_RGB) ? 2 : 1));
-    hipExtLaunchKernelGGL((k_se3_accum_fast<HAS_ICP, HAS_RGB, PACKED>), fgrid, fblock, 0, s, start, stop, 0, IV, RV, in, out.pairs);
-  }
-#else
-  constexpr int BLOCK = 64 * 2 * ACC_NW * ((HAS_ICP && HAS_RGB) ? 2 : 1);
-  const dim3 grid(VWARPS / ACC_NW), block(BLOCK);
-  // CH = steps (of four passes) a wavefront has in flight per round: 640x480 has 19 passes = 5 steps = ONE round of CH = 5; 1280x960 has
-  // 75 passes = 19 steps = four dependent rounds.  CH = 10 there (two rounds, 231 registers: the launch runs two wavefronts per SIMD
-  // anyway) was measured SLOWER: 28.4 vs 25.1 us (profiles/r03f_ab_fused_step_and_ch10.log) — twice the loads per round queue behind each
-  // other in the CU's one address pipe for longer than the two saved round trips.
-#ifdef EF_VISIT_PAIRS
-  // (round 6: two visits per lane — a round is CH / 2 packed evaluations; 640x480: 5 steps = one round of CH = 6, the sixth step empty;
-  // 1280x960: 19 steps = five rounds of CH = 4)
-  if (HAS_ICP || PACKED) {
-    const int S = ((N + VTHREADS - 1) / VTHREADS + 3) >> 2;
-    if (S <= 2) hipExtLaunchKernelGGL((k_se3_accum<2, HAS_ICP, HAS_RGB, PACKED>), grid, block, 0, s, start, stop, 0, IV, RV, in, out);
-    else if (S % 6 == 0 || S % 6 == 5 || !(S % 4 == 0 || S % 4 == 3)) hipExtLaunchKernelGGL((k_se3_accum<6, HAS_ICP, HAS_RGB, PACKED>), grid, block, 0, s, start, stop, 0, IV, RV, in, out);
-    else hipExtLaunchKernelGGL((k_se3_accum<4, HAS_ICP, HAS_RGB, PACKED>), grid, block, 0, s, start, stop, 0, IV, RV, in, out);
-    return;
-  }
-#endif
-  if (N > 8 * VTHREADS) hipExtLaunchKernelGGL((k_se3_accum<5, HAS_ICP, HAS_RGB, PACKED>), grid, block, 0, s, start, stop, 0, IV, RV, in, out);
-  else hipExtLaunchKernelGGL((k_se3_accum<2, HAS_ICP, HAS_RGB, PACKED>), grid, block, 0, s, start, stop, 0, IV, RV, in, out);
-#endif
-}
-}  // namespace
-
-namespace {
-// fast order: groups of a level / workgroups of a so3Step launch (one per group, XCD-contiguous); the reference order ignores the former
-inline int op_groups(int N) {
-#ifdef EF_FAST_ORDER
-  return fast_plan(N).NG;
-#else
-  (void)N;
-  return 0;
-#endif
-}
-inline int so3_grid(int N) {
-#ifdef EF_FAST_ORDER
-  return 8 * fast_groups_per_xcd(fast_plan(N).NG);
-#else
-  (void)N;
-  return VWARPS / SO3_WPB;
-#endif
-}
-}  // namespace
-
-void icp_step_op(const IcpArgs& a, const float* vmap_curr, const float* nmap_curr, const float* vmap_g_prev,
-                 const float* nmap_g_prev, int cols, int rows, float* scratch, float* out29_dev, hipStream_t s) {
-  IcpView V{vmap_curr, nmap_curr, vmap_g_prev, nmap_g_prev, cols, rows, a.k, a.distThres, a.angleThres, sq_le_max(a.distThres), sq_lt_max(a.angleThres)};
-  RgbView RV{};
-  float* pose = scratch + SE3_ACCS * VWARPS;   // 24 floats of parameters behind the partials
-  float h[24];
-  for (int i = 0; i < 9; ++i) { h[i] = a.Rcurr[i]; h[12 + i] = a.Rprev_inv[i]; }
-  for (int i = 0; i < 3; ++i) { h[9 + i] = a.tcurr[i]; h[21 + i] = a.tprev[i]; }
-  (void)hipMemcpyAsync(pose, h, sizeof(h), hipMemcpyHostToDevice, s);
-  (void)hipStreamSynchronize(s);  // h is a stack buffer
-  Se3Inputs in{pose, pose + 9, pose + 12, pose + 21, nullptr, nullptr, 0.f, false};
-  launch_accum<true, false, false>(V, RV, in, cols * rows, Se3Out{scratch}, s);
-  hipLaunchKernelGGL(k_final_tree_op, dim3(1), dim3(SOLVE_BLOCK), 0, s, (const float*)scratch, SE3_ACCS, op_groups(cols * rows), out29_dev);
-}
-void rgb_residual_op(const RgbResidualArgs& a, const int16_t* dIdx, const int16_t* dIdy, const float* lastDepth,
-                     const float* nextDepth, const uint8_t* lastImage, const uint8_t* nextImage, void* corres, int cols,
-                     int rows, int* out2_dev, hipStream_t s) {
-  ResidualView V{dIdx, dIdy, lastDepth, nextDepth, lastImage, nextImage, (DataTerm*)corres, cols, rows, a.minScale, a.maxDepthDelta};
-  float* params;
-  (void)hipMalloc((void**)&params, 12 * sizeof(float));
-  float h[12];
-  for (int i = 0; i < 9; ++i) h[i] = a.krkinv[i];
-  for (int i = 0; i < 3; ++i) h[9 + i] = a.kt[i];
-  (void)hipMemcpyAsync(params, h, sizeof(h), hipMemcpyHostToDevice, s);
-  (void)hipMemsetAsync(out2_dev, 0, 2 * sizeof(int), s);
-  hipLaunchKernelGGL(k_rgb_residual_op, dim3(ceil_div(cols * rows, REDUCE_BLOCK)), dim3(REDUCE_BLOCK), 0, s, V, (const float*)params,
-                     (const float*)(params + 9), out2_dev);
-  (void)hipStreamSynchronize(s);
-  (void)hipFree(params);
-}
-void rgb_step_op(const void* corres, float sigma, const float* cloud, float fx, float fy, const int16_t* dIdx, const int16_t* dIdy,
-                 float sobelScale, int cols, int rows, float* scratch, float* out29_dev, hipStream_t s) {
-  IcpView IV{};
-  RgbView V{corres, nullptr, cloud, dIdx, dIdy, cols, rows, Intr{fx, fy, 0, 0}, sobelScale};
-  Se3Inputs in{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, sigma, false};
-  launch_accum<false, true, false>(IV, V, in, cols * rows, Se3Out{scratch}, s);
-  hipLaunchKernelGGL(k_final_tree_op, dim3(1), dim3(SOLVE_BLOCK), 0, s, (const float*)scratch, SE3_ACCS, op_groups(cols * rows), out29_dev);
-}
-void so3_step_op(const So3Args& a, const uint8_t* lastImage, const uint8_t* nextImage, int cols, int rows, float* scratch, float* out11_dev,
-                 hipStream_t s) {
-  hipLaunchKernelGGL(k_so3_op, dim3(so3_grid(cols * rows)), dim3(SO3_BLOCK), 0, s, lastImage, nextImage, cols, rows, a, scratch);
-  hipLaunchKernelGGL(k_final_tree_op, dim3(1), dim3(SOLVE_BLOCK), 0, s, (const float*)scratch, SO3_ACCS, op_groups(cols * rows), out11_dev);
-}
-
-// ---- frame tier ----
-void init_icp(const Pyramid& p, const uint16_t* depth_filtered, Intr k, float cutoff, hipStream_t s) {
-  // level 0 of depth_tmp is the filtered depth image itself (no copy: cudaMemcpy2DFromArray of
-  // RGBDOdometry.cpp:126-134 existed only to cross the GL/CUDA boundary)
-  for (int i = 1; i < NUM_PYRS; ++i)
-    pyr_down_u16(i == 1 ? depth_filtered : p.depth_tmp[i - 1], p.W(i - 1), p.H(i - 1), p.depth_tmp[i], s);
-  VNLevels L;
-  for (int i = 0; i < NUM_PYRS; ++i) {
-    L.depth[i] = i == 0 ? depth_filtered : p.depth_tmp[i];
-    L.vmap[i] = p.vmap_curr[i];
-    L.nmap[i] = p.nmap_curr[i];
-    L.cols[i] = p.W(i);
-    L.rows[i] = p.H(i);
-    L.k[i] = intr_level(k, i);
-  }
-  L.cutoff = cutoff;
-  dim3 g = tile_grid(p.W(0), p.H(0));
-  g.z = NUM_PYRS;
-  hipLaunchKernelGGL(k_vmap_nmap_levels, g, tile_block(), 0, s, L);
-}
-
-// k_model_maps: one lane per level-0 column of a 4-row band (a quad of lanes per 4x4 block)
-static inline dim3 model_maps_grid(const Pyramid& p) {
-  return dim3(ceil_div(p.W(0), 64), ceil_div(p.H(0) / 4, 4));
-}
-void init_icp_model(const Pyramid& p, const float* pred_vertex, const float* pred_normal, const float* fill_vertex,
-                    const float* fill_normal, const TrackState* st, float maxDepthRGB, hipStream_t s, const uint8_t* pred_image_rgba,
-                    const uint8_t* fill_image_rgba, bool frameToFrameRGB, const FramePreprocess* with, bool tally) {
-  ModelMapsArgs A{};
-  A.pred_image = pred_image_rgba; A.fill_image = fill_image_rgba; A.force_fill_image = frameToFrameRGB;
-  A.tally_image = (tally && pred_image_rgba) ? pred_image_rgba : nullptr;
-  A.tally_out = const_cast<unsigned*>(&st->dense_count);
-  A.last0 = pred_image_rgba ? p.lastImage[0] : nullptr;
-  A.pred_vertex = (const float4*)pred_vertex; A.pred_normal = (const float4*)pred_normal;
-  A.fill_vertex = (const float4*)fill_vertex; A.fill_normal = (const float4*)fill_normal;
-  for (int i = 0; i < NUM_PYRS; ++i) { A.vmap[i] = p.vmap_g_prev[i]; A.nmap[i] = p.nmap_g_prev[i]; }
-  A.depth0 = p.lastDepth[0];
-  A.cols = p.W(0); A.rows = p.H(0);
-  A.maxDepthRGB = maxDepthRGB;
-  A.camera_frame = false;
-  const dim3 mg = model_maps_grid(p);
-  if (with) {   // the frame's depth pre-processing rides on this launch (k_frame_inputs)
-    PreArgs P{};
-    P.raw = with->raw; P.cols = p.W(0); P.rows = p.H(0); P.maxv = (unsigned)(with->maxD * 1000.0f); P.table = with->table;
-    P.filtered = with->filtered; P.metric = with->metric; P.metric_filtered = with->metric_filtered;
-    P.rgb3 = with->rgb3; P.next0 = p.nextImage[0]; P.rgb_keep = with->rgb_keep;
-    P.tiles_x = (P.cols + pre::PRE_TW - 1) / pre::PRE_TW;
-    P.tiles = P.tiles_x * ((P.rows + pre::PRE_TH - 1) / pre::PRE_TH);
-    P.mm_x = (int)mg.x;
-    hipLaunchKernelGGL(k_frame_inputs, dim3(P.tiles + (int)(mg.x * mg.y)), dim3(64, 4), 0, s, P, A, st);
-    return;
-  }
-  hipLaunchKernelGGL(k_model_maps, mg, dim3(64, 4), 0, s, A, st);
-}
-
-namespace {
-// model intensity L0 comes from the predicted image unless the device-side flag says fill-in
-__global__ void k_model_intensity(const uint8_t* __restrict__ pred, const uint8_t* __restrict__ fill, bool force_fill,
-                                  const TrackState* __restrict__ st, int n, uint8_t* __restrict__ dst) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint8_t* src = (force_fill || use_fill_in(st)) ? fill : pred;
-  const uchar4 c = ((const uchar4*)src)[i];
-  dst[i] = intensity_of((float)c.x, (float)c.y, (float)c.z);
-}
-}  // namespace
-
-void init_rgb_model(const Pyramid& p, const uint8_t* pred_image_rgba, const uint8_t* fill_image_rgba, bool frameToFrameRGB,
-                    const TrackState* st, hipStream_t s) {
-  const int n = p.W(0) * p.H(0);
-  // populateRGBDData(model): depth L0 already written by init_icp_model
-  for (int i = 0; i + 1 < NUM_PYRS; ++i) pyr_down_gauss_f(p.lastDepth[i], p.W(i), p.H(i), p.lastDepth[i + 1], s);
-  hipLaunchKernelGGL(k_model_intensity, dim3(ceil_div(n, 256)), dim3(256), 0, s, pred_image_rgba, fill_image_rgba, frameToFrameRGB, st, n,
-                     p.lastImage[0]);
-  for (int i = 0; i + 1 < NUM_PYRS; ++i) pyr_down_uchar_gauss(p.lastImage[i], p.W(i), p.H(i), p.lastImage[i + 1], s);
-}
-void init_icp_maps(const Pyramid& p, const float* vertex, const float* normal, const uint8_t* image_rgba, const TrackState* st,
-                   float maxDepthRGB, hipStream_t s) {
-  ModelMapsArgs A{};
-  A.pred_vertex = A.fill_vertex = (const float4*)vertex;
-  A.pred_normal = A.fill_normal = (const float4*)normal;
-  for (int i = 0; i < NUM_PYRS; ++i) { A.vmap[i] = p.vmap_curr[i]; A.nmap[i] = p.nmap_curr[i]; }
-  A.depth0 = p.nextDepth[0];
-  A.cols = p.W(0); A.rows = p.H(0);
-  A.maxDepthRGB = maxDepthRGB;
-  A.camera_frame = true;
-  hipLaunchKernelGGL(k_model_maps, model_maps_grid(p), dim3(64, 4), 0, s, A, st);
-  const int n = p.W(0) * p.H(0);
-  for (int i = 0; i + 1 < NUM_PYRS; ++i) pyr_down_gauss_f(p.nextDepth[i], p.W(i), p.H(i), p.nextDepth[i + 1], s);
-  hipLaunchKernelGGL(k_model_intensity, dim3(ceil_div(n, 256)), dim3(256), 0, s, image_rgba, image_rgba, true, st, n, p.nextImage[0]);
-  for (int i = 0; i + 1 < NUM_PYRS; ++i) pyr_down_uchar_gauss(p.nextImage[i], p.W(i), p.H(i), p.nextImage[i + 1], s);
-}
-namespace {
-// level-0 intensity of two RGBA images in one launch: blockIdx.y 0 = the model image ("last"), 1 = the current side's ("next")
-__global__ void k_rgba_intensity_pair(const uint8_t* __restrict__ last_rgba, const uint8_t* __restrict__ next_rgba, int n, uint8_t* __restrict__ last0,
-                                      uint8_t* __restrict__ next0) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uchar4 c = ((const uchar4*)(blockIdx.y == 0 ? last_rgba : next_rgba))[i];
-  (blockIdx.y == 0 ? last0 : next0)[i] = intensity_of((float)c.x, (float)c.y, (float)c.z);
-}
-}  // namespace
-// Model-to-model tracking (the local loop closure's second tracker, ElasticFusion.cpp:463-467): init_icp_model + init_rgb_model on one
-// predicted view and init_icp_maps on the other, as FIVE launches instead of twelve — the two k_model_maps, one launch for both level-0
-// intensity images, one k_pyr_down_multi per pyramid step over {model depth, current depth, model intensity, current intensity}.  The two
-// sides share no buffer (pyr2 / pyr3 keep nextDepth apart from lastDepth), the per-pixel functions are the ones the separate launches
-// call: same results (rocprofv3, closed-loop bench: the separate launches were 4.3 + 4.3 + 2.1 per frame, ~76 us).
-void init_model_pair(const Pyramid& p, const float* model_vertex, const float* model_normal, const uint8_t* model_image_rgba, const float* cur_vertex,
-                     const float* cur_normal, const uint8_t* cur_image_rgba, const TrackState* st, float maxDepthRGB, hipStream_t s) {
-  ModelMapsArgs A{};
-  A.pred_vertex = A.fill_vertex = (const float4*)model_vertex;
-  A.pred_normal = A.fill_normal = (const float4*)model_normal;
-  for (int i = 0; i < NUM_PYRS; ++i) { A.vmap[i] = p.vmap_g_prev[i]; A.nmap[i] = p.nmap_g_prev[i]; }
-  A.depth0 = p.lastDepth[0];
-  A.cols = p.W(0); A.rows = p.H(0);
-  A.maxDepthRGB = maxDepthRGB;
-  A.camera_frame = false;
-  hipLaunchKernelGGL(k_model_maps, model_maps_grid(p), dim3(64, 4), 0, s, A, st);
-  A.pred_vertex = A.fill_vertex = (const float4*)cur_vertex;
-  A.pred_normal = A.fill_normal = (const float4*)cur_normal;
-  for (int i = 0; i < NUM_PYRS; ++i) { A.vmap[i] = p.vmap_curr[i]; A.nmap[i] = p.nmap_curr[i]; }
-  A.depth0 = p.nextDepth[0];
-  A.camera_frame = true;
-  hipLaunchKernelGGL(k_model_maps, model_maps_grid(p), dim3(64, 4), 0, s, A, st);
-  const int n = p.W(0) * p.H(0);
-  hipLaunchKernelGGL(k_rgba_intensity_pair, dim3(ceil_div(n, 256), 2), dim3(256), 0, s, model_image_rgba, cur_image_rgba, n, p.lastImage[0], p.nextImage[0]);
-  for (int i = 0; i + 1 < NUM_PYRS; ++i) {
-    PyrJobs J;
-    J.src[0] = p.lastDepth[i]; J.dst[0] = p.lastDepth[i + 1]; J.type[0] = 1;
-    J.src[1] = p.nextDepth[i]; J.dst[1] = p.nextDepth[i + 1]; J.type[1] = 1;
-    J.src[2] = p.lastImage[i]; J.dst[2] = p.lastImage[i + 1]; J.type[2] = 2;
-    J.src[3] = p.nextImage[i]; J.dst[3] = p.nextImage[i + 1]; J.type[3] = 2;
-    J.scols = p.W(i); J.srows = p.H(i);
-    dim3 g = tile_grid(p.W(i + 1), p.H(i + 1));
-    g.z = 4;
-    hipLaunchKernelGGL(k_pyr_down_multi, g, tile_block(), 0, s, J);
-  }
-}
-void init_rgb_frame(const Pyramid& p, const uint8_t* rgb3, hipStream_t s) {
-  // populateRGBDData(frame): nextDepth == lastDepth (Q1), only the intensity pyramid is new
-  bgr_to_intensity(rgb3, 3, p.W(0), p.H(0), p.nextImage[0], s);
-  for (int i = 0; i + 1 < NUM_PYRS; ++i) pyr_down_uchar_gauss(p.nextImage[i], p.W(i), p.H(i), p.nextImage[i + 1], s);
-}
-namespace {
-// both level-0 intensity images in one launch: blockIdx.y 0 = the camera frame ("next"), 1 = the model image ("last")
-__global__ void k_intensity_both(const uint8_t* __restrict__ rgb3, const uint8_t* __restrict__ pred, const uint8_t* __restrict__ fill,
-                                 bool force_fill, const TrackState* __restrict__ st, int n, uint8_t* __restrict__ next0,
-                                 uint8_t* __restrict__ last0, uint8_t* __restrict__ rgb_keep, int first_half) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  if (blockIdx.y + first_half == 0) {   // (first_half + gridDim.y halves: both in the single-stream script, one each in the two-stream script)
-    const uint8_t* sp = rgb3 + (size_t)i * 3;
-    const uint8_t r = sp[0], g = sp[1], b = sp[2];
-    next0[i] = intensity_of((float)r, (float)g, (float)b);
-    if (rgb_keep) { rgb_keep[(size_t)i * 3] = r; rgb_keep[(size_t)i * 3 + 1] = g; rgb_keep[(size_t)i * 3 + 2] = b; }   // the context's copy of the frame
-  } else {
-    const uint8_t* src = (force_fill || use_fill_in(st)) ? fill : pred;
-    const uchar4 c = ((const uchar4*)src)[i];
-    last0[i] = intensity_of((float)c.x, (float)c.y, (float)c.z);
-  }
-}
-}  // namespace
-// initICP's depth pyramid + both halves of populateRGBDData in THREE launches instead of twelve (single-stream frame
-// script): level-0 intensities, then one k_pyr_down_multi per pyramid step over {frame depth u16, model depth f32,
-// model intensity, frame intensity}; then the per-level vertex/normal maps.  Same per-pixel functions, same results.
-static SobelLevels sobel_levels_of(const Pyramid& p);
-static void build_vn_levels(const Pyramid& p, const uint16_t* depth_filtered, Intr k, float cutoff, bool with_sobel, hipStream_t s);
-void build_pyramids(const Pyramid& p, const uint16_t* depth_filtered, Intr k, float cutoff, const uint8_t* pred_image_rgba,
-                    const uint8_t* fill_image_rgba, bool frameToFrameRGB, const uint8_t* rgb3, const TrackState* st, hipStream_t s,
-                    uint8_t* rgb_keep, bool with_sobel) {
-  const int n = p.W(0) * p.H(0);
-  // (rgb3 == null: both level-0 intensity images are already there — the frame's from the pre-processing launch, the model's from k_model_maps)
-  if (rgb3) hipLaunchKernelGGL(k_intensity_both, dim3(ceil_div(n, 256), 2), dim3(256), 0, s, rgb3, pred_image_rgba, fill_image_rgba, frameToFrameRGB, st,
-                     n, p.nextImage[0], p.lastImage[0], rgb_keep, 0);
-  // (both pyramid steps as ONE launch — a workgroup computing the 36 x 36 level-1 pixels its 16 x 16 level-2 tile reads, then the tile — was
-  // built and measured in round 6: 25.2 us against 8.0 + 5.4 for the two launches: six dependent 25-tap trips per thread; dropped,
-  // profiles/r06q_kernel_stats_fused_pyramid_steps.csv)
-  // (one launch per pyramid STAGE — step l -> l + 1 with the maps and the Sobel of level l — measured no faster in round 6: 1934 against 1939
-  // frames/s, profiles/r07d_ab_pyramid_stages.log; removed, last present in commit 2372c48)
-  for (int i = 0; i + 1 < NUM_PYRS; ++i) {
-    PyrJobs J;
-    J.src[0] = i == 0 ? (const void*)depth_filtered : (const void*)p.depth_tmp[i]; J.dst[0] = p.depth_tmp[i + 1]; J.type[0] = 0;
-    J.src[1] = p.lastDepth[i]; J.dst[1] = p.lastDepth[i + 1]; J.type[1] = 1;
-    J.src[2] = p.lastImage[i]; J.dst[2] = p.lastImage[i + 1]; J.type[2] = 2;
-    J.src[3] = p.nextImage[i]; J.dst[3] = p.nextImage[i + 1]; J.type[3] = 2;
-    J.scols = p.W(i); J.srows = p.H(i);
-    dim3 g = tile_grid(p.W(i + 1), p.H(i + 1));
-    g.z = 4;
-    hipLaunchKernelGGL(k_pyr_down_multi, g, tile_block(), 0, s, J);
-  }
-  build_vn_levels(p, depth_filtered, k, cutoff, with_sobel, s);
-}
-// The two-stream frame script (ef_set_input_overlap; round 6): build_pyramids split by what each kernel READS, so that the half that needs
-// nothing but the new frame runs on the input stream beside the previous frame's fusion and prediction.  Same per-pixel functions, same
-// results; four launches each instead of round 5's six and seven.
-//   frame side:  level-0 intensity of the frame (+ the context's copy of the RGB image), two pyramid steps over {frame depth u16, frame
-//                intensity}, the vertex / normal maps of all levels
-//   model side:  (behind init_icp_model) level-0 intensity of the model image, two pyramid steps over {model depth f32, model intensity};
-//                the Sobel / photometric-gate launch (init_rgb_sobel) reads both sides (the gate tests the MODEL's depth: quirk Q1) and
-//                follows the join
-void build_pyramids_frame_side(const Pyramid& p, const uint16_t* depth_filtered, Intr k, float cutoff, const uint8_t* rgb3, hipStream_t s,
-                               uint8_t* rgb_keep) {
-  const int n = p.W(0) * p.H(0);
-  if (rgb3)   // (null: the pre-processing launch wrote the frame's level-0 intensity)
-    hipLaunchKernelGGL(k_intensity_both, dim3(ceil_div(n, 256), 1), dim3(256), 0, s, rgb3, (const uint8_t*)nullptr, (const uint8_t*)nullptr, false,
-                       (const TrackState*)nullptr, n, p.nextImage[0], p.lastImage[0], rgb_keep, 0);
-  for (int i = 0; i + 1 < NUM_PYRS; ++i) {
-    PyrJobs J{};
-    J.src[0] = i == 0 ? (const void*)depth_filtered : (const void*)p.depth_tmp[i]; J.dst[0] = p.depth_tmp[i + 1]; J.type[0] = 0;
-    J.src[1] = p.nextImage[i]; J.dst[1] = p.nextImage[i + 1]; J.type[1] = 2;
-    J.scols = p.W(i); J.srows = p.H(i);
-    dim3 g = tile_grid(p.W(i + 1), p.H(i + 1));
-    g.z = 2;
-    hipLaunchKernelGGL(k_pyr_down_multi, g, tile_block(), 0, s, J);
-  }
-  build_vn_levels(p, depth_filtered, k, cutoff, false, s);
-}
-void build_pyramids_model_side(const Pyramid& p, const uint8_t* pred_image_rgba, const uint8_t* fill_image_rgba, bool frameToFrameRGB,
-                               const TrackState* st, hipStream_t s) {
-  const int n = p.W(0) * p.H(0);
-  if (pred_image_rgba)   // (null: k_model_maps wrote the model's level-0 intensity)
-    hipLaunchKernelGGL(k_intensity_both, dim3(ceil_div(n, 256), 1), dim3(256), 0, s, (const uint8_t*)nullptr, pred_image_rgba, fill_image_rgba,
-                       frameToFrameRGB, st, n, p.nextImage[0], p.lastImage[0], (uint8_t*)nullptr, 1);
-  for (int i = 0; i + 1 < NUM_PYRS; ++i) {
-    PyrJobs J{};
-    J.src[0] = p.lastDepth[i]; J.dst[0] = p.lastDepth[i + 1]; J.type[0] = 1;
-    J.src[1] = p.lastImage[i]; J.dst[1] = p.lastImage[i + 1]; J.type[1] = 2;
-    J.scols = p.W(i); J.srows = p.H(i);
-    dim3 g = tile_grid(p.W(i + 1), p.H(i + 1));
-    g.z = 2;
-    hipLaunchKernelGGL(k_pyr_down_multi, g, tile_block(), 0, s, J);
-  }
-}
-static void build_vn_levels(const Pyramid& p, const uint16_t* depth_filtered, Intr k, float cutoff, bool with_sobel, hipStream_t s) {
-  VNLevels L;
-  for (int i = 0; i < NUM_PYRS; ++i) {
-    L.depth[i] = i == 0 ? depth_filtered : p.depth_tmp[i];
-    L.vmap[i] = p.vmap_curr[i];
-    L.nmap[i] = p.nmap_curr[i];
-    L.cols[i] = p.W(i);
-    L.rows[i] = p.H(i);
-    L.k[i] = intr_level(k, i);
-  }
-  L.cutoff = cutoff;
-  dim3 g = tile_grid(p.W(0), p.H(0));
-  if (with_sobel) {   // init_rgb_sobel's launch rides along
-    g.z = 2 * NUM_PYRS;
-    hipLaunchKernelGGL(k_vn_sobel_levels, g, tile_block(), 0, s, L, sobel_levels_of(p));
-    return;
-  }
-  g.z = NUM_PYRS;
-  hipLaunchKernelGGL(k_vmap_nmap_levels, g, tile_block(), 0, s, L);
-}
-void init_rgb_sobel(const Pyramid& p, hipStream_t s) {
-  dim3 g = tile_grid(p.W(0), p.H(0));
-  g.z = NUM_PYRS;
-  hipLaunchKernelGGL(k_sobel_levels, g, tile_block(), 0, s, sobel_levels_of(p));
-}
-static SobelLevels sobel_levels_of(const Pyramid& p) {
-  SobelLevels L;
-  const float minGrad[NUM_PYRS] = {5, 3, 1};  // RGBDOdometry.cpp:112-114
-  const float sobelScale = 1.0f / 8.0f;       // RGBDOdometry.cpp:39-40
-  for (int i = 0; i < NUM_PYRS; ++i) {
-    L.src[i] = p.nextImage[i]; L.dx[i] = p.dIdx[i]; L.dy[i] = p.dIdy[i];
-    L.nextDepth[i] = p.nextDepth[i]; L.mask[i] = p.rgbMask[i]; L.corres[i] = p.corres[i];
-    L.minScale[i] = (float)(pow((double)minGrad[i], 2.0) / pow((double)sobelScale, 2.0));  // RGBDOdometry.cpp:425
-    L.cols[i] = p.W(i); L.rows[i] = p.H(i);
-  }
-  return L;
-}
-
-void init_first_rgb(const Pyramid& p, const uint8_t* rgb3, hipStream_t s) {
-  bgr_to_intensity(rgb3, 3, p.W(0), p.H(0), p.lastNextImage[0], s);
-  for (int i = 0; i + 1 < NUM_PYRS; ++i) pyr_down_uchar_gauss(p.lastNextImage[i], p.W(i), p.H(i), p.lastNextImage[i + 1], s);
-}
-
-namespace {
-template <int PPT>
-void launch_step(const Pyramid& p, TrackState* st, int level, int cur, int slots_out, const StepArgs& A, hipStream_t s) {
-  const int cols = p.W(level), rows = p.H(level), N = cols * rows;
-  ResidualPackedView RV{p.rgbMask[level], p.lastDepth[level], p.nextDepth[level], p.lastImage[level], p.nextImage[level], p.corres[level], cols, rows,
-                        0.07f /* maxDepthDeltaRGB, RGBDOdometry.cpp:41 */};
-  const int grid = A.has_body ? ceil_div(N, REDUCE_BLOCK * PPT) : 1;
-  hipLaunchKernelGGL(k_track_step<PPT>, dim3(grid), dim3(REDUCE_BLOCK), 0, s, RV, st, (const GNState*)&st->gn[cur], &st->gn[cur ^ 1],
-                     (const float*)p.partials, (const int*)&st->rgb_slots[slots_out ^ 1][0][0], &st->rgb_slots[slots_out][0][0], A);
-}
-// one Gauss-Newton iteration = two launches: k_track_step (update of the previous iteration + correspondence search) and
-// k_se3_accum (normal equations).  `it` = index of the iteration within the call; cur = GNState buffer to read.
-// Returns the buffer the NEXT step reads.
-int launch_iteration(const Pyramid& p, TrackState* st, int level, Intr kl, const TrackParams& tp, bool icp, bool rgb, int it, int cur,
-                     int prev_level, hipStream_t s, KernelProbe* probe) {
-  const int cols = p.W(level), rows = p.H(level), N = cols * rows;
-  const bool sample = probe && level == 0 && probe->used < probe->capacity;
-  const int sp = it & 1;
-  const bool level_changes = level != prev_level;
-  StepArgs A{it > 0, rgb, icp, rgb, tp.rgbOnly, tp.icpWeight, kl, level_changes, it, op_groups(p.W(prev_level) * p.H(prev_level))};
-  // The update step as its own ONE-workgroup launch (head only), then the correspondence search alone (body only): three launches
-  // per iteration.  Evaluating the update redundantly at the head of every workgroup of the correspondence kernel instead (two
-  // launches) was built and measured in round 2: 888 vs 1322 frames/s; dropped from the source in round 3.
-  if (A.has_head && A.has_body && tp.fused_step && !tp.rgbOnly) {
-    // two launches per iteration: the update step by workgroup 0 of the search launch, handed to the others in-launch (see k_track_step)
-    if (N >= 256 * 1024) launch_step<2>(p, st, level, cur, sp, A, s);
-    else launch_step<1>(p, st, level, cur, sp, A, s);
-    cur ^= 1;
-  } else {
-  if (A.has_head) {
-    StepArgs H = A;
-    H.has_body = false;
-    launch_step<1>(p, st, level, cur, sp, H, s);
-    cur ^= 1;
-  }
-  if (A.has_body) {
-    StepArgs B = A;
-    B.has_head = false;
-    // (four times fewer, four times fatter wavefronts — PPT 8 / 4 — measured 4.5 % slower end to end: DESIGN.md 6)
-    if (N >= 256 * 1024) launch_step<2>(p, st, level, cur, sp, B, s);
-    else launch_step<1>(p, st, level, cur, sp, B, s);
-  }
-  }
-  const GNState* g = &st->gn[cur];
-  IcpView IV{p.vmap_curr[level], p.nmap_curr[level], p.vmap_g_prev[level], p.nmap_g_prev[level], cols, rows, kl, tp.distThres, tp.angleThres, sq_le_max(tp.distThres), sq_lt_max(tp.angleThres)};
-  RgbView GV{p.corres[level], p.lastDepth[level], nullptr, p.dIdx[level], p.dIdy[level], cols, rows, kl, 1.0f / 8.0f};
-  Se3Inputs in{g->Rcurr, g->tcurr, st->Rprev_inv, st->tprev, &st->rgb_slots[sp][0][0], &g->rgb_broken, 0.f, tp.rgbOnly};
-  in.slots_zero = &st->rgb_slots[sp ^ 1][0][0];
-  const Se3Out out{p.partials};
-  hipEvent_t e0 = sample ? probe->start[probe->used] : nullptr, e1 = sample ? probe->stop[probe->used] : nullptr;
-  if (sample) probe->used++;
-  if (icp && rgb) launch_accum<true, true, true>(IV, GV, in, N, out, s, e0, e1);
-  else if (icp) launch_accum<true, false, true>(IV, GV, in, N, out, s, e0, e1);
-  else launch_accum<false, true, true>(IV, GV, in, N, out, s, e0, e1);
-  return cur;
-}
-}  // namespace
-
-namespace {
-std::mutex g_chain_mu;                 // the per-device chain of persistent launches (see track())
-hipStream_t g_chain_last[64] = {};
-bool g_chain_has[64] = {};
-hipEvent_t g_chain_ev[64] = {};
-inline bool last_valid_other(int dev, hipStream_t s) { return g_chain_has[dev] && g_chain_last[dev] != s; }
-}  // namespace
-void persistent_chain_forget(hipStream_t s) {
-  std::lock_guard<std::mutex> lk(g_chain_mu);
-  for (int d = 0; d < 64; ++d)
-    if (g_chain_has[d] && g_chain_last[d] == s) { g_chain_has[d] = false; g_chain_last[d] = nullptr; }
-}
-
-// Which script a call runs decides what the exchange areas (Pyramid::partials) hold: 1 = the granules of a 256-workgroup persistent launch, 0 = the
-// per-step kernels' plain partials / k_track_small's barrier words.  A context that changes scripts gets the areas cleared (tags must never match
-// by accident; the other script's words start from zeros) — and the sticky words they hold, the abort flag and the fallback count, carried over
-// on the host first (a clear used to erase them silently): one synchronisation per switch, which happens when an option is toggled or
-// a sampled frame leaves a graph-replaying context's script, never in a steady replay.  Under a CALLER's capture nothing can be read back: the
-// clear is recorded (the caller's graph then runs the launch-per-step script, which keeps no sticky word).
-static void switch_script(Pyramid& p, int target, hipStream_t s, bool capturing) {
-  if (p.last_mode == target) return;
-  if (p.partials) {
-    if (!capturing) {
-      if (tracker_aborted(p, s) > 0) p.sticky_abort = 1u;
-      const int f = tracker_fallbacks(p, s);
-      if (f > 0) p.fallbacks_base = (unsigned)f;   // (tracker_fallbacks already includes the earlier base)
-    }
-    (void)hipMemsetAsync(p.partials, 0, sizeof(float) * PARTIAL_ALLOC_FLOATS, s);
-  }
-  p.last_mode = target;
-}
-static int script_of(const TrackParams& tp, bool capturing, int n_total) {
-#ifdef EF_FAST_ORDER
-  const int pmode = (tp.persistent && !capturing) ? 1 : 0;
-#else
-  const int pmode = capturing ? 0 : tp.persistent;
-#endif
-  return (pmode == 1 && !tp.rgbOnly && n_total <= FT_MAX_ITER) ? 1 : 0;
-}
-void track_prepare(Pyramid& p, const TrackParams& tp, hipStream_t s) {
-  const int n_total = (tp.fastOdom ? 3 : 10) + (tp.pyramid ? 9 : 0);
-  switch_script(p, script_of(tp, false, n_total), s, false);
-}
-TrackTail track(Pyramid& p, TrackState* st, Intr k, const TrackParams& tp, hipStream_t s, KernelProbe* probe, KernelProbe* probe_all) {
-  const bool icp = !tp.rgbOnly && tp.icpWeight > 0;       // RGBDOdometry.cpp:266-267
-  const bool rgb = tp.rgbOnly || tp.icpWeight < 100;
-  int iterations[NUM_PYRS];
-  iterations[0] = tp.fastOdom ? 3 : 10;  // RGBDOdometry.cpp:371-373
-  iterations[1] = tp.pyramid ? 5 : 0;
-  iterations[2] = tp.pyramid ? 4 : 0;
-  int first_level = 0;
-  for (int i = NUM_PYRS - 1; i >= 0; --i)
-    if (iterations[i] > 0) { first_level = i; break; }
-  const int so3_level = 2;
-  // (a caller capturing `s` into a graph of its own gets the launch-per-step script: the persistent launches take a fresh epoch per launch
-  // and wait for the device's chain event, neither of which a replayed graph can carry)
-  hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
-  const bool capturing = hipStreamIsCapturing(s, &capture) == hipSuccess && capture != hipStreamCaptureStatusNone;
-#ifdef EF_FAST_ORDER
-  const int pmode = (tp.persistent && !capturing) ? 1 : 0;
-#else
-  const int pmode = capturing ? 0 : tp.persistent;
-#endif
-  // The persistent launch takes k_track_begin, the SO(3) loop and the leading iterations whose level fits (coarse to fine: once a
-  // level is too large, it and everything after it run one launch per step).  rgbOnly keeps the per-step script (its per-level
-  // "break" bookkeeping is not in the persistent kernel).
-  int n_small = 0;
-  PtArgs PA{};
-  if (pmode == 2 && !tp.rgbOnly) {   // (reference-order builds only: the fast order has no launch of the small levels)
-    bool fits = true;
-    for (int i = NUM_PYRS - 1; i >= 0 && fits; --i) {
-      if (iterations[i] == 0) continue;
-      fits = p.W(i) * p.H(i) <= PT_MAX_PIXELS && n_small + iterations[i] <= PT_MAX_ITER;
-      for (int j = 0; fits && j < iterations[i]; ++j) PA.levels |= (unsigned)i << (2 * n_small++);
-    }
-  }
-  int it = 0, cur = 0, prev_level = first_level;
-  // The persistent launch of 256 co-resident workgroups takes the WHOLE call — k_track_begin, the SO(3) loop, every iteration of every level
-  // (fast order: k_track_fast, ef_track_fast_persistent.inc; reference order: k_track_ref, ef_track_ref_persistent.inc) — or, with `persistent`
-  // off / rgbOnly (whose per-level "break" bookkeeping is not in the kernels), nothing: then every step is its own launch, in the same order
-  // of additions.  (Reference-order builds: persistent == 2 asks for round 3's launch of the small levels, k_track_small, below.)
-  const int n_total = iterations[0] + iterations[1] + iterations[2];
-  if (pmode == 1 && !tp.rgbOnly && n_total <= FT_MAX_ITER) {
-    switch_script(p, 1, s, capturing);   // another script of this instance may have left anything in the exchange areas: tags must never match by accident
-    FtArgs FA{};
-    for (int i = 0; i < NUM_PYRS; ++i)
-      FA.L[i] = PtLevel{p.vmap_curr[i], p.nmap_curr[i], p.vmap_g_prev[i], p.nmap_g_prev[i], p.rgbMask[i], p.lastDepth[i], p.nextDepth[i],
-                        p.lastImage[i], p.nextImage[i], p.corres[i], p.dIdx[i], p.dIdy[i], p.W(i), p.H(i), intr_level(k, i)};
-    int n = 0;
-    for (int i = NUM_PYRS - 1; i >= 0; --i)
-      for (int j = 0; j < iterations[i]; ++j) FA.levels |= (unsigned long long)i << (2 * n++);
-    FA.n_iter = n;
-    FA.so3 = tp.so3;
-    FA.so3_last = p.lastNextImage[so3_level];
-    FA.so3_next = p.nextImage[so3_level];
-    FA.so3_cols = p.W(so3_level);
-    FA.so3_rows = p.H(so3_level);
-    FA.kso3 = intr_level(k, so3_level);
-    FA.kfirst = intr_level(k, first_level);
-    FA.icpWeight = tp.icpWeight;
-    FA.distThres = tp.distThres;
-    FA.angleThres = tp.angleThres;
-    FA.dist2Max = sq_le_max(tp.distThres);
-    FA.sine2Max = sq_lt_max(tp.angleThres);
-    FA.partials = p.partials;
-    if (p.epoch > 0xFFFFFFFFu - 2u * FT_EPOCHS) p.epoch = 1;   // (a slot keeps a 2^32-launch-old tag only if nobody wrote it since)
-    FA.epoch = p.epoch;
-    p.epoch += FT_EPOCHS;
-    FA.out_cur = 0;
-    FA.empty_model_flag = tp.so3 ? nullptr : tp.empty_model_flag;   // (the SO(3) loop looks at the frame-side images only: not covered by the shortcut)
-    FA.empty_model_value = tp.empty_model_value;
-#ifndef EF_FAST_ORDER
-    // level-resident pixel data (ef_track_ref_persistent.inc, rt_res_mode): the largest need of a level whose slots fit — both sides, or the
-    // ICP side alone (1280 x 960 level 0) — under what the chip gives one workgroup beside the kernel's static LDS
-    unsigned res_bytes = 0;
-    if (!tp.no_resident && rt_res_budget() > 0) {
-      for (int i = 0; i < NUM_PYRS; ++i) {
-        if (iterations[i] == 0) continue;
-        const unsigned S = (unsigned)(((p.W(i) * p.H(i) + VTHREADS - 1) / VTHREADS + 3) >> 2);
-        const unsigned n2 = S * ((icp ? RT_ICP_STEP_BYTES : 0) + (rgb ? RT_RGB_STEP_BYTES : 0)), n1 = icp ? S * RT_ICP_STEP_BYTES : 0u;
-        const unsigned need = n2 <= rt_res_budget() ? n2 : (n1 <= rt_res_budget() ? n1 : 0u);
-        res_bytes = need > res_bytes ? need : res_bytes;
-      }
-    }
-    FA.res_bytes = res_bytes;
-#endif
-    const bool sample_all = probe_all && probe_all->used < probe_all->capacity;
-    hipEvent_t e0 = sample_all ? probe_all->start[probe_all->used] : nullptr, e1 = sample_all ? probe_all->stop[probe_all->used] : nullptr;
-    if (sample_all) probe_all->used++;
-    {
-      // The launch needs its 256 workgroups resident TOGETHER, one per CU.  Two such launches in flight at once (two contexts of this
-      // process, each on its own stream) could each hold a part of the chip and wait for the rest for ever, so the persistent launches of
-      // a device are chained, in the order the host enqueues them, through one event per device: a launch first waits (on the GPU, not on
-      // the host) for the previous one, whatever stream that ran on.  On one stream this is a no-op.  Ordinary kernels of other streams
-      // only delay it (they end without waiting for anybody); another PROCESS's persistent kernels are outside this chain: bounded spins,
-      // FtSync::abort, tracker_aborted.
-      // Round 6: the chain costs nothing while ONE stream launches them (the common case: an event record between two kernels of a stream is a
-      // barrier packet, measured as a 6 us bubble behind every tracker launch in profiles/r06f_timeline_single_stream.txt) — the dependency is
-      // created by the launch that finds ANOTHER stream's launch before it: it records the event on that stream now (everything enqueued there
-      // so far, the persistent launch included) and makes its own stream wait for it.  persistent_chain_forget() drops a stream that is destroyed.
-      std::lock_guard<std::mutex> lk(g_chain_mu);
-      int dev = 0;
-      (void)hipGetDevice(&dev);
-      if (dev >= 0 && dev < 64) {   // (a device index beyond the table: no chain, the bounded spins remain)
-        hipStream_t& last = g_chain_last[dev];
-        hipEvent_t& ev = g_chain_ev[dev];
-        if (last_valid_other(dev, s)) {
-          if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) ev = nullptr;
-          if (ev && hipEventRecord(ev, last) == hipSuccess) (void)hipStreamWaitEvent(s, ev, 0);
-          (void)hipGetLastError();
-        }
-        last = s;
-        g_chain_has[dev] = true;
-      }
-#ifdef EF_FAST_ORDER
-      if (icp && rgb) hipExtLaunchKernelGGL((k_track_fast<true, true>), dim3(FT_WGS), dim3(FT_BLOCK), 0, s, e0, e1, 0, FA, st);
-      else if (icp) hipExtLaunchKernelGGL((k_track_fast<true, false>), dim3(FT_WGS), dim3(FT_BLOCK), 0, s, e0, e1, 0, FA, st);
-      else hipExtLaunchKernelGGL((k_track_fast<false, true>), dim3(FT_WGS), dim3(FT_BLOCK), 0, s, e0, e1, 0, FA, st);
-#else
-      if (icp && rgb) hipExtLaunchKernelGGL((k_track_ref<true, true>), dim3(FT_WGS), dim3(FT_BLOCK), res_bytes, s, e0, e1, 0, FA, st);
-      else if (icp) hipExtLaunchKernelGGL((k_track_ref<true, false>), dim3(FT_WGS), dim3(FT_BLOCK), res_bytes, s, e0, e1, 0, FA, st);
-      else hipExtLaunchKernelGGL((k_track_ref<false, true>), dim3(FT_WGS), dim3(FT_BLOCK), res_bytes, s, e0, e1, 0, FA, st);
-#endif
-    }
-    // (returns at once unless the launch above found part of the chip taken: see its admission step)
-#ifdef EF_FAST_ORDER
-    if (icp && rgb) hipLaunchKernelGGL((k_track_serial<true, true>), dim3(1), dim3(REDUCE_BLOCK), 0, s, p.partials, st, FA.epoch);
-    else if (icp) hipLaunchKernelGGL((k_track_serial<true, false>), dim3(1), dim3(REDUCE_BLOCK), 0, s, p.partials, st, FA.epoch);
-    else hipLaunchKernelGGL((k_track_serial<false, true>), dim3(1), dim3(REDUCE_BLOCK), 0, s, p.partials, st, FA.epoch);
-#endif
-    track_swap(p, tp);
-    TrackTail tail{0, (n - 1) & 1, n > 0, icp, rgb, tp.rgbOnly, tp.icpWeight, intr_level(k, 0), p.partials + FT_P_OFF};
-    tail.ng = 1;   // the reducers of the last iteration left the TOTALS in column 0
-#ifndef EF_FAST_ORDER
-    tail.merged_end = true;   // (the one-workgroup fallback rides at the head of track_end's launch: k_track_ref_end)
-    tail.epoch = FA.epoch;
-    tail.partials = p.partials;
-#endif
-    return tail;
-  }
-  switch_script(p, 0, s, capturing);   // (the per-step kernels' plain partials and k_track_small's barrier words start from zeros)
-#ifdef EF_FAST_ORDER
-  n_small = 0;
-  hipLaunchKernelGGL(k_track_begin, dim3(1), dim3(64), 0, s, st, tp.so3, intr_level(k, so3_level), intr_level(k, first_level));
-  if (tp.so3) {
-    for (int i = 0; i < 10; ++i)
-      hipLaunchKernelGGL(k_so3_iteration, dim3(so3_grid(p.W(so3_level) * p.H(so3_level))), dim3(SO3_BLOCK), 0, s,
-                         (const uint8_t*)p.lastNextImage[so3_level], (const uint8_t*)p.nextImage[so3_level], p.W(so3_level), p.H(so3_level),
-                         intr_level(k, so3_level), intr_level(k, first_level), i, st, p.partials);
-  }
-#else
-  if (pmode == 2 && !tp.rgbOnly && (n_small > 0 || tp.so3)) {   // (pmode, not tp.persistent: a capturing caller gets the launch-per-step script)
-    for (int i = 0; i < NUM_PYRS; ++i)
-      PA.L[i] = PtLevel{p.vmap_curr[i], p.nmap_curr[i], p.vmap_g_prev[i], p.nmap_g_prev[i], p.rgbMask[i], p.lastDepth[i], p.nextDepth[i],
-                        p.lastImage[i], p.nextImage[i], p.corres[i], p.dIdx[i], p.dIdy[i], p.W(i), p.H(i), intr_level(k, i)};
-    PA.n_iter = n_small;
-    PA.so3 = tp.so3;
-    PA.so3_last = p.lastNextImage[so3_level];
-    PA.so3_next = p.nextImage[so3_level];
-    PA.so3_cols = p.W(so3_level);
-    PA.so3_rows = p.H(so3_level);
-    PA.kso3 = intr_level(k, so3_level);
-    PA.kfirst = intr_level(k, first_level);
-    PA.icpWeight = tp.icpWeight;
-    PA.distThres = tp.distThres;
-    PA.angleThres = tp.angleThres;
-    PA.dist2Max = sq_le_max(tp.distThres);
-    PA.sine2Max = sq_lt_max(tp.angleThres);
-    PA.partials = p.partials;
-    PA.out_cur = 0;
-    if (icp && rgb) hipLaunchKernelGGL((k_track_small<true, true>), dim3(PT_WGS), dim3(PT_BLOCK), 0, s, PA, st);
-    else if (icp) hipLaunchKernelGGL((k_track_small<true, false>), dim3(PT_WGS), dim3(PT_BLOCK), 0, s, PA, st);
-    else hipLaunchKernelGGL((k_track_small<false, true>), dim3(PT_WGS), dim3(PT_BLOCK), 0, s, PA, st);
-    it = n_small;
-    if (n_small > 0) prev_level = (int)((PA.levels >> (2 * (n_small - 1))) & 3u);
-  } else {
-    n_small = 0;
-    hipLaunchKernelGGL(k_track_begin, dim3(1), dim3(64), 0, s, st, tp.so3, intr_level(k, so3_level), intr_level(k, first_level));
-    if (tp.so3) {
-      for (int i = 0; i < 10; ++i)
-        hipLaunchKernelGGL(k_so3_iteration, dim3(VWARPS / SO3_WPB), dim3(SO3_BLOCK), 0, s, (const uint8_t*)p.lastNextImage[so3_level],
-                           (const uint8_t*)p.nextImage[so3_level], p.W(so3_level), p.H(so3_level), intr_level(k, so3_level),
-                           intr_level(k, first_level), i, st, p.partials);
-    }
-  }
-#endif
-  int done = 0;
-  for (int i = NUM_PYRS - 1; i >= 0; --i) {
-    const Intr kl = intr_level(k, i);
-    for (int j = 0; j < iterations[i]; ++j) {
-      if (done++ < n_small) continue;   // ran inside the persistent launch
-      cur = launch_iteration(p, st, i, kl, tp, icp, rgb, it, cur, prev_level, s, probe);
-      prev_level = i;
-      ++it;
-    }
-  }
-  track_swap(p, tp);
-  // the last iteration's update is evaluated at the head of k_track_end (track_end below)
-  TrackTail tail{cur, (it - 1) & 1, it > 0, icp, rgb, tp.rgbOnly, tp.icpWeight, intr_level(k, 0), p.partials};
-  tail.ng = op_groups(p.W(prev_level) * p.H(prev_level));
-  return tail;
-}
-// host-side tail of getIncrementalTransformation: the frame's intensity pyramid becomes the SO(3) reference of the next
-// (RGBDOdometry.cpp:284-288 swaps lastNextImage / nextImage); separate so that a replayed hipGraph can do it without launching
-// developer instrumentation: the -DEF_STAGE_CLOCKS sums of k_track_small (24 x u64, 10 ns ticks; zeros in a normal build), read and reset
-int tracker_small_clocks(const Pyramid& p, unsigned long long* out32, hipStream_t s) {
-  if (!p.partials) return -1;
-  unsigned long long* src = (unsigned long long*)((char*)(p.partials + FT_SY_OFF) + offsetof(FtSync, clk));
-  int n = 32;
-#ifndef EF_FAST_ORDER
-  if (p.last_mode != 1) { src = (unsigned long long*)((char*)(p.partials + 2 * PARTIAL_FLOATS) + offsetof(PtSync, clk)); n = 24; }   // k_track_small
-#endif
-  for (int i = 0; i < 32; ++i) out32[i] = 0ull;
-  if (hipStreamSynchronize(s) != hipSuccess) return -1;
-  if (hipMemcpy(out32, src, n * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  return hipMemset(src, 0, n * sizeof(unsigned long long)) == hipSuccess ? 0 : -1;
-}
-int tracker_aborted(const Pyramid& p, hipStream_t s) {
-  if (p.sticky_abort) return 1;   // (carried over a script switch)
-  if (!p.partials) return 0;
-#ifndef EF_FAST_ORDER
-  if (p.last_mode != 1) {   // round 3's launch of the small levels (k_track_small) keeps its flag in PtSync
-    PtSync h;
-    if (hipMemcpyAsync(&h, p.partials + 2 * PARTIAL_FLOATS, offsetof(PtSync, wg_sums), hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
-    if (hipStreamSynchronize(s) != hipSuccess) return -1;
-    return h.abort != 0 ? 1 : 0;
-  }
-#endif
-  unsigned flag = 0;
-  if (hipMemcpyAsync(&flag, (const char*)(p.partials + FT_SY_OFF) + offsetof(FtSync, abort), sizeof(flag), hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
-  if (hipStreamSynchronize(s) != hipSuccess) return -1;
-  return flag != 0 ? 1 : 0;
-}
-int tracker_fallbacks(const Pyramid& p, hipStream_t s) {
-  if (!p.partials || p.last_mode != 1) return (int)p.fallbacks_base;   // (what earlier persistent launches of this instance counted)
-  unsigned n = 0;
-  if (hipMemcpyAsync(&n, (const char*)(p.partials + FT_SY_OFF) + offsetof(FtSync, fallbacks), sizeof(n), hipMemcpyDeviceToHost, s) != hipSuccess) return -1;
-  if (hipStreamSynchronize(s) != hipSuccess) return -1;
-  return (int)(n + p.fallbacks_base);
-}
-void track_swap(Pyramid& p, const TrackParams& tp) {
-  if (tp.so3)
-    for (int i = 0; i < NUM_PYRS; ++i) { uint8_t* tmp = p.lastNextImage[i]; p.lastNextImage[i] = p.nextImage[i]; p.nextImage[i] = tmp; }
-}
-
-// exported for the context: finishing kernels
-void track_end(TrackState* st, const TrackTail& u, bool rgb, float weightMultiplier, double* traj, int slot, hipStream_t s, const unsigned* abort_word,
-               unsigned* abort_report) {
-  const StepArgs A{u.has_head, false, u.icp, u.rgb, u.rgbOnly, u.icpWeight, u.k0, true, 63, u.ng};
-#ifndef EF_FAST_ORDER
-  if (u.merged_end) {
-    unsigned* report = abort_word ? abort_report : nullptr;
-    if (u.icp && u.rgb) hipLaunchKernelGGL((k_track_ref_end<true, true>), dim3(1), dim3(FT_BLOCK), 0, s, u.partials, st, u.epoch, A, u.slots, rgb, weightMultiplier, traj, slot, report);
-    else if (u.icp) hipLaunchKernelGGL((k_track_ref_end<true, false>), dim3(1), dim3(FT_BLOCK), 0, s, u.partials, st, u.epoch, A, u.slots, rgb, weightMultiplier, traj, slot, report);
-    else hipLaunchKernelGGL((k_track_ref_end<false, true>), dim3(1), dim3(FT_BLOCK), 0, s, u.partials, st, u.epoch, A, u.slots, rgb, weightMultiplier, traj, slot, report);
-    return;
-  }
-#endif
-  hipLaunchKernelGGL(k_track_end, dim3(1), dim3(REDUCE_BLOCK), 0, s, st, (const GNState*)&st->gn[u.cur], &st->gn[u.cur ^ 1], u.pairs,
-                     (const int*)&st->rgb_slots[u.slots & 1][0][0], A, rgb, weightMultiplier, traj, slot, abort_word, abort_word ? abort_report : nullptr);
-}
-// device address of the sticky abort word of this tracker instance's persistent launches (FtSync::abort; round 3's k_track_small: PtSync::abort)
-unsigned* tracker_abort_word(const Pyramid& p) {
-  if (!p.partials) return nullptr;
-#ifndef EF_FAST_ORDER
-  if (p.last_mode != 1) return (unsigned*)((char*)(p.partials + 2 * PARTIAL_FLOATS) + offsetof(PtSync, abort));
-#endif
-  return (unsigned*)((char*)(p.partials + FT_SY_OFF) + offsetof(FtSync, abort));
-}
-void pose_injected(TrackState* st, const double* T_wc16, bool save_prev, float weightMultiplier, bool with_weighting, double* traj, int slot,
-                   hipStream_t s) {
-  hipLaunchKernelGGL(k_pose_injected, dim3(1), dim3(64), 0, s, st, efl::se3_from_matrix(T_wc16), save_prev, weightMultiplier, with_weighting,
-                     traj, slot);
-}
-void pose_restored(TrackState* st, const double* q4, const double* t3, hipStream_t s) {
-  efl::SE3 T;
-  for (int i = 0; i < 4; ++i) T.q[i] = q4[i];
-  for (int i = 0; i < 3; ++i) T.t[i] = t3[i];
-  hipLaunchKernelGGL(k_pose_injected, dim3(1), dim3(64), 0, s, st, T, false, 1.0f, false, (double*)nullptr, 0);
-}
-void copy_pose(TrackState* dst, const TrackState* src, hipStream_t s) { hipLaunchKernelGGL(k_copy_pose, dim3(1), dim3(64), 0, s, dst, src); }
-void adopt_pose(TrackState* st, const TrackState* est, double* traj, int slot, hipStream_t s) {
-  hipLaunchKernelGGL(k_adopt_pose, dim3(1), dim3(64), 0, s, st, est, traj, slot);
-}
-void sample_constraints(const float* vertex4, const uint16_t* old_time, int cols, int rows, int step, float* out4, hipStream_t s) {
-  const int cw = cols / step, ch = rows / step;
-  hipLaunchKernelGGL(k_sample_constraints, dim3(ceil_div(cw * ch, 256)), dim3(256), 0, s, (const float4*)vertex4, old_time, cols, cw, ch, step,
-                     (float4*)out4);
-}
-void log_pose(const TrackState* st, double* traj, int slot, hipStream_t s) { hipLaunchKernelGGL(k_log_pose, dim3(1), dim3(64), 0, s, st, traj, slot); }
+// host code: launchers (one translation unit with the kernels they launch)
+#include "ef_track_host_ops.inc"
+#include "ef_track_host_inputs.inc"
+#include "ef_track_host_track.inc"
 
 }  // namespace eft

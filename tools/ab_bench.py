@@ -2,7 +2,7 @@
 """Same-box A/B of library builds / tracker scripts in ONE process (GPU boxes of the pool differ by 10-20 %; a `gpurun` visit is charged by the
 minute, and bench.py pays Python + torch start-up and frame generation per run):
 
-    python tools/ab_bench.py [--steps 200] [--reps 2] spec ...
+    python tools/ab_bench.py [--steps 200] [--reps 2] [--close-loops | --graph --track-only] spec ...
 
 spec = <library>[@<mode>][+ov<N>]: library "d" = libefusion_hip.so (the default: reference rounding), a name = libefusion_hip_<name>.so; mode = the
 argument of ef_set_persistent_tracker (1 = one persistent launch, 0 = one launch per step, 2 = round 3's small-level launch); +ov<N> = the next
@@ -24,6 +24,8 @@ def main():
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--preroll", type=int, default=100)
     ap.add_argument("--close-loops", action="store_true")
+    ap.add_argument("--graph", action="store_true", help="the tracker's launches replayed from a hipGraph (BASELINE configs[4] with --track-only)")
+    ap.add_argument("--track-only", action="store_true", help="odometry only in the timed region, on the map the pre-roll built (BASELINE configs[4])")
     ap.add_argument("--big", action="store_true", help="BASELINE configs[2]: 1280x960 on a map pre-seeded with ~1 M surfels (bench.py's side leg: preroll 16, warm-up 24)")
     a = ap.parse_args()
     import bench
@@ -46,7 +48,7 @@ def main():
             name, _, mode = base.partition("@")
             api.use_library(None if name in ("d", "-") else os.path.join(os.path.dirname(build.LIB), f"libefusion_hip_{name}.so"))
             dev = [(api.DevBuf.from_array(r), api.DevBuf.from_array(d)) for r, d, _ in frames]   # (per library: the allocator is the library's)
-            ef = bench.make_engine(api, w, h, 0, 0, close_loops=a.close_loops)
+            ef = bench.make_engine(api, w, h, 0, 0, close_loops=a.close_loops, graph=a.graph)
             k0 = 0
             if a.big:
                 bench.preseed(ef, 0xEF0001, w, h, 1 << 20, frames[0])
@@ -67,6 +69,8 @@ def main():
                     ef.processFrameDevice(dev[k][0].p.value, dev[k][1].p.value, k * 33333)
             for k in range(k0, first):
                 step(k)
+            if a.track_only:
+                ef.setTrackOnly(True)
             ef.synchronize()
             t0 = time.perf_counter()
             for k in range(first, first + a.steps):
