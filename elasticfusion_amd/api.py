@@ -46,6 +46,10 @@ class ef_timing(C.Structure):
     _fields_ = [("name", C.c_char_p), ("ms", c_f)]
 
 
+class ef_tracker_plan(C.Structure):
+    _fields_ = [("script", c_i), ("n_small", c_i), ("n_iter", c_i), ("levels", C.c_ulonglong), ("res_bytes", C.c_uint), ("res_budget", C.c_uint)]
+
+
 class ef_render_params(C.Structure):
     _fields_ = [("width", c_i), ("height", c_i), ("fx", c_f), ("fy", c_f), ("cx", c_f), ("cy", c_f), ("T_wc", C.c_double * 16),
                 ("max_depth", c_f), ("threshold", c_f), ("draw_unstable", c_i), ("color_type", c_i), ("draw_window", c_i),
@@ -760,6 +764,15 @@ class ElasticFusion:
         n = c_i(0)
         _chk(lib().ef_get_tracker_fallbacks(self.h, C.byref(n)), self.h)
         return n.value
+
+    def trackerPlan(self) -> dict:
+        """which launches the last tracked frame ran (ef_get_tracker_plan): script 0 / 1 / 2, n_small, n_iter, levels (one per iteration inside the
+        one launch), res_bytes, res_budget; host state only, synchronises nothing"""
+        p = ef_tracker_plan()
+        _chk(lib().ef_get_tracker_plan(self.h, C.byref(p)), self.h)
+        n = p.n_iter if p.script == 1 else p.n_small
+        return dict(script=p.script, n_small=p.n_small, n_iter=p.n_iter, levels=[(p.levels >> (2 * i)) & 3 for i in range(n)],
+                    res_bytes=p.res_bytes, res_budget=p.res_budget)
 
     def debugOccupy(self, workgroups: int, microseconds: int):
         """test hook: CU-filling workgroups spinning on a stream of their own (ef_debug_occupy)"""

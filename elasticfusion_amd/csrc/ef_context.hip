@@ -242,7 +242,7 @@ struct ef_ctx {
   bool fused_step = false;       // ef_set_fused_step: level-0 update step inside the correspondence-search launch
   int persistent = 1;            // ef_set_persistent_tracker: 1 = the whole tracker as one persistent launch of 256 workgroups, 0 = one launch per step,
                                  // 2 = (reference-order builds) round 3's launch of the small levels on 128 workgroups
-  struct TrackGraph { hipGraphExec_t exec = nullptr; const void* key = nullptr; eft::TrackParams tp{}; eft::TrackTail tail{}; };
+  struct TrackGraph { hipGraphExec_t exec = nullptr; const void* key = nullptr; eft::TrackParams tp{}; eft::TrackTail tail{}; eft::TrackerPlan plan{}; };
   TrackGraph tgraph[2];
   // HIP-event sampling (ef_kernel_timing) of the dominant kernel (level 0 of the launch-per-step script), of the IndexMap point splat
   // (k_index_splat of the first predictIndices of a frame) and of the persistent tracker launch

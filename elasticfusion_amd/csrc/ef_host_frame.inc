@@ -126,6 +126,7 @@ int track_replayed(ef_ctx* c, const eft::TrackParams& tp, eft::TrackTail* tail) 
     hipGraph_t graph = nullptr;
     EF_HIP(c, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     g->tail = eft::track(pyr_copy, c->st, c->intr, tp, s, nullptr);
+    g->plan = pyr_copy.plan;
     hipError_t ce = hipStreamEndCapture(s, &graph);   // always ends the capture, whatever was recorded
     if (ce == hipSuccess) ce = hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0);
     if (graph) (void)hipGraphDestroy(graph);
@@ -139,6 +140,7 @@ int track_replayed(ef_ctx* c, const eft::TrackParams& tp, eft::TrackTail* tail) 
   }
   EF_HIP(c, hipGraphLaunch(g->exec, s));
   eft::track_swap(c->pyr, tp);
+  c->pyr.plan = g->plan;
   *tail = g->tail;
   return EF_OK;
 }

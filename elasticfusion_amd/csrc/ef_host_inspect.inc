@@ -73,6 +73,13 @@ int ef_get_tracker_fallbacks(ef_ctx* c, int* count) {
   *count = total;
   return EF_OK;
 }
+// host state only: nothing is enqueued, nothing synchronised
+int ef_get_tracker_plan(ef_ctx* c, ef_tracker_plan* out) {
+  if (!c || !out) return EF_EINVAL;
+  const eft::TrackerPlan& p = c->pyr.plan;
+  *out = ef_tracker_plan{p.script, p.n_small, p.n_iter, p.levels, p.res_bytes, p.res_budget};
+  return EF_OK;
+}
 // test hook: raises the sticky abort flag of the frame tracker's persistent launches, as a wait that timed out would
 int ef_debug_inject_tracker_abort(ef_ctx* c) {
   if (!c) return EF_EINVAL;

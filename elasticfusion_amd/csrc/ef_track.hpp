@@ -106,6 +106,17 @@ struct TrackState {
   float R_wc_f[9], t_wc_f[3]; // T_wc.rotationMatrix().cast<float>()    (RGBDOdometry.cpp:192-193)
 };
 
+// What track() decided for its last call on a tracker instance (host side, written by track(); ef_get_tracker_plan reads it).  script: 0 = one
+// launch per step, 1 = the persistent launch of the whole call, 2 = the launch of the small levels + one launch per remaining step.
+struct TrackerPlan {
+  int script = 0;
+  int n_small = 0;                 // script 2: iterations inside k_track_small
+  int n_iter = 0;                  // iterations of the call
+  unsigned long long levels = 0;   // the level of each iteration inside the one launch (script 1: all n_iter, script 2: the first n_small), two bits each
+  unsigned res_bytes = 0;          // script 1: dynamic LDS of the launch (level-resident pixel data)
+  unsigned res_budget = 0;         // what rt_res_budget() answered when the launch was planned (0: never asked)
+};
+
 struct Pyramid {               // one RGBDOdometry instance's device buffers (RGBDOdometry.h:87-140)
   int width, height;
   uint16_t* depth_tmp[NUM_PYRS];
@@ -130,6 +141,7 @@ struct Pyramid {               // one RGBDOdometry instance's device buffers (RG
   // host side: what the sticky words of the exchange areas held when a context switched scripts (the areas are cleared at a switch: ADVICE r5) —
   // tracker_aborted / tracker_fallbacks add them to what the device holds now
   unsigned sticky_abort = 0, fallbacks_base = 0;
+  TrackerPlan plan;                // host side: what the last track() on this instance ran
   int W(int l) const { return width >> l; }
   int H(int l) const { return height >> l; }
 };

@@ -224,6 +224,7 @@ TrackTail launch_persistent(Pyramid& p, TrackState* st, Intr k, const TrackParam
   // level-resident pixel data (ef_track_ref_persistent.inc, rt_res_mode): the largest need of a level whose slots fit — both sides, or the
   // ICP side alone (1280 x 960 level 0) — under what the chip gives one workgroup beside the kernel's static LDS
   unsigned res_bytes = 0;
+  if (!tp.no_resident) p.plan.res_budget = rt_res_budget();
   if (!tp.no_resident && rt_res_budget() > 0) {
     for (int i = 0; i < NUM_PYRS; ++i) {
       if (sp.iterations[i] == 0) continue;
@@ -234,7 +235,9 @@ TrackTail launch_persistent(Pyramid& p, TrackState* st, Intr k, const TrackParam
     }
   }
   FA.res_bytes = res_bytes;
+  p.plan.res_bytes = res_bytes;
 #endif
+  p.plan.levels = FA.levels;
   const bool sample_all = probe_all && probe_all->used < probe_all->capacity;
   hipEvent_t e0 = sample_all ? probe_all->start[probe_all->used] : nullptr, e1 = sample_all ? probe_all->stop[probe_all->used] : nullptr;
   if (sample_all) probe_all->used++;
@@ -342,6 +345,7 @@ TrackTail track(Pyramid& p, TrackState* st, Intr k, const TrackParams& tp, hipSt
   const bool capturing = is_capturing(s);
   const ScriptPlan sp = plan_script(p, tp, capturing);
   switch_script(p, sp.exchange_mode(), s, capturing);   // another script of this instance may have left anything in the exchange areas
+  p.plan = TrackerPlan{sp.script, sp.n_small, sp.n_total, sp.levels, 0u, p.plan.res_budget};
   if (sp.script == 1) return launch_persistent(p, st, k, tp, sp, s, probe_all);
   if (sp.script == 2) launch_small_levels(p, st, k, tp, sp, s);
   else launch_begin_so3(p, st, k, tp, sp, s);

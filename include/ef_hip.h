@@ -960,6 +960,19 @@ int ef_get_tracker_timing(ef_ctx* ctx, ef_kernel_time* out);
  * workgroups) that found part of the chip taken by other work and ran on one workgroup instead: same results, ~25x the tracking time, nothing for
  * the caller to do — a server that sees the count grow is sharing the GPU with something that holds CUs for milliseconds.  Synchronises. */
 int ef_get_tracker_fallbacks(ef_ctx* ctx, int* count);
+/* Which launches the frame-to-model tracker's last RGBDOdometry::getIncrementalTransformation ran (all zero before the first tracked frame).
+ * script: 0 = one launch per step, 1 = the whole call as one persistent launch, 2 = the launch of the small levels, then one launch per
+ * remaining step (ef_set_persistent_tracker; graph replay and rgbOnly run script 0 whatever was asked).  n_iter: Gauss-Newton iterations of the
+ * call; n_small: how many of them ran inside script 2's launch; levels: the pyramid level of each iteration inside the one launch (script 1:
+ * all n_iter, script 2: the first n_small; 0 otherwise), two bits each, the first iteration lowest.  res_bytes: dynamic LDS of script 1's launch
+ * (its levels' resident pixel data; 0 = every level streams); res_budget: what the device allows for it (0 = not asked yet, or none).
+ * Reads host state only: enqueues and synchronises nothing, and answers whatever the stream is doing. */
+typedef struct ef_tracker_plan {
+  int script, n_small, n_iter;
+  unsigned long long levels;
+  unsigned res_bytes, res_budget;
+} ef_tracker_plan;
+int ef_get_tracker_plan(ef_ctx* ctx, ef_tracker_plan* out);
 /* developer instrumentation for the test of that path: `workgroups` workgroups that each fill one CU spin for `microseconds` on a stream of their own */
 int ef_debug_occupy(ef_ctx* ctx, int workgroups, int microseconds);
 /* developer instrumentation: lanes that share one query of ef_query_nearest / ef_query_knn (1, 8; nearest also 16, 64; 0 = the default: 16 for nearest, 1 for kNN).  Results do not
