@@ -42,6 +42,22 @@ class ef_cam(C.Structure):
     _fields_ = [("cols", c_i), ("rows", c_i), ("fx", c_f), ("fy", c_f), ("cx", c_f), ("cy", c_f)]
 
 
+class ef_gn_state(C.Structure):   # what one Gauss-Newton update hands to the next (ef_op_gn_update)
+    _fields_ = [("Rcurr", c_f * 9), ("tcurr", c_f * 3), ("resultRt", C.c_double * 16), ("krkinv", c_f * 9), ("kt", c_f * 3),
+                ("lastRGBErrorLevel", c_f), ("rgb_broken", c_i)]
+
+
+class ef_gn_update_args(C.Structure):
+    _fields_ = [("sums", c_f * 58), ("prev", ef_gn_state), ("Rprev", c_f * 9), ("tprev", c_f * 3), ("count", c_i), ("sigma", c_i),
+                ("icp", c_i), ("rgb", c_i), ("rgb_only", c_i), ("icp_weight", c_f), ("knext", ef_intr), ("level_changes", c_i),
+                ("split_tail", c_i)]
+
+
+class ef_track_end_out(C.Structure):
+    _fields_ = [("q", C.c_double * 4), ("t", C.c_double * 3), ("logged", C.c_double * 16), ("T_cw", c_f * 16), ("pose_f", c_f * 16),
+                ("R_wc_f", c_f * 9), ("t_wc_f", c_f * 3), ("weighting", c_f)]
+
+
 class ef_timing(C.Structure):
     _fields_ = [("name", C.c_char_p), ("ms", c_f)]
 
@@ -1503,7 +1519,8 @@ class ops:
                                       bufs[4].p, c_i(len(g)), bufs[5].p, c_i(int(isFern)), out.p, C.byref(n), None))
         return out.to_array(np.float32, (n.value, 12))
 
-    LINALG = dict(ldlt6=0, ldlt3f=1, polar3=2, rodrigues=3, se3_inverse=4, se3_log_norm=5, scalar=6, ldlt6_wave=7)
+    LINALG = dict(ldlt6=0, ldlt3f=1, polar3=2, rodrigues=3, se3_inverse=4, se3_log_norm=5, scalar=6, ldlt6_wave=7, ldlt6_every_lane=8,
+                  mat_to_quat=9, se3_mul=10, se3_castf=11, se3_inverse_f=12, m4_affine_inverse=13, ldlt_pivots=14, lu_inverse6=15)
 
     @staticmethod
     def linalg(which, vec, n_out):
@@ -1511,6 +1528,45 @@ class ops:
         v = np.ascontiguousarray(np.asarray(vec, np.float64).reshape(-1))
         out = np.zeros(n_out, np.float64)
         _chk(lib().ef_op_linalg(c_i(ops.LINALG[which]), _ptr(v), c_i(v.size), _ptr(out), c_i(n_out)))
+        return out
+
+    GN_STATE = ("Rcurr", "tcurr", "resultRt", "krkinv", "kt", "lastRGBErrorLevel", "rgb_broken")
+
+    @staticmethod
+    def gn_update(sums, prev, Rprev, tprev, count, sigma, icp, rgb, rgbOnly, icpWeight, knext, level_changes, split_tail, lastA, lastb, stats):
+        """One Gauss-Newton update step as the tracker's kernels run it, on caller-supplied state (ef_op_gn_update).  prev: dict with the
+        members of GN_STATE; knext: (fx, fy, cx, cy); lastA [36], lastb [6], stats [4] = lastICPError, lastICPCount, lastRGBError,
+        lastRGBCount before the step.  Returns (next: dict, lastA, lastb, stats) after it."""
+        a = ef_gn_update_args()
+        a.sums[:] = [float(v) for v in ops._f32(sums).reshape(58)]
+        for name in ("Rcurr", "tcurr", "krkinv", "kt"):
+            getattr(a.prev, name)[:] = [float(v) for v in ops._f32(prev[name]).reshape(-1)]
+        a.prev.resultRt[:] = [float(v) for v in np.asarray(prev["resultRt"], np.float64).reshape(16)]
+        a.prev.lastRGBErrorLevel, a.prev.rgb_broken = float(np.float32(prev["lastRGBErrorLevel"])), int(prev["rgb_broken"])
+        a.Rprev[:] = [float(v) for v in ops._f32(Rprev).reshape(9)]
+        a.tprev[:] = [float(v) for v in ops._f32(tprev).reshape(3)]
+        a.count, a.sigma, a.icp, a.rgb, a.rgb_only = int(count), int(sigma), int(icp), int(rgb), int(rgbOnly)
+        a.icp_weight, a.knext, a.level_changes, a.split_tail = float(icpWeight), ef_intr(*[float(v) for v in knext]), int(level_changes), int(split_tail)
+        nxt = ef_gn_state()
+        A = np.ascontiguousarray(np.asarray(lastA, np.float64).reshape(36)).copy()
+        b = np.ascontiguousarray(np.asarray(lastb, np.float64).reshape(6)).copy()
+        st = ops._f32(stats).reshape(4).copy()
+        _chk(lib().ef_op_gn_update(C.byref(a), C.byref(nxt), _ptr(A), _ptr(b), _ptr(st)))
+        out = {n: np.array(getattr(nxt, n)) for n in ("Rcurr", "tcurr", "resultRt", "krkinv", "kt")}
+        out["lastRGBErrorLevel"], out["rgb_broken"] = np.float32(nxt.lastRGBErrorLevel), int(nxt.rgb_broken)
+        return out, A, b, st
+
+    @staticmethod
+    def track_end_tail(Rcurr, tcurr, Rprev, tprev, q_prev, t_prev, rgb, weightMultiplier):
+        """The end of tracking on one lane (0.3 m guard, re-orthonormalisation, the float pose matrices, the velocity weighting, the logged
+        pose) on caller-supplied state (ef_op_track_end_tail); returns a dict of arrays."""
+        o = ef_track_end_out()
+        qp = np.ascontiguousarray(np.asarray(q_prev, np.float64).reshape(4))
+        tp = np.ascontiguousarray(np.asarray(t_prev, np.float64).reshape(3))
+        _chk(lib().ef_op_track_end_tail(_ptr(ops._f32(Rcurr).reshape(9)), _ptr(ops._f32(tcurr).reshape(3)), _ptr(ops._f32(Rprev).reshape(9)),
+                                        _ptr(ops._f32(tprev).reshape(3)), _ptr(qp), _ptr(tp), c_i(int(rgb)), c_f(weightMultiplier), C.byref(o)))
+        out = {n: np.array(getattr(o, n)) for n in ("q", "t", "logged", "T_cw", "pose_f", "R_wc_f", "t_wc_f")}
+        out["weighting"] = np.float32(o.weighting)
         return out
 
     @staticmethod

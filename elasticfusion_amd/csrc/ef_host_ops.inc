@@ -194,12 +194,15 @@ int ef_op_so3_step(const uint8_t* lastImage, const uint8_t* nextImage, const flo
 }  // extern "C"
 namespace {
 __global__ void k_linalg_probe(int which, const double* __restrict__ in, double* __restrict__ out) {
-  if (which == EF_LINALG_LDLT6_WAVE) {  // the one-element-per-lane factorisation the tracker uses (ef_solve_dev.hpp)
+  // the two wavefront factorisations of ef_solve_dev.hpp: the earlier one with one element per lane (kept for tests), and the whole matrix in every lane's
+  // registers, which is what the update step runs
+  if (which == EF_LINALG_LDLT6_WAVE || which == EF_LINALG_LDLT6_EVERY_LANE) {
     __shared__ efs::SolveScratch S;
     const int lane = threadIdx.x;
     if (lane < 6) S.b[lane] = in[36 + lane];
     efs::wave_sync();
-    efs::ldlt6_wave(in[lane < 36 ? lane : 0], S);
+    if (which == EF_LINALG_LDLT6_WAVE) efs::ldlt6_wave(in[lane < 36 ? lane : 0], S);
+    else efs::ldlt6_every_lane(in[lane < 36 ? lane : 0], S);
     if (lane < 6) out[lane] = S.x[lane];
     return;
   }
@@ -221,13 +224,37 @@ __global__ void k_linalg_probe(int which, const double* __restrict__ in, double*
     case EF_LINALG_SCALAR:
       out[0] = sqrt(in[0]); out[1] = in[0] / in[1]; out[2] = sin(in[0]); out[3] = cos(in[0]); out[4] = atan2(in[0], in[1]);
       break;
+    case EF_LINALG_MAT_TO_QUAT: {
+      efl::mat_to_quat(in, out);
+      efl::SE3 T;
+      efl::se3_set_rotation(T, in);
+      for (int i = 0; i < 4; ++i) out[4 + i] = T.q[i];
+      break;
+    }
+    case EF_LINALG_SE3_MUL: {
+      const efl::SE3 T = efl::se3_mul(efl::se3_from_matrix(in), efl::se3_from_matrix(in + 16));
+      for (int i = 0; i < 4; ++i) out[i] = T.q[i];
+      for (int i = 0; i < 3; ++i) out[4 + i] = T.t[i];
+      break;
+    }
+    case EF_LINALG_SE3_CASTF:
+    case EF_LINALG_SE3_INVERSE_F: {
+      float M[16];
+      if (which == EF_LINALG_SE3_CASTF) efl::se3_castf_matrix(efl::se3_from_matrix(in), M);
+      else efl::se3_inverse_matrix_f(efl::se3_from_matrix(in), M);
+      for (int i = 0; i < 16; ++i) out[i] = (double)M[i];
+      break;
+    }
+    case EF_LINALG_M4_AFFINE_INVERSE: efl::m4_affine_inverse(in, out); break;
+    case EF_LINALG_LDLT_PIVOTS: efl::ldlt_pivots<double, 6>(in, out); break;
+    case EF_LINALG_LU_INVERSE6: efl::lu_inverse<double, 6>(in, out); break;
     default: break;
   }
 }
 }  // namespace
 extern "C" {
 int ef_op_linalg(int which, const double* in, int n_in, double* out, int n_out) {
-  if (!in || !out || n_in <= 0 || n_out <= 0 || n_in > 64 || n_out > 64 || which < 0 || which > EF_LINALG_LDLT6_WAVE) return EF_EINVAL;
+  if (!in || !out || n_in <= 0 || n_out <= 0 || n_in > 64 || n_out > 64 || which < 0 || which > EF_LINALG_LU_INVERSE6) return EF_EINVAL;
   double* d;
   if (hipMalloc((void**)&d, 128 * sizeof(double)) != hipSuccess) return EF_ENOMEM;
   (void)hipMemset(d, 0, 128 * sizeof(double));
@@ -236,6 +263,44 @@ int ef_op_linalg(int which, const double* in, int n_in, double* out, int n_out) 
   hipError_t e = hipMemcpy(out, d + 64, n_out * sizeof(double), hipMemcpyDeviceToHost);
   (void)hipFree(d);
   if (e != hipSuccess) { g_create_error = hipGetErrorString(e); return EF_EHIP; }
+  return EF_OK;
+}
+
+// ---- operator tier: the update step and the end of tracking on caller-supplied state (probes in the tracker's translation unit) ----
+static_assert(sizeof(ef_gn_state) == sizeof(eft::GNState), "ef_gn_state is eft::GNState");
+int ef_op_gn_update(const ef_gn_update_args* in, ef_gn_state* next, double* lastA36, double* lastb6, float* stats4) {
+  if (!in || !next || !lastA36 || !lastb6 || !stats4 || !(in->icp || in->rgb)) return EF_EINVAL;
+  eft::GnUpdateProbe p;
+  memcpy(p.sums, in->sums, sizeof(p.sums));
+  memcpy(&p.prev, &in->prev, sizeof(p.prev));
+  memcpy(p.Rprev, in->Rprev, 36); memcpy(p.tprev, in->tprev, 12);
+  p.count = in->count; p.sigma = in->sigma;
+  p.icp = in->icp != 0; p.rgb = in->rgb != 0; p.rgbOnly = in->rgb_only != 0;
+  p.icpWeight = in->icp_weight;
+  p.knext = eft::Intr{in->knext.fx, in->knext.fy, in->knext.cx, in->knext.cy};
+  p.level_changes = in->level_changes != 0;
+  p.split_tail = in->split_tail != 0;
+  const hipError_t e = (hipError_t)eft::gn_update_op(p, (eft::GNState*)next, lastA36, lastb6, stats4);
+  if (e != hipSuccess) { g_create_error = hipGetErrorString(e); return e == hipErrorOutOfMemory ? EF_ENOMEM : EF_EHIP; }
+  return EF_OK;
+}
+int ef_op_track_end_tail(const float* Rcurr9, const float* tcurr3, const float* Rprev9, const float* tprev3, const double* q_prev4,
+                         const double* t_prev3, int rgb, float weight_multiplier, ef_track_end_out* out) {
+  if (!Rcurr9 || !tcurr3 || !Rprev9 || !tprev3 || !q_prev4 || !t_prev3 || !out) return EF_EINVAL;
+  eft::TrackState* st = new eft::TrackState();
+  memcpy(st->Rprev, Rprev9, 36); memcpy(st->tprev, tprev3, 12);
+  memcpy(st->q_prev, q_prev4, 32); memcpy(st->t_prev, t_prev3, 24);
+  float pose[12];
+  memcpy(pose, Rcurr9, 36); memcpy(pose + 9, tcurr3, 12);
+  const hipError_t e = (hipError_t)eft::track_end_tail_op(st, pose, rgb != 0, weight_multiplier, out->logged);
+  if (e == hipSuccess) {
+    memcpy(out->q, st->q, 32); memcpy(out->t, st->t, 24);
+    memcpy(out->T_cw, st->T_cw, 64); memcpy(out->pose_f, st->pose_f, 64);
+    memcpy(out->R_wc_f, st->R_wc_f, 36); memcpy(out->t_wc_f, st->t_wc_f, 12);
+    out->weighting = st->weighting;
+  }
+  delete st;
+  if (e != hipSuccess) { g_create_error = hipGetErrorString(e); return e == hipErrorOutOfMemory ? EF_ENOMEM : EF_EHIP; }
   return EF_OK;
 }
 

@@ -211,6 +211,25 @@ struct So3Args { float imageBasis[9], kinv[9], krlr[9]; };
 void so3_step_op(const So3Args& a, const uint8_t* lastImage, const uint8_t* nextImage, int cols, int rows, float* scratch,
                  float* out11_dev, hipStream_t s);
 
+// The update step between two reductions, and the end of tracking, on caller-supplied state (ef_op_gn_update / ef_op_track_end_tail):
+// one workgroup each around the device functions the tracker's kernels call, no image.  Both allocate, run and free (synchronous) and
+// return the hipError_t of the first call that failed as an int, 0 = hipSuccess (an int: this header is also compiled without the HIP runtime).
+struct GnUpdateProbe {
+  float sums[2 * SE3_ACCS];
+  GNState prev;
+  float Rprev[9], tprev[3];
+  int count, sigma;            // {count, sum diff^2} of the residual pass (spread over the RGB_SLOTS slots the step adds up)
+  bool icp, rgb, rgbOnly;
+  float icpWeight;
+  Intr knext;
+  bool level_changes;
+  bool split_tail;             // the two tails on wavefronts 0 and 1, as the persistent launch dispatches them
+};
+// lastA36 / lastb6 / stats4 {lastICPError, lastICPCount, lastRGBError, lastRGBCount}: in/out (a step that breaks leaves them alone)
+int gn_update_op(const GnUpdateProbe& p, GNState* next_host, double* lastA36, double* lastb6, float* stats4);
+// st_host: Rprev / tprev / q_prev / t_prev filled in, the rest zero; receives the state track_end_tail leaves.  pose12: Rcurr | tcurr
+int track_end_tail_op(TrackState* st_host, const float* pose12, bool rgb, float weightMultiplier, double* logged16);
+
 // ---- frame-tier launchers (device-resident state; nothing here synchronises) ----
 // initICPModel + initRGBModel's depth half: predicted (or fill-in, chosen by the dense_count tally) float4 maps ->
 // world-frame planar pyramids + model depth L0.  RGBDOdometry.cpp:171-210, :217

@@ -154,3 +154,94 @@ void so3_step_op(const So3Args& a, const uint8_t* lastImage, const uint8_t* next
   hipLaunchKernelGGL(k_so3_op, dim3(so3_grid(cols * rows)), dim3(SO3_BLOCK), 0, s, lastImage, nextImage, cols, rows, a, scratch);
   hipLaunchKernelGGL(k_final_tree_op, dim3(1), dim3(SOLVE_BLOCK), 0, s, (const float*)scratch, SO3_ACCS, op_groups(cols * rows), out11_dev);
 }
+
+// ------------------------------------------------------------------------------------------
+// probes: the update step and the end of tracking on caller-supplied state
+// ------------------------------------------------------------------------------------------
+namespace {
+// One workgroup runs the head of k_track_step (solve_prefetch, the 58 sums in LDS, solve_step_wave) on a TrackState the host filled in.
+// SPLIT_TAIL: 128 threads; the update step stops behind resultRt and its two tails run on wavefronts 0 and 1 side by side.  The three
+// lines of that dispatch are restated from k_track_ref's loop (ef_track_ref_persistent.inc) — the one piece of this probe that is a
+// copy and not a call.
+template <bool SPLIT_TAIL>
+__global__ void __launch_bounds__(128) k_gn_update_probe(TrackState* st, const float* __restrict__ sums, const StepArgs A) {
+  __shared__ efs::SolveScratch S;
+  __shared__ float sums_s[2 * SE3_ACCS];
+  const int t = threadIdx.x, wave = t >> 6;
+  const GNState* prev = &st->gn[0];
+  GNState* next = &st->gn[1];
+  efs::SolvePrefetch PF{};
+  if (t < 64) PF = efs::solve_prefetch(st, prev, &st->rgb_slots[0][0][0]);
+  if (t < 2 * SE3_ACCS) sums_s[t] = sums[t];
+  __syncthreads();
+  if (t < 64) solve_step_wave<SPLIT_TAIL>(st, prev, next, true, sums_s, A, S, PF, true);
+  __syncthreads();
+  if (SPLIT_TAIL && S.tail_pending) {   // (uniform: LDS)
+    if (wave == 0) efs::gn_tail_pose(S, next, true);
+    else if (wave == 1) efs::gn_tail_krk(A.knext, S, next, true);
+    __syncthreads();
+  }
+}
+__global__ void k_track_end_tail_probe(TrackState* st, const float* __restrict__ pose12, bool rgb, float weightMultiplier, double* traj) {
+  if (threadIdx.x != 0) return;
+  track_end_tail(st, pose12, pose12 + 9, rgb, weightMultiplier, traj, 0);
+}
+}  // namespace
+
+int gn_update_op(const GnUpdateProbe& p, GNState* next_host, double* lastA36, double* lastb6, float* stats4) {
+  TrackState* h = new TrackState();
+  h->gn[0] = p.prev;
+  for (int i = 0; i < 9; ++i) h->Rprev[i] = p.Rprev[i];
+  for (int i = 0; i < 3; ++i) h->tprev[i] = p.tprev[i];
+  for (int l = 0; l < RGB_SLOTS; ++l) {   // the totals, spread the way the residual pass's workgroups leave them
+    h->rgb_slots[0][l][0] = p.count / RGB_SLOTS + (l < p.count % RGB_SLOTS ? 1 : 0);
+    h->rgb_slots[0][l][1] = p.sigma / RGB_SLOTS + (l < p.sigma % RGB_SLOTS ? 1 : 0);
+  }
+  for (int i = 0; i < 36; ++i) h->lastA[i] = lastA36[i];
+  for (int i = 0; i < 6; ++i) h->lastb[i] = lastb6[i];
+  h->lastICPError = stats4[0]; h->lastICPCount = stats4[1]; h->lastRGBError = stats4[2]; h->lastRGBCount = stats4[3];
+  StepArgs A{true, false, p.icp, p.rgb, p.rgbOnly, p.icpWeight, p.knext, p.level_changes, 1};
+  TrackState* st = nullptr;
+  float* sums = nullptr;
+  hipError_t e = hipMalloc((void**)&st, sizeof(TrackState));
+  if (e == hipSuccess) e = hipMalloc((void**)&sums, sizeof(p.sums));
+  if (e == hipSuccess) e = hipMemcpy(st, h, sizeof(TrackState), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(sums, p.sums, sizeof(p.sums), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    if (p.split_tail) hipLaunchKernelGGL(k_gn_update_probe<true>, dim3(1), dim3(128), 0, 0, st, (const float*)sums, A);
+    else hipLaunchKernelGGL(k_gn_update_probe<false>, dim3(1), dim3(64), 0, 0, st, (const float*)sums, A);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(h, st, sizeof(TrackState), hipMemcpyDeviceToHost);
+  if (st) (void)hipFree(st);
+  if (sums) (void)hipFree(sums);
+  if (e == hipSuccess) {
+    *next_host = h->gn[1];
+    for (int i = 0; i < 36; ++i) lastA36[i] = h->lastA[i];
+    for (int i = 0; i < 6; ++i) lastb6[i] = h->lastb[i];
+    stats4[0] = h->lastICPError; stats4[1] = h->lastICPCount; stats4[2] = h->lastRGBError; stats4[3] = h->lastRGBCount;
+  }
+  delete h;
+  return (int)e;
+}
+
+int track_end_tail_op(TrackState* st_host, const float* pose12, bool rgb, float weightMultiplier, double* logged16) {
+  TrackState* st = nullptr;
+  float* pose = nullptr;
+  double* traj = nullptr;
+  hipError_t e = hipMalloc((void**)&st, sizeof(TrackState));
+  if (e == hipSuccess) e = hipMalloc((void**)&pose, 12 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&traj, 16 * sizeof(double));
+  if (e == hipSuccess) e = hipMemcpy(st, st_host, sizeof(TrackState), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(pose, pose12, 12 * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_track_end_tail_probe, dim3(1), dim3(64), 0, 0, st, (const float*)pose, rgb, weightMultiplier, traj);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(st_host, st, sizeof(TrackState), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(logged16, traj, 16 * sizeof(double), hipMemcpyDeviceToHost);
+  if (st) (void)hipFree(st);
+  if (pose) (void)hipFree(pose);
+  if (traj) (void)hipFree(traj);
+  return (int)e;
+}

@@ -1054,9 +1054,51 @@ enum ef_linalg_op {
   EF_LINALG_SE3_INVERSE,      /* in T[16]                   -> T^-1[16] Sophus::SE3d::inverse().matrix()    */
   EF_LINALG_SE3_LOG_NORM,     /* in T[16]                   -> |log(T)| Sophus::SE3d::log().norm()          */
   EF_LINALG_SCALAR,           /* in a, b -> sqrt(a), a/b, sin(a), cos(a), atan2(a,b) (fp64 device math)     */
-  EF_LINALG_LDLT6_WAVE        /* as EF_LINALG_LDLT6, through the one-element-per-lane wavefront version      */
+  EF_LINALG_LDLT6_WAVE,       /* as EF_LINALG_LDLT6, through the earlier one-element-per-lane wavefront version, kept for tests */
+  EF_LINALG_LDLT6_EVERY_LANE, /* as EF_LINALG_LDLT6, through the whole-matrix-per-lane version the update step runs  */
+  EF_LINALG_MAT_TO_QUAT,      /* in R[9]                    -> q[4] Eigen::Quaternion(Matrix3) xyzw, q[4] after Sophus' setRotationMatrix */
+  EF_LINALG_SE3_MUL,          /* in Ta[16] Tb[16]           -> q[4] t[3] of Sophus::SE3d Ta * Tb            */
+  EF_LINALG_SE3_CASTF,        /* in T[16]                   -> T.cast<float>().matrix()[16], widened        */
+  EF_LINALG_SE3_INVERSE_F,    /* in T[16]                   -> T.inverse().matrix().cast<float>()[16], widened */
+  EF_LINALG_M4_AFFINE_INVERSE,/* in M[16] (last row 0 0 0 1) -> M^-1[16]                                    */
+  EF_LINALG_LDLT_PIVOTS,      /* in A[36]                   -> d[6] the pivots of EF_LINALG_LDLT6, in elimination order */
+  EF_LINALG_LU_INVERSE6       /* in A[36]                   -> A^-1[36] Eigen::PartialPivLU inverse (getCovariance) */
 };
 int ef_op_linalg(int which, const double* in_host, int n_in, double* out_host, int n_out);
+
+/* The Gauss-Newton update step between two reductions (RGBDOdometry.cpp:440-551 + OdometryProvider.h:73-96) as the tracker's kernels run
+ * it, on caller-supplied state: one workgroup, no image.  ef_gn_state is what one update hands to the next. */
+typedef struct ef_gn_state {
+  float Rcurr[9], tcurr[3];
+  double resultRt[16];
+  float krkinv[9], kt[3];     /* K R K^-1, K t of the coming iteration */
+  float lastRGBErrorLevel;    /* rgbOnly early-exit bookkeeping */
+  int rgb_broken;
+} ef_gn_state;
+typedef struct ef_gn_update_args {
+  float sums[58];             /* the 29 + 29 members of JtJJtrSE3 (ICP, RGB; types.cuh:98-143) */
+  ef_gn_state prev;
+  float Rprev[9], tprev[3];
+  int count, sigma;           /* {count, sum diff^2} of the residual pass */
+  int icp, rgb, rgb_only;
+  float icp_weight;
+  ef_intr knext;              /* intrinsics of the coming iteration's level */
+  int level_changes;          /* the coming iteration runs at another level */
+  int split_tail;             /* 1: the step's two tails on two wavefronts side by side, as the persistent launch runs them */
+} ef_gn_update_args;
+/* lastA36, lastb6, stats4 = {lastICPError, lastICPCount, lastRGBError, lastRGBCount} are in/out: a step that takes the rgbOnly break
+ * leaves them as they are */
+int ef_op_gn_update(const ef_gn_update_args* in, ef_gn_state* next, double* lastA36, double* lastb6, float* stats4);
+/* The end of getIncrementalTransformation on one lane (0.3 m guard, re-orthonormalisation, RGBDOdometry.cpp:555-570), the float
+ * matrices of the map passes, the velocity weighting (ElasticFusion.cpp:369-383) and the logged pose, on caller-supplied state */
+typedef struct ef_track_end_out {
+  double q[4], t[3];
+  double logged[16];
+  float T_cw[16], pose_f[16], R_wc_f[9], t_wc_f[3];
+  float weighting;
+} ef_track_end_out;
+int ef_op_track_end_tail(const float* Rcurr9, const float* tcurr3, const float* Rprev9, const float* tprev3, const double* q_prev4,
+                         const double* t_prev3, int rgb, float weight_multiplier, ef_track_end_out* out);
 
 /* ---- operator tier: pre-processing and surfel map (the reference's GLSL passes) ---- */
 typedef struct ef_cam { int cols, rows; float fx, fy, cx, cy; } ef_cam;

@@ -48,14 +48,33 @@ void efo_odom_init_first_rgb(efo_odometry*, const uint8_t* rgba);
 void efo_odom_track(efo_odometry*, double* T_wc16, int rgbOnly, float icpWeight, int pyramid, int fastOdom, int so3);
 void efo_odom_stats(const efo_odometry*, float* out6, double* lastA36, double* lastb6);
 const void* efo_odom_buffer(const efo_odometry*, int which, int level);
+/* one Gauss-Newton update step / the end of tracking on caller-supplied state (efo_odometry.cpp: the functions the driver itself runs) */
+typedef struct efo_gn_state {
+  float Rcurr[9], tcurr[3];
+  double resultRt[16];
+  float krkinv[9], kt[3];
+  float lastRGBErrorLevel;
+  int rgb_broken;
+} efo_gn_state;
+void efo_gn_update(const float* sums58, const efo_gn_state* prev, const float* Rprev9, const float* tprev3, int count, int sigma, int icp,
+                   int rgb, int rgbOnly, float icpWeight, const float* knext4, int level_changes, const double* sincos2, efo_gn_state* next,
+                   double* lastA36, double* lastb6, float* stats4, double* x6);
+void efo_track_end(const float* Rcurr9, const float* tcurr3, const float* Rprev9, const float* tprev3, const double* q_prev4,
+                   const double* t_prev3, int rgb, float weightMultiplier, double* q4, double* t3, float* T_cw16, float* pose16, float* R_wc9,
+                   float* t_wc3, float* weighting, double* T_wc16);
 
 /* ---- small linear algebra (Eigen / Sophus restatement) for known-answer tests ---- */
 void efo_ldlt6(const double* A36, const double* b6, double* x6);
+void efo_ldlt_pivots(const double* A36, double* d6);   /* the pivots efo_ldlt6 divides by, in elimination order */
 void efo_ldlt3f(const float* A9, const float* b3, float* x3);
 void efo_polar3(const double* A9, double* R9);
 void efo_rodrigues(const double* v3, double* R9);
+void efo_rodrigues_sc(const double* v3, const double* sincos2, double* R9);   /* sin, cos of |v| handed in */
 void efo_se3_inverse(const double* T16, double* out16);
 double efo_se3_log_norm(const double* T16, double* out6);
+void efo_mat_to_quat(const double* R9, double* q8);   /* Eigen::Quaternion(Matrix3) xyzw, then the same after Sophus' setRotationMatrix */
+void efo_se3_mul(const double* Ta16, const double* Tb16, double* q4_t3);
+void efo_m4_affine_inverse(const double* M16, double* out16);
 float efo_expf_spec(float x);
 void efo_covariance(const double* lastA36, double* cov36);   /* getCovariance: PartialPivLU inverse of lastA */
 

@@ -9,6 +9,7 @@
 // (:593-595) is the solver callback's business (efo_sample_graph).
 #include "efo_common.h"
 #include "efo_linalg.h"
+#include "efo_pose.h"
 #include "efo_api.h"
 #include <cstdarg>
 #include <cstdio>
@@ -423,12 +424,7 @@ struct efo_fusion {
         T_wc = se3_from_matrix(in_T_wc);
       }
       // velocity weighting, :369-383
-      SE3 T_curr_prev = se3_mul(se3_inverse(T_wc), T_prev);
-      double tn = std::sqrt(T_curr_prev.t[0] * T_curr_prev.t[0] + T_curr_prev.t[1] * T_curr_prev.t[1] + T_curr_prev.t[2] * T_curr_prev.t[2]);
-      float weighting = (float)std::max(tn, se3_log_norm(T_curr_prev));
-      float largest = 0.01f, minWeight = 0.5f;
-      if (weighting > largest) weighting = largest;
-      weighting = std::max(1.0f - (weighting / largest), minWeight) * weightMultiplier;
+      float weighting = velocity_weighting(T_wc, T_prev, weightMultiplier);
       lastWeighting = weighting;
 
       predict();  // :387 (result unused when closeLoops == false; kept for fidelity)
@@ -659,13 +655,30 @@ efo_odometry* efo_fusion_odometry(efo_fusion* f) { return f->frameToModel; }
 
 // ---- linalg exports for known-answer tests ----
 void efo_ldlt6(const double* A, const double* b, double* x) { ldlt_solve<double, 6>(A, b, x); }
+void efo_ldlt_pivots(const double* A, double* d) { const double b[6] = {0, 0, 0, 0, 0, 0}; double x[6]; ldlt_solve<double, 6>(A, b, x, d); }
 void efo_ldlt3f(const float* A, const float* b, float* x) { ldlt_solve<float, 3>(A, b, x); }
 void efo_polar3(const double* A, double* R) { M3d a; std::memcpy(a.m, A, sizeof(a.m)); M3d r = polar3(a); std::memcpy(R, r.m, sizeof(r.m)); }
 void efo_rodrigues(const double* v, double* R) { M3d r = rodrigues(V3d{{v[0], v[1], v[2]}}); std::memcpy(R, r.m, sizeof(r.m)); }
+// ... with sin and cos of the angle handed in (efo_linalg.h rodrigues(): for comparisons with an evaluation on another libm, bit for bit)
+void efo_rodrigues_sc(const double* v, const double* sincos2, double* R) { M3d r = rodrigues(V3d{{v[0], v[1], v[2]}}, sincos2); std::memcpy(R, r.m, sizeof(r.m)); }
 void efo_se3_inverse(const double* T, double* out) { M4d m = se3_matrix(se3_inverse(se3_from_matrix(T))); std::memcpy(out, m.m, sizeof(m.m)); }
 double efo_se3_log_norm(const double* T, double* out6) { return se3_log_norm(se3_from_matrix(T), out6); }
 float efo_expf_spec(float x) { return efo_expf(x); }
 // RGBDOdometry::getCovariance (RGBDOdometry.cpp:573-575): lastA.cast<double>().lu().inverse()
+void efo_mat_to_quat(const double* R, double* q8) {
+  M3d r;
+  std::memcpy(r.m, R, sizeof(r.m));
+  mat_to_quat(r, q8);
+  SE3 T;
+  se3_set_rotation(T, r);
+  std::memcpy(q8 + 4, T.q, sizeof(T.q));
+}
+void efo_se3_mul(const double* Ta, const double* Tb, double* qt) {
+  SE3 r = se3_mul(se3_from_matrix(Ta), se3_from_matrix(Tb));
+  std::memcpy(qt, r.q, sizeof(r.q));
+  std::memcpy(qt + 4, r.t, sizeof(r.t));
+}
+void efo_m4_affine_inverse(const double* M, double* out) { M4d m; std::memcpy(m.m, M, sizeof(m.m)); M4d r = m4_affine_inverse(m); std::memcpy(out, r.m, sizeof(r.m)); }
 void efo_covariance(const double* lastA36, double* cov36) { lu_inverse<double, 6>(lastA36, cov36); }
 
 }  // extern "C"

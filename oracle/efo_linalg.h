@@ -115,8 +115,9 @@ inline M4d m4_affine_inverse(const M4d& a) {
 
 // Symmetric N x N solve by LDL^T with diagonal (symmetric) pivoting, the scheme Eigen::LDLT uses:
 // at step k pick the largest |diagonal| of the trailing block, swap rows+cols, eliminate.
+// pivots: null, or N values to fill with the diagonal entry each step divides by, in elimination order.
 template <typename T, int N>
-inline void ldlt_solve(const T* A_in, const T* b_in, T* x) {
+inline void ldlt_solve(const T* A_in, const T* b_in, T* x, T* pivots = nullptr) {
   T A[N * N];
   int perm[N];
   for (int i = 0; i < N * N; ++i) A[i] = A_in[i];
@@ -134,6 +135,7 @@ inline void ldlt_solve(const T* A_in, const T* b_in, T* x) {
       std::swap(perm[k], perm[p]);
     }
     T d = A[k * N + k];
+    if (pivots) pivots[k] = d;
     if (d == T(0)) continue;  // singular direction: leave (Eigen zeroes the remaining factor)
     T colk[N];
     for (int i = k + 1; i < N; ++i) colk[i] = A[i * N + k];
@@ -163,13 +165,15 @@ inline void ldlt_solve(const T* A_in, const T* b_in, T* x) {
 }
 
 // OdometryProvider::rodrigues (OdometryProvider.h:34-71)
-inline M3d rodrigues(const V3d& src) {
+// sincos: null, or {sin(theta), cos(theta)} to use instead of this libm's (a test that compares with an evaluation on another libm bit for
+// bit hands that libm's two values in; everything else is IEEE +, -, *, /, sqrt)
+inline M3d rodrigues(const V3d& src, const double* sincos = nullptr) {
   M3d dst = m3_identity();
   double rx = src.v[0], ry = src.v[1], rz = src.v[2];
   double theta = std::sqrt(rx * rx + ry * ry + rz * rz);
   if (theta >= DBL_EPSILON) {
     const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    double c = std::cos(theta), s = std::sin(theta), c1 = 1. - c;
+    double c = sincos ? sincos[1] : std::cos(theta), s = sincos ? sincos[0] : std::sin(theta), c1 = 1. - c;
     double itheta = theta ? 1. / theta : 0.;
     rx *= itheta; ry *= itheta; rz *= itheta;
     double rrt[9] = {rx * rx, rx * ry, rx * rz, rx * ry, ry * ry, ry * rz, rx * rz, ry * rz, rz * rz};

@@ -9,11 +9,84 @@
 // efo_linalg.h; the device operators it calls are pinned against the compiled reference (efo_track.cpp).
 #include "efo_common.h"
 #include "efo_linalg.h"
+#include "efo_pose.h"
 #include "efo_api.h"
 #include <vector>
 #include <cassert>
 
 using namespace efo;
+
+namespace {
+// K R K^-1 and K t of an iteration, from the inverse of resultRt (RGBDOdometry.cpp:395-417)
+void krk_of(const M4d& resultRt, const M3d& K, float* krkInv, float* kt) {
+  M4d Rt = m4_affine_inverse(resultRt);
+  M3d R;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) R.m[r * 3 + c] = Rt.m[r * 4 + c];
+  M3d KRK_inv = m3_mul(m3_mul(K, R), m3_inverse(K));
+  for (int i = 0; i < 9; ++i) krkInv[i] = (float)KRK_inv.m[i];
+  V3d Kt = m3_mulv(K, V3d{{Rt.m[3], Rt.m[7], Rt.m[11]}});
+  for (int i = 0; i < 3; ++i) kt[i] = (float)Kt.v[i];
+}
+
+// What one iteration of getIncrementalTransformation does on the host behind its reductions (RGBDOdometry.cpp:440-551 +
+// OdometryProvider.h:73-96): the photometric error with the rgbOnly "break", the statistics, A = A_rgb + w^2 A_icp and b, the 6x6 solve,
+// computeUpdateSE3, resultRt = upd * resultRt, and the float pose of the coming iteration.  Returns false at the break: nothing has changed
+// then.  residual: what icpStep left ({0, 0} while the ICP term has never run).  sincos: see rodrigues().  result6: the solution, or null.
+// The driver below and efo_gn_update (the reference of the device's update step) both call it.
+bool gn_update(bool icp, bool rgb, bool rgbOnly, float icpWeight, int sigma, int rgbSize, const float* A_icp, const float* b_icp,
+               const float* residual, const float* A_rgbd, const float* b_rgbd, const float* Rprev, const float* tprev, const double* sincos,
+               M4d& resultRt, float* Rcurr, float* tcurr, float& lastRGBError, float& lastRGBCount, float& lastICPError, float& lastICPCount,
+               double* lastA, double* lastb, double* result6) {
+  float rgbError = (float)(std::sqrt((double)sigma) / (rgbSize == 0 ? 1 : rgbSize));  // std::sqrt(int) is double
+  if (rgbOnly && rgbError > lastRGBError) return false;
+  lastRGBError = rgbError;
+  lastRGBCount = (float)rgbSize;
+  lastICPError = sqrtf(residual[0]) / residual[1];
+  lastICPCount = residual[1];
+
+  double result[6];
+  if (icp && rgb) {
+    double w = icpWeight;
+    for (int k = 0; k < 36; ++k) lastA[k] = (double)A_rgbd[k] + w * w * (double)A_icp[k];
+    for (int k = 0; k < 6; ++k) lastb[k] = (double)b_rgbd[k] + w * (double)b_icp[k];
+  } else if (icp) {
+    for (int k = 0; k < 36; ++k) lastA[k] = A_icp[k];
+    for (int k = 0; k < 6; ++k) lastb[k] = b_icp[k];
+  } else {
+    for (int k = 0; k < 36; ++k) lastA[k] = A_rgbd[k];
+    for (int k = 0; k < 6; ++k) lastb[k] = b_rgbd[k];
+  }
+  ldlt_solve<double, 6>(lastA, lastb, result);
+  if (result6) std::memcpy(result6, result, sizeof(result));
+
+  // OdometryProvider::computeUpdateSE3, OdometryProvider.h:73-96
+  M4d upd = m4_identity();
+  M3d Rr = rodrigues(V3d{{result[3], result[4], result[5]}}, sincos);
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) upd.m[r * 4 + c] = Rr.m[r * 3 + c];
+    upd.m[r * 4 + 3] = result[r];
+  }
+  resultRt = m4_mul(upd, resultRt);
+  // rgbOdom (Isometry3f) = float cast of resultRt;  currentT = [Rprev|tprev] * rgbOdom^-1, with
+  // Isometry inverse = (R^T, -R^T t) and Isometry::rotation() = linear()  (Q13)
+  float oR[9], ot[3];
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) oR[r * 3 + c] = (float)resultRt.m[r * 4 + c];
+    ot[r] = (float)resultRt.m[r * 4 + 3];
+  }
+  float iR[9], it[3];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) iR[r * 3 + c] = oR[c * 3 + r];
+  for (int r = 0; r < 3; ++r) it[r] = -(iR[r * 3] * ot[0] + iR[r * 3 + 1] * ot[1] + iR[r * 3 + 2] * ot[2]);
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c)
+      Rcurr[r * 3 + c] = Rprev[r * 3] * iR[c] + Rprev[r * 3 + 1] * iR[3 + c] + Rprev[r * 3 + 2] * iR[6 + c];
+    tcurr[r] = (Rprev[r * 3] * it[0] + Rprev[r * 3 + 1] * it[1] + Rprev[r * 3 + 2] * it[2]) + tprev[r];
+  }
+  return true;
+}
+}  // namespace
 
 struct efo_odometry {
   static constexpr int NUM_PYRS = 3;  // RGBDOdometry.h:114
@@ -203,15 +276,8 @@ struct efo_odometry {
       lastRGBError = std::numeric_limits<float>::max();
 
       for (int j = 0; j < iterations[i]; ++j) {
-        M4d Rt = m4_affine_inverse(resultRt);
-        M3d R;
-        for (int r = 0; r < 3; ++r)
-          for (int c = 0; c < 3; ++c) R.m[r * 3 + c] = Rt.m[r * 4 + c];
-        M3d KRK_inv = m3_mul(m3_mul(K, R), m3_inverse(K));
-        float krkInv[9];
-        to_f33(KRK_inv, krkInv);
-        V3d Kt = m3_mulv(K, V3d{{Rt.m[3], Rt.m[7], Rt.m[11]}});
-        float kt[3] = {(float)Kt.v[0], (float)Kt.v[1], (float)Kt.v[2]};
+        float krkInv[9], kt[3];
+        krk_of(resultRt, K, krkInv, kt);
 
         int sigma = 0, rgbSize = 0;
         if (rgb) {
@@ -222,77 +288,25 @@ struct efo_odometry {
         }
         // Q2: precedence makes this sqrt(rgbSize) unless (float)sigma/rgbSize == 0 (RGBDOdometry.cpp:442)
         float sigmaVal = std::sqrt((float)sigma / rgbSize == 0 ? 1 : rgbSize);
-        float rgbError = (float)(std::sqrt((double)sigma) / (rgbSize == 0 ? 1 : rgbSize));  // std::sqrt(int) is double
-        if (rgbOnly && rgbError > lastRGBError) break;
-        lastRGBError = rgbError;
-        lastRGBCount = (float)rgbSize;
         if (rgbOnly) sigmaVal = -1;
-
+        // the break (:445-450) is taken inside gn_update, behind the two steps here: under rgbOnly the ICP step does not run, and the
+        // photometric step only fills its own outputs, so evaluating it in the iteration that breaks changes nothing
         float A_icp[36] = {0}, b_icp[6] = {0}, A_rgbd[36] = {0}, b_rgbd[6] = {0};
         if (icp)
           efo_icp_step(Rcurr, tcurr, vmaps_curr[i].data(), nmaps_curr[i].data(), Rprev_inv, tprev, fx_, fy_, cx_, cy_,
                        vmaps_g_prev[i].data(), nmaps_g_prev[i].data(), distThres, angleThres, W(i), H(i), A_icp, b_icp, residual);
-        lastICPError = sqrtf(residual[0]) / residual[1];
-        lastICPCount = residual[1];
         if (rgb)
           efo_rgb_step(corresImg[i].data(), sigmaVal, pointClouds[i].data(), fx_, fy_, nextdIdx[i].data(), nextdIdy[i].data(),
                        sobelScale, W(i), H(i), A_rgbd, b_rgbd);
-
-        double result[6];
-        if (icp && rgb) {
-          double w = icpWeight;
-          for (int k = 0; k < 36; ++k) lastA[k] = (double)A_rgbd[k] + w * w * (double)A_icp[k];
-          for (int k = 0; k < 6; ++k) lastb[k] = (double)b_rgbd[k] + w * (double)b_icp[k];
-        } else if (icp) {
-          for (int k = 0; k < 36; ++k) lastA[k] = A_icp[k];
-          for (int k = 0; k < 6; ++k) lastb[k] = b_icp[k];
-        } else {
-          for (int k = 0; k < 36; ++k) lastA[k] = A_rgbd[k];
-          for (int k = 0; k < 6; ++k) lastb[k] = b_rgbd[k];
-        }
-        ldlt_solve<double, 6>(lastA, lastb, result);
-
-        // OdometryProvider::computeUpdateSE3, OdometryProvider.h:73-96
-        M4d upd = m4_identity();
-        M3d Rr = rodrigues(V3d{{result[3], result[4], result[5]}});
-        for (int r = 0; r < 3; ++r) {
-          for (int c = 0; c < 3; ++c) upd.m[r * 4 + c] = Rr.m[r * 3 + c];
-          upd.m[r * 4 + 3] = result[r];
-        }
-        resultRt = m4_mul(upd, resultRt);
-        // rgbOdom (Isometry3f) = float cast of resultRt;  currentT = [Rprev|tprev] * rgbOdom^-1, with
-        // Isometry inverse = (R^T, -R^T t) and Isometry::rotation() = linear()  (Q13)
-        float oR[9], ot[3];
-        for (int r = 0; r < 3; ++r) {
-          for (int c = 0; c < 3; ++c) oR[r * 3 + c] = (float)resultRt.m[r * 4 + c];
-          ot[r] = (float)resultRt.m[r * 4 + 3];
-        }
-        float iR[9], it[3];
-        for (int r = 0; r < 3; ++r)
-          for (int c = 0; c < 3; ++c) iR[r * 3 + c] = oR[c * 3 + r];
-        for (int r = 0; r < 3; ++r) it[r] = -(iR[r * 3] * ot[0] + iR[r * 3 + 1] * ot[1] + iR[r * 3 + 2] * ot[2]);
-        for (int r = 0; r < 3; ++r) {
-          for (int c = 0; c < 3; ++c)
-            Rcurr[r * 3 + c] = Rprev[r * 3] * iR[c] + Rprev[r * 3 + 1] * iR[3 + c] + Rprev[r * 3 + 2] * iR[6 + c];
-          tcurr[r] = (Rprev[r * 3] * it[0] + Rprev[r * 3 + 1] * it[1] + Rprev[r * 3 + 2] * it[2]) + tprev[r];
-        }
+        if (!gn_update(icp, rgb, rgbOnly, icpWeight, sigma, rgbSize, A_icp, b_icp, residual, A_rgbd, b_rgbd, Rprev, tprev, nullptr, resultRt,
+                       Rcurr, tcurr, lastRGBError, lastRGBCount, lastICPError, lastICPCount, lastA, lastb, nullptr))
+          break;
       }
     }
 
-    if (rgb) {  // :555-558
-      float d0 = tcurr[0] - tprev[0], d1 = tcurr[1] - tprev[1], d2 = tcurr[2] - tprev[2];
-      if (sqrtf(d0 * d0 + d1 * d1 + d2 * d2) > 0.3) {
-        std::memcpy(Rcurr, Rprev, sizeof(Rcurr));
-        std::memcpy(tcurr, tprev, sizeof(tcurr));
-      }
-    }
     if (so3)
       for (int i = 0; i < NUM_PYRS; ++i) std::swap(lastNextImage[i], nextImage[i]);
-
-    M3d Rc;
-    for (int k = 0; k < 9; ++k) Rc.m[k] = (double)Rcurr[k];
-    for (int k = 0; k < 3; ++k) T_wc.t[k] = (double)tcurr[k];
-    se3_set_rotation(T_wc, polar3(Rc));
+    track_end_pose(rgb, Rcurr, tcurr, Rprev, tprev, T_wc);   // :555-570
   }
 };
 
@@ -344,6 +358,65 @@ const void* efo_odom_buffer(const efo_odometry* o, int which, int level) {
     case 14: return o->corresImg[level].data();
   }
   return nullptr;
+}
+
+// One update step on caller-supplied state: gn_update above (what the driver's loop runs), then what the loop does around it — the
+// K R K^-1 / K t of the coming iteration at ITS level's intrinsics (:395-417), and the rgbOnly break (:445-450) as state: an iteration
+// that breaks, and every later one of the same level (prev->rgb_broken), changes nothing; with level_changes the coming iteration is the
+// first of the next level, where lastRGBError starts at the largest float again (:437) and the flag is clear.  sums58: the 29 + 29
+// members of JtJJtrSE3 (ICP, RGB; types.cuh:98-143) as the reductions leave them.  stats4 = {lastICPError, lastICPCount, lastRGBError,
+// lastRGBCount}, lastA36 and lastb6 are in/out: a step that breaks leaves them alone.  sincos2: null or {sin, cos} of the increment's
+// angle (rodrigues()); x6: the solution of the 6x6 system, or null.
+void efo_gn_update(const float* sums58, const efo_gn_state* prev, const float* Rprev9, const float* tprev3, int count, int sigma, int icp,
+                   int rgb, int rgbOnly, float icpWeight, const float* knext4, int level_changes, const double* sincos2, efo_gn_state* next,
+                   double* lastA36, double* lastb6, float* stats4, double* x6) {
+  float A[2][36], b[2][6];
+  for (int term = 0; term < 2; ++term) {   // reduce.cu:385-400
+    int shift = 0;
+    for (int i = 0; i < 6; ++i)
+      for (int j = i; j < 7; ++j) {
+        const float value = sums58[term * 29 + shift++];
+        if (j == 6) b[term][i] = value;
+        else A[term][j * 6 + i] = A[term][i * 6 + j] = value;
+      }
+  }
+  const float residual[2] = {icp ? sums58[27] : 0.f, icp ? sums58[28] : 0.f};
+  *next = *prev;
+  M4d resultRt;
+  std::memcpy(resultRt.m, prev->resultRt, sizeof(resultRt.m));
+  float lastRGBError = prev->lastRGBErrorLevel;
+  const bool went = !prev->rgb_broken &&
+                    gn_update(icp != 0, rgb != 0, rgbOnly != 0, icpWeight, sigma, count, A[0], b[0], residual, A[1], b[1], Rprev9, tprev3, sincos2,
+                              resultRt, next->Rcurr, next->tcurr, lastRGBError, stats4[3], stats4[0], stats4[1], lastA36, lastb6, x6);
+  if (went) stats4[2] = lastRGBError;
+  std::memcpy(next->resultRt, resultRt.m, sizeof(resultRt.m));
+  next->rgb_broken = (went || level_changes) ? 0 : 1;
+  next->lastRGBErrorLevel = level_changes ? std::numeric_limits<float>::max() : lastRGBError;
+  if (went || level_changes) {
+    M3d K{};
+    K.m[0] = knext4[0]; K.m[4] = knext4[1]; K.m[2] = knext4[2]; K.m[5] = knext4[3]; K.m[8] = 1;
+    krk_of(resultRt, K, next->krkinv, next->kt);
+  }
+}
+
+// The end of tracking on caller-supplied state: track_end_pose (the driver's last statements), the float matrices every map pass derives
+// from the pose (efo_pose_matrices, RGBDOdometry.cpp:192-193) and the velocity weighting of the frame (ElasticFusion.cpp:369-383).
+void efo_track_end(const float* Rcurr9, const float* tcurr3, const float* Rprev9, const float* tprev3, const double* q_prev4,
+                   const double* t_prev3, int rgb, float weightMultiplier, double* q4, double* t3, float* T_cw16, float* pose16, float* R_wc9,
+                   float* t_wc3, float* weighting, double* T_wc16) {
+  SE3 T, Tp;
+  std::memcpy(Tp.q, q_prev4, sizeof(Tp.q));
+  std::memcpy(Tp.t, t_prev3, sizeof(Tp.t));
+  track_end_pose(rgb != 0, Rcurr9, tcurr3, Rprev9, tprev3, T);
+  std::memcpy(q4, T.q, sizeof(T.q));
+  std::memcpy(t3, T.t, sizeof(T.t));
+  M4d M = se3_matrix(T);
+  std::memcpy(T_wc16, M.m, sizeof(M.m));
+  efo_pose_matrices(M.m, T_cw16, pose16);
+  M3d Rd = se3_rotation(T);
+  for (int i = 0; i < 9; ++i) R_wc9[i] = (float)Rd.m[i];
+  for (int i = 0; i < 3; ++i) t_wc3[i] = (float)T.t[i];
+  *weighting = velocity_weighting(T, Tp, weightMultiplier);
 }
 
 }  // extern "C"

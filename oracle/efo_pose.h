@@ -35,4 +35,32 @@ inline Mat4f pose_castf(const double* T_wc16) {
   return r;
 }
 
+// The end of getIncrementalTransformation (RGBDOdometry.cpp:555-570): the 0.3 m guard of the photometric term, then the pose from the
+// float Rcurr / tcurr with the rotation re-orthonormalised (JacobiSVD U V^T).
+inline void track_end_pose(bool rgb, const float* Rcurr_in, const float* tcurr_in, const float* Rprev, const float* tprev, SE3& T_wc) {
+  float Rcurr[9], tcurr[3];
+  std::memcpy(Rcurr, Rcurr_in, sizeof(Rcurr));
+  std::memcpy(tcurr, tcurr_in, sizeof(tcurr));
+  if (rgb) {  // :555-558
+    float d0 = tcurr[0] - tprev[0], d1 = tcurr[1] - tprev[1], d2 = tcurr[2] - tprev[2];
+    if (sqrtf(d0 * d0 + d1 * d1 + d2 * d2) > 0.3) {
+      std::memcpy(Rcurr, Rprev, sizeof(Rcurr));
+      std::memcpy(tcurr, tprev, sizeof(tcurr));
+    }
+  }
+  M3d Rc;
+  for (int k = 0; k < 9; ++k) Rc.m[k] = (double)Rcurr[k];
+  for (int k = 0; k < 3; ++k) T_wc.t[k] = (double)tcurr[k];
+  se3_set_rotation(T_wc, polar3(Rc));
+}
+// velocity weighting of the fusion (ElasticFusion.cpp:369-383)
+inline float velocity_weighting(const SE3& T_wc, const SE3& T_prev, float weightMultiplier) {
+  SE3 T_curr_prev = se3_mul(se3_inverse(T_wc), T_prev);
+  double tn = std::sqrt(T_curr_prev.t[0] * T_curr_prev.t[0] + T_curr_prev.t[1] * T_curr_prev.t[1] + T_curr_prev.t[2] * T_curr_prev.t[2]);
+  float weighting = (float)std::max(tn, se3_log_norm(T_curr_prev));
+  float largest = 0.01f, minWeight = 0.5f;
+  if (weighting > largest) weighting = largest;
+  return std::max(1.0f - (weighting / largest), minWeight) * weightMultiplier;
+}
+
 }  // namespace efo

@@ -510,6 +510,44 @@ class Odometry:
         return arr.view(dt).reshape(h * planes, w).copy()
 
 
+class GnState(C.Structure):   # efo_gn_state: what one Gauss-Newton update hands to the next
+    _fields_ = [("Rcurr", c_f * 9), ("tcurr", c_f * 3), ("resultRt", C.c_double * 16), ("krkinv", c_f * 9), ("kt", c_f * 3),
+                ("lastRGBErrorLevel", c_f), ("rgb_broken", c_i)]
+
+
+def gn_update(sums, prev, Rprev, tprev, count, sigma, icp, rgb, rgbOnly, icpWeight, knext, level_changes, lastA, lastb, stats, sincos=None):
+    """One update step of the driver's loop on caller-supplied state (efo_gn_update); the arguments and the first four results are those
+    of elasticfusion_amd.api.ops.gn_update, the fifth is the solution of the 6x6 system (NaN where the step took the rgbOnly break).
+    sincos: None or (sin, cos) of the increment's angle, to use instead of this machine's libm."""
+    p, n = GnState(), GnState()
+    for name in ("Rcurr", "tcurr", "krkinv", "kt"):
+        getattr(p, name)[:] = [float(v) for v in f32(prev[name]).reshape(-1)]
+    p.resultRt[:] = [float(v) for v in np.asarray(prev["resultRt"], np.float64).reshape(16)]
+    p.lastRGBErrorLevel, p.rgb_broken = float(np.float32(prev["lastRGBErrorLevel"])), int(prev["rgb_broken"])
+    A = np.ascontiguousarray(np.asarray(lastA, np.float64).reshape(36)).copy()
+    b = np.ascontiguousarray(np.asarray(lastb, np.float64).reshape(6)).copy()
+    st = f32(stats).reshape(4).copy()
+    x = np.full(6, np.nan)
+    sc = None if sincos is None else np.array(sincos, np.float64)
+    lib().efo_gn_update(ptr(f32(sums).reshape(58)), C.byref(p), ptr(f32(Rprev).reshape(9)), ptr(f32(tprev).reshape(3)), c_i(int(count)),
+                        c_i(int(sigma)), c_i(int(icp)), c_i(int(rgb)), c_i(int(rgbOnly)), c_f(icpWeight), ptr(f32(knext)), c_i(int(level_changes)),
+                        None if sc is None else ptr(sc), C.byref(n), ptr(A), ptr(b), ptr(st), ptr(x))
+    out = {k: np.array(getattr(n, k)) for k in ("Rcurr", "tcurr", "resultRt", "krkinv", "kt")}
+    out["lastRGBErrorLevel"], out["rgb_broken"] = np.float32(n.lastRGBErrorLevel), int(n.rgb_broken)
+    return out, A, b, st, x
+
+
+def track_end(Rcurr, tcurr, Rprev, tprev, q_prev, t_prev, rgb, weightMultiplier):
+    """The end of tracking on caller-supplied state (efo_track_end): the results of elasticfusion_amd.api.ops.track_end_tail"""
+    o = dict(q=np.zeros(4), t=np.zeros(3), T_cw=np.zeros(16, np.float32), pose_f=np.zeros(16, np.float32), R_wc_f=np.zeros(9, np.float32),
+             t_wc_f=np.zeros(3, np.float32), weighting=np.zeros(1, np.float32), logged=np.zeros(16))
+    qp, tp = np.ascontiguousarray(q_prev, np.float64).reshape(4), np.ascontiguousarray(t_prev, np.float64).reshape(3)
+    lib().efo_track_end(ptr(f32(Rcurr).reshape(9)), ptr(f32(tcurr).reshape(3)), ptr(f32(Rprev).reshape(9)), ptr(f32(tprev).reshape(3)), ptr(qp),
+                        ptr(tp), c_i(int(rgb)), c_f(weightMultiplier), *[ptr(o[k]) for k in ("q", "t", "T_cw", "pose_f", "R_wc_f", "t_wc_f", "weighting", "logged")])
+    o["weighting"] = o["weighting"][0]
+    return o
+
+
 def resize_nearest(img, factor):
     """Resize::{image,vertex,time}: img [H, W] or [H, W, C] of any dtype -> [H // factor, W // factor(, C)]"""
     a = np.ascontiguousarray(img)

@@ -124,3 +124,35 @@ def test_wave_parallel_ldlt_equals_the_scalar_statement(tmp_path):
         got2 = np.zeros(6)
         shipped.run_ldlt6_every_lane(P(A), P(b), P(got2))     # the whole-matrix-per-lane variant (-DEF_LDLT_EVERY_LANE)
         assert np.array_equal(got2.view(np.uint64), want.view(np.uint64)), (k, got2, want)
+
+
+def test_emulated_update_step_equals_the_oracle(tmp_path):
+    """efs::gauss_newton_update_wave<false> and <true> (with its two tails) on 64 emulated lanes against the function the oracle's driver loop
+    runs (efo_gn_update), on the cases of tests/test_gpu_update_step.py whose step is evaluated (the rgbOnly break is solve_step_wave's
+    business, in front of this function), bit for bit: both sides take sin and cos from this machine's libm.  This pins the lane logic —
+    which lane assembles, solves, multiplies and publishes what; what the gfx950 compiler makes of it is the GPU test's business."""
+    import efo
+    import gn_cases
+    shipped = build_solve(str(tmp_path))
+    P = lambda a: a.ctypes.data_as(C.c_void_p)
+    shipped.run_gn_update.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float] + [C.c_void_p] * 8
+    ran = 0
+    for c in gn_cases.cases():
+        if gn_cases.takes_the_break(c):
+            continue
+        canary = (np.full(36, gn_cases.CANARY), np.full(6, gn_cases.CANARY), np.full(4, gn_cases.CANARY, np.float32))
+        args = [c[k] for k in ("sums", "prev", "Rprev", "tprev", "count", "sigma", "icp", "rgb", "rgbOnly", "icpWeight", "knext", "level_changes")]
+        want, A_w, b_w, _, x = efo.gn_update(*args, *canary)
+        assert np.all(np.isfinite(x)), c["name"]
+        for split in (0, 1):
+            got = dict(resultRt=np.zeros(16), Rcurr=np.zeros(9, np.float32), tcurr=np.zeros(3, np.float32), krkinv=np.zeros(9, np.float32), kt=np.zeros(3, np.float32))
+            A_g, b_g = np.zeros(36), np.zeros(6)
+            shipped.run_gn_update(split, P(np.ascontiguousarray(c["sums"], np.float32)), P(np.ascontiguousarray(c["prev"]["resultRt"], np.float64)),
+                                  P(np.ascontiguousarray(c["Rprev"], np.float32)), P(np.ascontiguousarray(c["tprev"], np.float32)), c["icp"], c["rgb"], c["rgbOnly"],
+                                  c["icpWeight"], P(np.array(c["knext"], np.float32)), *[P(got[k]) for k in ("resultRt", "Rcurr", "tcurr", "krkinv", "kt")], P(A_g), P(b_g))
+            for k, g in list(got.items()) + [("lastA", A_g), ("lastb", b_g)]:
+                w = {"lastA": A_w, "lastb": b_w}.get(k, want.get(k))
+                u = np.uint64 if g.dtype == np.float64 else np.uint32
+                assert np.array_equal(g.view(u), np.ascontiguousarray(w, g.dtype).view(u)), (c["name"], split, k, g, w)
+        ran += 1
+    assert ran >= 18
