@@ -97,6 +97,17 @@ def thinned_map(ef: "api.ElasticFusion", cell: float, keep: int = api.THIN_KEEP_
     return ef.gatherSurfels(ef.thinSelect(cell=float(cell), keep=int(keep), among=among, representatives=True))
 
 
+def carved_map(ef: "api.ElasticFusion", depths, poses=None, **kw) -> np.ndarray:
+    """ef's map without the surfels that the depth views see through, [k, 12] float32 as downloadMap() gives them, without a download of the
+    whole map and without changing it: carveSelect + gatherSurfels of the other rows (ef_map_carve_select + ef_map_gather), which is what
+    carveSurfels with the same arguments would leave.  depths, poses and the keywords (params, among, ef_carve_params fields) as carveSelect
+    takes them."""
+    removed = ef.carveSelect(depths, poses, **kw)
+    kept = np.ones(ef.lastCount(), bool)
+    kept[removed] = False
+    return ef.gatherSurfels(np.nonzero(kept)[0].astype(np.uint32))
+
+
 def map_accuracy(ef: "api.ElasticFusion", gt_surfels: np.ndarray, max_dist: float = 0.05, map_rows=None, gt_rows=None, device: int = 0,
                  align: bool = False, align_schedule=REGISTER_SCHEDULE) -> dict:
     """ef: a context with a map; gt_surfels: [m, 12] float32, laid out as downloadMap() gives them (synth.sample_surfels), in the map's world

@@ -117,6 +117,21 @@ class ef_thin_result(C.Structure):
     _fields_ = [("participants", c_u32), ("cells", c_u32), ("removed", c_u32), ("count_after", c_u32)]
 
 
+class ef_carve_params(C.Structure):
+    _fields_ = [("width", c_i), ("height", c_i), ("fx", c_f), ("fy", c_f), ("cx", c_f), ("cy", c_f), ("min_depth", c_f), ("max_depth", c_f),
+                ("margin", c_f), ("margin_quad", c_f), ("window", c_i), ("min_views", c_i), ("protect", c_i)]
+
+
+class ef_carve_views(C.Structure):
+    _fields_ = [("n", c_i), ("T_wc16", C.c_void_p), ("depth", C.c_void_p)]
+
+
+class ef_carve_result(C.Structure):
+    _fields_ = [("participants", c_u32), ("observed", c_u32), ("free_space", c_u32), ("protected_", c_u32), ("removed", c_u32),
+                ("count_after", c_u32)]
+
+
+CARVE_MAX_VIEWS = 32   # EF_CARVE_MAX_VIEWS of include/ef_hip.h
 THIN_KEEP_MAX_CONF, THIN_KEEP_NEWEST, THIN_KEEP_FIRST = 0, 1, 2   # EF_THIN_KEEP_* of include/ef_hip.h
 THIN_ROWS_REMOVED, THIN_ROWS_REPRESENTATIVES = 0, 1               # EF_THIN_ROWS_*
 INSERT_KEEP = -1   # EF_INSERT_KEEP of include/ef_hip.h
@@ -1293,6 +1308,72 @@ class ElasticFusion:
         res = ef_thin_result()
         _chk(lib().ef_map_thin(self.h, C.byref(params), pa, C.byref(res)), self.h)
         return {"participants": int(res.participants), "cells": int(res.cells), "removed": int(res.removed), "count_after": int(res.count_after)}
+
+    # --- carve free space: remove the surfels that depth views see through (ef_map_carve / ef_map_carve_select) ---
+    def carveParams(self, **kw) -> ef_carve_params:
+        """ef_default_carve_params (the frame camera, min_depth 0.3, max_depth = the depth cut-off, margin 0.02, margin_quad 0.0025, window 1,
+        min_views 1, protect 1) with fields replaced by keyword"""
+        return self._params(ef_carve_params, lib().ef_default_carve_params, kw, "carve")
+
+    def _carveArgs(self, depths, poses, params, among, kw):
+        """(params, views, among's pointer, what must stay alive).  depths: [K, H, W] or [H, W] uint16 millimetres, or a DevBuf holding K
+        images of the parameters' size; poses: [K, 4, 4] T_wc, or None for the current pose with K = 1"""
+        T = self.get_T_wc().reshape(1, 16) if poses is None else np.ascontiguousarray(poses, np.float64).reshape(-1, 16)
+        if params is None:
+            if not isinstance(depths, DevBuf) and "width" not in kw and "height" not in kw:
+                kw = dict(kw, width=int(np.shape(depths)[-1]), height=int(np.shape(depths)[-2]))
+            params = self.carveParams(**kw)
+        else:
+            assert not kw, "give params or keywords, not both"
+        if isinstance(depths, DevBuf):
+            assert len(T) * params.width * params.height * 2 <= depths.nbytes, (len(T), depths.nbytes)
+            keep, dp = depths, depths.p
+        else:
+            keep = np.ascontiguousarray(depths, np.uint16).reshape(-1, params.height, params.width)
+            assert len(keep) == len(T), (keep.shape, T.shape)
+            dp = _ptr(keep)
+        views = ef_carve_views(len(T), C.cast(_ptr(T), C.c_void_p), C.cast(dp, C.c_void_p))
+        if isinstance(among, dict):
+            among = self.mapSelection(**among)
+        return params, views, (C.byref(among) if among is not None else None), (T, keep, among)
+
+    def carveSelect(self, depths, poses=None, params: ef_carve_params | None = None, among=None, max_rows: int | None = None,
+                    count: bool = False, votes: bool = False, **kw):
+        """the rows a carve with these views would remove, in ascending order (uint32), at most max_rows of them (None: all); the map does
+        not change.  depths: [K, H, W] or [H, W] uint16 millimetres; poses: [K, 4, 4] T_wc or None (the current pose, K = 1); among: an
+        ef_map_selection, a dict of mapSelection keywords or None (every surfel participates); other keywords are ef_carve_params fields
+        (width and height default to the images').  count=True adds the total, votes=True the [rows of the map, 2] uint8 {free, support}:
+        rows[, total][, votes]"""
+        params, views, pa, keep = self._carveArgs(depths, poses, params, among, kw)
+        n = self.lastCount() if max_rows is None or votes else 0      # (asked only where it sizes an array)
+        cap = n if max_rows is None else int(max_rows)
+        rows = np.zeros(max(cap, 1), np.uint32)
+        v2 = np.zeros((max(n, 1), 2), np.uint8) if votes else None
+        total = c_u32(0)
+        _chk(lib().ef_map_carve_select(self.h, C.byref(params), C.byref(views), pa, _ptr(rows) if cap else None, c_u32(cap), C.byref(total),
+                                       _ptr(v2) if votes else None), self.h)
+        out = (rows[:min(cap, total.value)].copy(),) + ((total.value,) if count else ()) + ((v2[:n],) if votes else ())
+        return out if len(out) > 1 else out[0]
+
+    def carveSelectDevice(self, depths_dev, poses, params: ef_carve_params, among, rows_dev, max_rows: int, count_dev, votes_dev=None):
+        """ef_map_carve_select_dev: raw device pointers (int, c_void_p or None for rows with max_rows 0 and for votes) for the K images, rows,
+        count and votes; poses [K, 4, 4] on the host; enqueued on the context's stream"""
+        T = np.ascontiguousarray(poses, np.float64).reshape(-1, 16)
+        if isinstance(among, dict):
+            among = self.mapSelection(**among)
+        args = [None if v is None else int(v.value if isinstance(v, P) else v) for v in (depths_dev, rows_dev, count_dev, votes_dev)]
+        views = ef_carve_views(len(T), C.cast(_ptr(T), C.c_void_p), C.c_void_p(args[0]))
+        _chk(lib().ef_map_carve_select_dev(self.h, C.byref(params), C.byref(views), C.byref(among) if among is not None else None,
+                                           P(args[1]), c_u32(int(max_rows)), P(args[2]), P(args[3])), self.h)
+
+    def carveSurfels(self, depths, poses=None, params: ef_carve_params | None = None, among=None, **kw) -> dict:
+        """removes the surfels the views see through (ef_map_carve; depths a DevBuf: ef_map_carve_dev): what eraseRows(carveSelect(...))
+        leaves.  {"participants", "observed", "free_space", "protected_", "removed", "count_after"}"""
+        params, views, pa, keep = self._carveArgs(depths, poses, params, among, kw)
+        res = ef_carve_result()
+        fn = lib().ef_map_carve_dev if isinstance(depths, DevBuf) else lib().ef_map_carve
+        _chk(fn(self.h, C.byref(params), C.byref(views), pa, C.byref(res)), self.h)
+        return {k: int(getattr(res, k)) for k, _ in ef_carve_result._fields_}
 
     def setReferenceDownload(self, on=True):
         """downloadMap / savePly read what GlobalModel::downloadMap reads (the pre-clean buffer, quirk Q14) instead of model()"""

@@ -189,12 +189,14 @@ int erase_run(ef_ctx* c, const char* fn, unsigned flip, uint32_t* removed, Mark 
   return EF_OK;
 }
 // The "list of rows" host tier of ef_map_select and ef_map_thin_select: enqueue(rows_dev, max_rows, count_dev) is the _dev tier's work into the
-// staging (named `staging` in an allocation error); the count and the first min(count, max_rows) rows are copied out.
+// staging (named `staging` in an allocation error); the count and the first min(count, max_rows) rows are copied out.  `extra` bytes behind the
+// list (rows_list_extra: 16-byte aligned) are the caller's own: the staging is reserved once, for both.
+inline uint8_t* rows_list_extra(uint32_t* d_rows, uint32_t cap_rows) { return (uint8_t*)d_rows + (((size_t)cap_rows * 4 + 15) & ~(size_t)15); }
 template <typename Enqueue>
-int rows_list_host(ef_ctx* c, const char* staging, uint32_t* rows, uint32_t max_rows, uint32_t* count, Enqueue enqueue) {
+int rows_list_host(ef_ctx* c, const char* staging, uint32_t* rows, uint32_t max_rows, uint32_t* count, Enqueue enqueue, size_t extra = 0) {
   // (the list is never longer than the map: the staging is sized by the capacity at most)
   const size_t cap_rows = std::min((size_t)max_rows, (size_t)c->capacity);
-  int r = c->stage.reserve(c, 16 + cap_rows * 4, staging);
+  int r = c->stage.reserve(c, extra ? 16 + ((cap_rows * 4 + 15) & ~(size_t)15) + extra : 16 + cap_rows * 4, staging);
   if (r != EF_OK) return r;
   uint32_t* d_count = c->stage.as<uint32_t>();
   uint32_t* d_rows = (uint32_t*)(c->stage.p + 16);

@@ -347,6 +347,30 @@ struct ThinArgs {
 // one wave per bucket of the index: nothing is launched for an empty index
 void thin_flags(const ThinArgs& a, hipStream_t s);
 
+// ---- carve free space: flag the surfels that depth views see through (ef_carve.inc; ef_map_carve of include/ef_hip.h) ----
+constexpr int CARVE_MAX_VIEWS = 32;   // EF_CARVE_MAX_VIEWS
+struct CarveArgs {
+  const float4* pos_conf;   // the map's {x, y, z, conf} stream: the only map stream the carve reads
+  unsigned n;               // rows of the map: the length of the byte arrays below
+  const uint8_t* part;      // one byte per row, non-zero = the row passes the selection; null: every row does
+  const uint16_t* depth;    // n_views consecutive height x width images of millimetres (2-byte aligned, no more)
+  int n_views;
+  int width, height;
+  float fx, fy, cx, cy;
+  float min_depth, max_depth, margin, margin_quad;
+  int window, min_views, protect;
+  uint8_t* removed;         // one byte per row: 1 = removed, 0 = kept (every row is written)
+  uint8_t* votes;           // two bytes per row {free, support}; or null
+  uint32_t* tally;          // 3 x tally_stride words: per chunk of SELECT_ROW rows the participants, the observed and the free-space rows; or null
+  unsigned tally_stride;
+  float Tcw[CARVE_MAX_VIEWS][12];   // per view the rows {Rc i0, Rc i1, Rc i2, tc i} of T_cw, each entry rounded to f32 once; it travels in the
+                                    // kernel's argument segment and is read with scalar loads (uniform across the launch)
+};
+// one lane per row; nothing is launched for an empty map
+void carve_flags(const CarveArgs& a, hipStream_t s);
+// offsets and *total of per-chunk counts that a kernel has already written into sc.chunk_count (the scan select_flags and flags_count end with)
+void chunk_totals(const SelectScratch& sc, unsigned n, uint32_t* total, hipStream_t s);
+
 // ---- fuse surfels into the map (ef_fuse.inc; ef_map_fuse of include/ef_hip.h) ----
 constexpr unsigned long long FUSE_KEY_EMPTY = 0xFFFFFFFFFFFFFFFFull;
 constexpr unsigned FUSE_SKIPPED = 0, FUSE_NOVEL = 1, FUSE_WEIGHTLESS = 2, FUSE_ABSORBED = 3, FUSE_FUSED = 4, FUSE_INSERTED = 5;   // EF_FUSE_*

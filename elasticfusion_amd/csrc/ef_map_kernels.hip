@@ -1520,6 +1520,7 @@ void sample_graph(SurfelSoA map, const unsigned* count_dev, int stride, int max_
 #include "ef_select.inc"
 #include "ef_insert.inc"
 #include "ef_thin.inc"
+#include "ef_carve.inc"
 #include "ef_fuse.inc"
 
 }  // namespace efm

@@ -902,6 +902,94 @@ int ef_map_thin_select_dev(ef_ctx* ctx, const ef_thin_params* params, const ef_m
                            uint32_t max_rows, uint32_t* count_dev);
 int ef_map_thin(ef_ctx* ctx, const ef_thin_params* params, const ef_map_selection* among_or_null, ef_thin_result* result);
 
+/* ---- Carve free space: remove the surfels that depth views see through (the free-space violation test of surfel and TSDF mapping).  A frame's
+ * clean drops only unstable surfels; a surfel that became stable stays although the thing it stood for has moved.  Off until first used: no
+ * carve call, nothing allocated, nothing run, and no frame kernel knows of it.
+ *
+ * "Row" and the layout of a surfel are those of the section "Select, extract and erase surfels": position (X, Y, Z) = floats 0 .. 2.  All per-row
+ * arithmetic is f32, one rounding per operation, no contraction, in the written order.  Comparisons with NaN are false.  The outcome of a row is
+ * a pure function of that row, the views and the parameters: it depends on no other row, on no order of evaluation and on no sum.
+ *
+ * VIEWS.  n views, 1 <= n <= EF_CARVE_MAX_VIEWS.  View k has T_wc = T_wc16[16 k .. 16 k + 15] (world <- camera, row-major 4 x 4 double like every
+ * other pose here, rigid) and the image depth[k * height * width ..]: height x width uint16 millimetres, row-major, what ef_process_frame takes.
+ * All views share one camera (width, height, fx, fy, cx, cy of the parameters).  The host forms T_cw per view in double, in this order, and then
+ * rounds each of the twelve entries to f32 once: with t = (T_wc[0][3], T_wc[1][3], T_wc[2][3]),
+ *   Rc[i][j] = T_wc[j][i],     tc[i] = -((T_wc[0][i]*t[0] + T_wc[1][i]*t[1]) + T_wc[2][i]*t[2])
+ * (the transpose and its product with t: no quaternion, no normalisation; a T_wc that is not rigid gives what the expressions give).
+ *
+ * PER ROW AND VIEW.  The camera-frame point, with the box test's expression:
+ *   x = ((Rc00*X + Rc01*Y) + Rc02*Z) + tcx,   y = ((Rc10*X + Rc11*Y) + Rc12*Z) + tcy,   z = ((Rc20*X + Rc21*Y) + Rc22*Z) + tcz.
+ * The view SAYS NOTHING about the row in each of these cases:
+ *   - z > 0 does not hold;
+ *   - with uf = (fx*x)/z + cx and vf = (fy*y)/z + cy, not (uf >= 0 && uf < (float)width && vf >= 0 && vf < (float)height): compared as floats
+ *     BEFORE any conversion, so that NaN, +-infinity and values beyond the int range fall out here (and uf = -0.5 does: no truncation to 0);
+ *   - with u = (int)uf, v = (int)vf, the centre texel (u, v) has no data.
+ * A texel d HAS DATA iff d != 0 and, with zo = (float)d / 1000.0f, min_depth <= zo && zo <= max_depth.  The WINDOW is the texels (u + a, v + b)
+ * with |a| <= window and |b| <= window that lie inside the image and have data; for each of them tol = margin + (margin_quad*zo)*zo.  Then
+ *   FREE       iff (z + tol) < zo holds for EVERY texel of the window, the centre included: the view measured a surface behind the surfel along
+ *              every ray near it, so the ray through the surfel crossed the place where it claims a surface;
+ *   SUPPORTED  iff at the centre texel neither (z + tol) < zo nor (zo + tol) < z holds: the view measured the surfel's own surface;
+ *   otherwise the view says nothing: the surfel is occluded (something nearer was measured), or a depth edge runs through the window.
+ * A view is never both.  Texels outside the image or without data are ignored, so at a border or beside a hole the window is smaller.
+ *
+ * PER ROW.  A row PARTICIPATES iff it is SELECTED by among (the predicate of ef_map_select, unchanged, EF_SEL_INVERT included; among NULL:
+ * every row is) and its three position floats are finite.  free = the number of FREE views, support = the number of SUPPORTED views.  The row is
+ * REMOVED iff it participates, free >= min_views, and not (protect != 0 and support > 0).  Every other row is kept: occluded, outside every
+ * image, on a depth hole, not a participant.
+ *
+ * OUTPUTS.  votes2 (optional), 2 bytes per row of the map: {free, support}; {0, 0} for a row that does not participate.  ef_carve_result:
+ * participants; observed = the participants with free + support > 0; free_space = those with free >= min_views; protected_ = the free_space rows
+ * that support kept (free_space - removed); removed; count_after = the map count the call leaves.
+ *
+ * ef_map_carve_select changes nothing.  It writes the REMOVED rows with ef_map_select's conventions: the first min(max_rows, total) of them in
+ * ASCENDING order, *count = total however small max_rows is, rows may be NULL with max_rows 0, entries past min(max_rows, total) are left as they
+ * were.  The list is what ef_map_erase_rows takes.  The host variant stages the images and synchronises.  ef_map_carve_select_dev takes DEVICE
+ * pointers for depth, rows, count and votes2 (T_wc16 stays a HOST pointer: it is read before the call returns) and only enqueues on the context's
+ * stream, except for what the selection needs (ID numbering, label alignment, the count after a call that can change the map).
+ *
+ * ef_map_carve removes the removed rows and leaves everything exactly as ef_map_erase_rows(the list of ef_map_carve_select) would: see "What an
+ * erase leaves behind" above (the map, the context, the index, IDs, labels, the shadow buffer), with the same two synchronisations.  Removing
+ * nothing is valid.  ef_map_carve_dev takes a DEVICE pointer for depth; result is HOST memory in both.
+ *
+ * Defaults (ef_default_carve_params): the frame camera; min_depth 0.3 m; max_depth = the context's depth cut-off (ef_set_depth_cutoff); margin
+ * 0.02 m, margin_quad 0.0025 / m (tol = 2 cm at the camera, 3 cm at 2 m, 4.25 cm at 3 m); window 1, min_views 1, protect 1.  The two margins are a
+ * CHOICE, not a measurement: the quadratic term follows the way a structured-light sensor's depth noise grows with range, and nobody has fitted
+ * either number to a sensor.  Give your own.
+ *
+ * EF_EINVAL, before any GPU work (the arguments are checked before the context, so with a NULL context ef_last_error(NULL) names what is wrong
+ * with them): a NULL context, params, views, result or count; n outside 1 .. EF_CARVE_MAX_VIEWS; a NULL T_wc16 or depth; a non-finite pose entry;
+ * width or height outside 1 .. 4096; non-finite intrinsics; a NaN or negative margin or margin_quad; a NaN min_depth or max_depth, or min_depth >
+ * max_depth; window outside 0 .. 2; min_views outside 1 .. n; max_rows > 0 with NULL rows; with among given, everything
+ * ef_map_select refuses for a selection.
+ * EF_ESTATE: the context's stream is being captured; with among given, what ef_map_select answers with EF_ESTATE.  ef_map_carve[_dev] only: a
+ * context created with close_loops = 1 (the erase's reason; the map is unchanged); the select variants work on such contexts. */
+#define EF_CARVE_MAX_VIEWS 32
+typedef struct ef_carve_params {
+  int   width, height;          /* of every depth image */
+  float fx, fy, cx, cy;         /* the camera all views share */
+  float min_depth, max_depth;   /* metres: a texel outside has no data */
+  float margin, margin_quad;    /* tol = margin + (margin_quad*zo)*zo */
+  int   window;                 /* 0 .. 2: the (2 window + 1)^2 texels around the centre */
+  int   min_views;              /* 1 .. n: FREE views a removed row needs */
+  int   protect;                /* 1: one SUPPORTED view keeps the row */
+} ef_carve_params;
+typedef struct ef_carve_views {
+  int n;                        /* 1 .. EF_CARVE_MAX_VIEWS */
+  const double* T_wc16;         /* n x 16, HOST memory in every variant */
+  const uint16_t* depth;        /* n consecutive height x width images */
+} ef_carve_views;
+typedef struct ef_carve_result { uint32_t participants, observed, free_space, protected_, removed, count_after; } ef_carve_result;
+int ef_default_carve_params(ef_ctx* ctx, ef_carve_params* params);
+int ef_map_carve_select(ef_ctx* ctx, const ef_carve_params* params, const ef_carve_views* views, const ef_map_selection* among_or_null,
+                        uint32_t* rows, uint32_t max_rows, uint32_t* count, uint8_t* votes2_or_null);
+int ef_map_carve_select_dev(ef_ctx* ctx, const ef_carve_params* params, const ef_carve_views* views_depth_dev,
+                            const ef_map_selection* among_or_null, uint32_t* rows_dev, uint32_t max_rows, uint32_t* count_dev,
+                            uint8_t* votes2_dev_or_null);
+int ef_map_carve(ef_ctx* ctx, const ef_carve_params* params, const ef_carve_views* views, const ef_map_selection* among_or_null,
+                 ef_carve_result* result);
+int ef_map_carve_dev(ef_ctx* ctx, const ef_carve_params* params, const ef_carve_views* views_depth_dev, const ef_map_selection* among_or_null,
+                     ef_carve_result* result);
+
 /* named internal images, copied to HOST (synchronises); for tests and for a front-end's drawing code */
 enum ef_image {
   EF_IMG_DEPTH_FILTERED = 0,      /* u16  */
