@@ -744,7 +744,8 @@ bool finite16(const double* T) {
 int ids_prepare(ef_ctx* c, const char* fn) {
   if (c->labels.ids_bad) {
     c->err = std::string(fn) + ": the uploaded map's ID lane (float 5 of each surfel) is not a strictly increasing non-zero prefix followed by "
-             "a zero suffix";
+             "a zero suffix, or numbering that suffix above its largest ID and above every ID handed out so far would pass 0xFFFFFFFE: the "
+             "numbering would wrap";
     return EF_ESTATE;
   }
   efm::ids_assign(c->maps[c->cur], &c->st->map_counts[c->cur], c->labels.ids_state, c->stream);
@@ -752,10 +753,11 @@ int ids_prepare(ef_ctx* c, const char* fn) {
   return EF_OK;
 }
 // ef_map_upload with IDs on: the uploaded lane is kept when its shape is valid (the counter then continues above its largest ID, ids_assign);
-// any other shape is remembered and refused by the next ID-consuming call.  Labels restart from the prior.
+// any other shape, and a lane whose zero suffix cannot be numbered from there without leaving uint32 (the numbering would wrap to 0 or below the
+// prefix), is remembered and refused by the next ID-consuming call.  Labels restart from the prior.
 int ids_uploaded(ef_ctx* c, uint32_t count) {
   EF_HIP(c, hipMemsetAsync(c->labels.ids_state + 1, 0, sizeof(unsigned), c->stream));
-  efm::ids_check(c->maps[c->cur], count, c->labels.ids_state + 1, c->stream);
+  efm::ids_check(c->maps[c->cur], count, c->labels.ids_state, c->labels.ids_state + 1, c->stream);
   EF_HIP(c, hipGetLastError());
   unsigned flag = 0;
   EF_HIP(c, hipMemcpyAsync(&flag, c->labels.ids_state + 1, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));

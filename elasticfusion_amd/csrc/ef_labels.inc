@@ -50,15 +50,24 @@ __global__ void __launch_bounds__(1024) k_ids_assign(SurfelSoA map, const unsign
   for (unsigned i = start + threadIdx.x; i < n; i += blockDim.x) lane[(size_t)i * 4] = base + (i - start);
 }
 
-// the whole lane's shape after an upload: *flag |= 1 unless it is a strictly increasing non-zero prefix followed by a zero suffix
-__global__ void k_ids_check(SurfelSoA map, unsigned n, unsigned* flag) {
+// the whole lane after an upload: *flag |= 1 unless it is a strictly increasing non-zero prefix followed by a zero suffix, |= 2 when
+// k_ids_assign's numbering of that suffix, from max(*counter, largest ID + 1), would not stay below 0xFFFFFFFF with the counter it leaves
+// (past it the numbering wraps: an ID of 0, or IDs below the prefix)
+__global__ void k_ids_check(SurfelSoA map, unsigned n, const unsigned* __restrict__ counter, unsigned* flag) {
   const unsigned* lane = id_lane(map);
-  bool bad = false;
-  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i + 1 < n; i += gridDim.x * blockDim.x) {
-    const unsigned a = lane[(size_t)i * 4], b = lane[(size_t)(i + 1) * 4];
-    bad |= b != 0u && (a == 0u || b <= a);
+  unsigned bad = 0u;
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const unsigned a = lane[(size_t)i * 4], b = i + 1 < n ? lane[(size_t)(i + 1) * 4] : 0u;
+    if (b != 0u && (a == 0u || b <= a)) bad |= 1u;
+    // the row the numbering starts behind: the last of the prefix, or (an all-zero lane, seen from row 0) none
+    if (b == 0u && (a != 0u || i == 0u)) {
+      const unsigned long long next = *counter;
+      const unsigned long long base = a != 0u ? max(next, a + 1ull) : next;
+      const unsigned suffix = a != 0u ? n - 1u - i : n;
+      if (base + suffix > 0xFFFFFFFFull) bad |= 2u;
+    }
   }
-  if (bad) atomicOr(flag, 1u);
+  if (bad) atomicOr(flag, bad);
 }
 
 __global__ void k_ids_zero(SurfelSoA map, const unsigned* __restrict__ count_dev) {
@@ -174,8 +183,8 @@ __global__ void __launch_bounds__(BLK) k_labels_gather(const uint32_t* __restric
 void ids_assign(SurfelSoA map, const unsigned* count_dev, unsigned* state, hipStream_t s) {
   hipLaunchKernelGGL(k_ids_assign, dim3(1), dim3(1024), 0, s, map, count_dev, state);
 }
-void ids_check(SurfelSoA map, unsigned n, unsigned* flag, hipStream_t s) {
-  if (n > 1) hipLaunchKernelGGL(k_ids_check, dim3(min(ceil_div((int)n, BLK), 4096)), dim3(BLK), 0, s, map, n, flag);
+void ids_check(SurfelSoA map, unsigned n, const unsigned* counter, unsigned* flag, hipStream_t s) {
+  if (n) hipLaunchKernelGGL(k_ids_check, dim3(min(ceil_div((int)n, BLK), 4096)), dim3(BLK), 0, s, map, n, counter, flag);
 }
 void ids_zero(SurfelSoA map, const unsigned* count_dev, unsigned max_rows, hipStream_t s) {
   hipLaunchKernelGGL(k_ids_zero, dim3(max(1, min(ceil_div((int)max_rows, BLK), 4096))), dim3(BLK), 0, s, map, count_dev);

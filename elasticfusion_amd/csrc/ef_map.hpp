@@ -197,8 +197,9 @@ void render_model(const RenderArgs& a, SurfelSoA map, const unsigned* count_dev,
 // ---- stable surfel IDs and label fusion (ef_labels.inc; ef_set_surfel_ids / ef_enable_labels of include/ef_hip.h) ----
 // state[0]: the next ID to hand out.  One workgroup numbers the zero suffix of the ID lane (col_time.y as uint32).
 void ids_assign(SurfelSoA map, const unsigned* count_dev, unsigned* state, hipStream_t s);
-// *flag |= 1 unless the lane of rows [0, n) is a strictly increasing non-zero prefix followed by a zero suffix
-void ids_check(SurfelSoA map, unsigned n, unsigned* flag, hipStream_t s);
+// *flag |= 1 unless the lane of rows [0, n) is a strictly increasing non-zero prefix followed by a zero suffix, |= 2 when numbering that suffix
+// from max(*counter, largest ID + 1) would not stay below 0xFFFFFFFF (counter = state of ids_assign)
+void ids_check(SurfelSoA map, unsigned n, const unsigned* counter, unsigned* flag, hipStream_t s);
 // max_rows: an upper bound of *count_dev (sizes the grid only)
 void ids_zero(SurfelSoA map, const unsigned* count_dev, unsigned max_rows, hipStream_t s);
 void ids_gather(SurfelSoA map, unsigned n, uint32_t* out, hipStream_t s);

@@ -416,8 +416,12 @@ int ef_render_model_dev(ef_ctx* ctx, const ef_render_params* params, uint8_t* rg
  * created since the last one.  Switching on numbers the current map (1 .. N the first time); switching off zeroes the lane, so a download equals
  * that of a context that never had IDs, and switches labels off.  ef_map_upload while IDs are on keeps the uploaded lane when it is a strictly
  * increasing non-zero prefix followed by a zero suffix (a map downloaded with IDs; an all-zero lane, numbered by the next call); the counter
- * continues above its largest ID.  Any other lane makes every later ID-consuming call fail with EF_ESTATE until the next valid upload or
- * switch-on.  With ef_set_reference_download on, the downloaded buffer is the pre-clean copy (quirk Q14) and its lane is whatever that buffer
+ * continues above its largest ID.  The zero suffix of an upload, z rows, is numbered from b = max(one past the largest ID of the prefix, one
+ * past every ID the context has handed out); the upload is valid only if b + z <= 0xFFFFFFFF, so that the numbering ends at 0xFFFFFFFE at
+ * the latest and cannot wrap (an uploaded ID of 0xFFFFFFFF is therefore never valid).  Any other lane, a lane of one row included, makes
+ * every later ID-consuming call fail with EF_ESTATE until the next valid upload or switch-on.  A counter that the creation of surfels drives
+ * past 2^32 - 1 (four billion surfels created in one context, or fewer on top of uploaded IDs that close to the end) is outside the contract
+ * and is not detected.  With ef_set_reference_download on, the downloaded buffer is the pre-clean copy (quirk Q14) and its lane is whatever that buffer
  * holds: IDs as of the last frame's update pass, zero for surfels created after it.
  *
  * Labels: a float32 table [rows][C] in map row order on the device.  Every label call first re-aligns it to the current rows: a row whose ID was
@@ -450,7 +454,10 @@ int ef_fuse_labels(ef_ctx* ctx, const ef_render_params* view_or_null, const floa
 /* the same with a DEVICE image, enqueued on the context's stream */
 int ef_fuse_labels_dev(ef_ctx* ctx, const ef_render_params* view_or_null, const float* probs_chw_dev);
 /* per pixel of the view's index image: label = argmax of the surfel's row (ties to the lowest class), prob = that maximum; -1 and 0 where
- * nothing is drawn.  width x height each, row-major, HOST pointers (either may be NULL); synchronises. */
+ * nothing is drawn.  The argmax is the FIRST STRICT MAXIMUM starting from class 0: best = 0, m = p[0]; for c = 1 .. C-1 in ascending order, if
+ * p[c] > m then best = c, m = p[c].  Comparisons with NaN are false, so a NaN at a later class is passed over, and a NaN at class 0 is never
+ * replaced: such a row gives label 0 and prob NaN (an all-NaN row too).  width x height each, row-major, HOST pointers (either may be NULL);
+ * synchronises. */
 int ef_render_labels(ef_ctx* ctx, const ef_render_params* params, int32_t* label, float* prob);
 /* the same with DEVICE pointers, enqueued on the context's stream */
 int ef_render_labels_dev(ef_ctx* ctx, const ef_render_params* params, int32_t* label_dev, float* prob_dev);
