@@ -53,6 +53,13 @@ class ef_gn_update_args(C.Structure):
                 ("split_tail", c_i)]
 
 
+class ef_model_maps_op(C.Structure):   # ef_op_model_maps
+    _fields_ = [("cols", c_i), ("rows", c_i), ("pred_vertex", P), ("pred_normal", P), ("fill_vertex", P), ("fill_normal", P), ("pred_image", P),
+                ("fill_image", P), ("R", c_f * 9), ("t", c_f * 3), ("max_depth_rgb", c_f), ("camera_frame", c_i), ("force_fill_image", c_i),
+                ("tally", c_i), ("dense_count", C.c_uint), ("dense_samples", c_i), ("vmap", P * 3), ("nmap", P * 3), ("depth0", P), ("last0", P),
+                ("joint", c_i), ("raw", P), ("rgb3", P), ("depth_cut", c_f), ("filtered", P), ("metric", P), ("metric_filtered", P), ("next0", P)]
+
+
 class ef_track_end_out(C.Structure):
     _fields_ = [("q", C.c_double * 4), ("t", C.c_double * 3), ("logged", C.c_double * 16), ("T_cw", c_f * 16), ("pose_f", c_f * 16),
                 ("R_wc_f", c_f * 9), ("t_wc_f", c_f * 3), ("weighting", c_f)]
@@ -635,7 +642,8 @@ class ElasticFusion:
     TRACKER = dict(vmap_curr=(0, np.float32, 3), nmap_curr=(1, np.float32, 3), vmap_g_prev=(2, np.float32, 3),
                    nmap_g_prev=(3, np.float32, 3), lastDepth=(4, np.float32, 1), nextDepth=(5, np.float32, 1),
                    lastImage=(6, np.uint8, 1), nextImage=(7, np.uint8, 1), lastNextImage=(8, np.uint8, 1),
-                   dIdx=(9, np.int16, 1), dIdy=(10, np.int16, 1), depth_tmp=(11, np.uint16, 1))
+                   dIdx=(9, np.int16, 1), dIdy=(10, np.int16, 1), depth_tmp=(11, np.uint16, 1), rgbMask=(12, np.uint8, 1),
+                   corres=(13, np.uint32, 1))
 
     def __init__(self, width=640, height=480, fx=528.0, fy=528.0, cx=320.0, cy=240.0, timeDelta=2147483647 // 2,
                  confidence=10.0, depthCut=3.0, icpThresh=10.0, fastOdom=False, so3=True, frameToFrameRGB=False,
@@ -1429,11 +1437,12 @@ class ElasticFusion:
         _chk(lib().ef_get_image(self.h, c_i(which), _ptr(out), C.c_size_t(out.nbytes)), self.h)
         return out
 
-    def trackerBuffer(self, name: str, level: int = 0) -> np.ndarray:
+    def trackerBuffer(self, name: str, level: int = 0, tracker: int = 0) -> np.ndarray:
+        """tracker: 0 = frameToModel, 1 = modelToModel (closeLoops contexts only)"""
         which, dt, planes = self.TRACKER[name]
         w, h = self.cfg.width >> level, self.cfg.height >> level
         out = np.zeros((h * planes, w), dt)
-        _chk(lib().ef_get_tracker_buffer(self.h, c_i(which), c_i(level), _ptr(out), C.c_size_t(out.nbytes)), self.h)
+        _chk(lib().ef_get_tracker_buffer_of(self.h, c_i(tracker), c_i(which), c_i(level), _ptr(out), C.c_size_t(out.nbytes)), self.h)
         return out
 
     def enableTiming(self, on=True):
@@ -1585,6 +1594,68 @@ class ops:
         _chk(lib().ef_op_so3_step(li.p, ni.p, _ptr(ops._f32(imageBasis).reshape(9)), _ptr(ops._f32(kinv).reshape(9)),
                                   _ptr(ops._f32(krlr).reshape(9)), c_i(w), c_i(h), _ptr(A), _ptr(b), _ptr(res), None))
         return A, b, res
+
+    @staticmethod
+    def model_maps(pred_vertex, pred_normal, fill_vertex, fill_normal, R, t, maxDepthRGB=6.0, pred_image=None, fill_image=None, camera_frame=False,
+                   force_fill_image=False, tally=False, dense_count=0, dense_samples=1, joint=False, raw=None, rgb=None, depth_cut=3.0, init=None):
+        """The tracker's model-side input launch on caller-supplied maps (ef_op_model_maps): k_model_maps, or -- joint -- k_frame_inputs with the
+        pre-processing of (raw, rgb) in the same grid.  init: dict name -> contents an output starts from (vmap0..2, nmap0..2, depth0, last0,
+        and the joint outputs; zeros otherwise).  Returns a dict of arrays with those names plus dense_count."""
+        h, w, _ = pred_vertex.shape
+        init = init or {}
+        keep = [DevBuf.from_array(ops._f32(a)) for a in (pred_vertex, pred_normal, fill_vertex, fill_normal)]
+        a = ef_model_maps_op()
+        a.cols, a.rows = w, h
+        a.pred_vertex, a.pred_normal, a.fill_vertex, a.fill_normal = (b.p for b in keep)
+        if pred_image is not None:
+            imgs = [DevBuf.from_array(np.ascontiguousarray(i, np.uint8)) for i in (pred_image, fill_image)]
+            keep += imgs
+            a.pred_image, a.fill_image = imgs[0].p, imgs[1].p
+        a.R[:] = [float(v) for v in ops._f32(R).reshape(9)]
+        a.t[:] = [float(v) for v in ops._f32(t).reshape(3)]
+        a.max_depth_rgb = float(maxDepthRGB)
+        a.camera_frame, a.force_fill_image, a.tally = int(camera_frame), int(force_fill_image), int(tally)
+        a.dense_count, a.dense_samples = int(dense_count), int(dense_samples)
+        spec = {}
+        for l in range(3):
+            spec[f"vmap{l}"] = spec[f"nmap{l}"] = (np.float32, (3 * (h >> l), w >> l))
+        spec["depth0"], spec["last0"] = (np.float32, (h, w)), (np.uint8, (h, w))
+        if joint:
+            spec.update(filtered=(np.uint16, (h, w)), metric=(np.float32, (h, w)), metric_filtered=(np.float32, (h, w)), next0=(np.uint8, (h, w)))
+        out = {}
+        for name, (dt, shp) in spec.items():
+            start = np.zeros(shp, dt) if name not in init else np.ascontiguousarray(init[name], dt)
+            assert start.shape == shp, (name, start.shape, shp)
+            out[name] = DevBuf.from_array(start)
+        for l in range(3):
+            a.vmap[l], a.nmap[l] = out[f"vmap{l}"].p, out[f"nmap{l}"].p
+        a.depth0, a.last0 = out["depth0"].p, out["last0"].p
+        if joint:
+            fr = [DevBuf.from_array(np.ascontiguousarray(raw, np.uint16)), DevBuf.from_array(np.ascontiguousarray(rgb, np.uint8))]
+            assert raw.shape == (h, w) and rgb.shape == (h, w, 3)
+            keep += fr
+            a.joint, a.raw, a.rgb3, a.depth_cut = 1, fr[0].p, fr[1].p, float(depth_cut)
+            a.filtered, a.metric, a.metric_filtered, a.next0 = (out[n].p for n in ("filtered", "metric", "metric_filtered", "next0"))
+        left = C.c_uint(0)
+        _chk(lib().ef_op_model_maps(C.byref(a), C.byref(left), None))
+        res = {name: out[name].to_array(*spec[name]) for name in spec}
+        res["dense_count"] = int(left.value)
+        return res
+
+    @staticmethod
+    def sobel_mask(nextImage, nextDepth):
+        """k_sobel_levels on a caller's pyramids (ef_op_sobel_mask): nextImage / nextDepth are lists of three levels; returns four lists
+        (dIdx, dIdy, mask, corres) of three arrays each."""
+        h, w = nextImage[0].shape
+        img = [DevBuf.from_array(np.ascontiguousarray(a, np.uint8)) for a in nextImage]
+        dep = [DevBuf.from_array(ops._f32(a)) for a in nextDepth]
+        for l in range(3):
+            assert nextImage[l].shape == nextDepth[l].shape == (h >> l, w >> l), (l, nextImage[l].shape, nextDepth[l].shape)
+        # (outputs start from a pattern no result can be mistaken for: 0xA5 bytes)
+        outs = [[DevBuf((h >> l) * (w >> l) * sz, fill=0xA5) for l in range(3)] for sz in (2, 2, 1, 4)]
+        arr = lambda bufs: (P * 3)(*[b.p for b in bufs])
+        _chk(lib().ef_op_sobel_mask(arr(img), arr(dep), c_i(w), c_i(h), arr(outs[0]), arr(outs[1]), arr(outs[2]), arr(outs[3]), None))
+        return tuple([b.to_array(dt, (h >> l, w >> l)) for l, b in enumerate(bufs)] for bufs, dt in zip(outs, (np.int16, np.int16, np.uint8, np.uint32)))
 
     @staticmethod
     def clean_deform(cam, T_wc, time, idx, vc, ct, nr, confThreshold, timeDelta, maxDepth, surfels, newUnstable, graph, depth, isFern=0):

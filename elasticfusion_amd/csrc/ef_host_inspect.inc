@@ -330,25 +330,30 @@ int ef_get_image_resized(ef_ctx* c, int which, int factor, void* dst, size_t byt
   EF_HIP(c, e);
   return EF_OK;
 }
-int ef_get_tracker_buffer(ef_ctx* c, int which, int level, void* dst, size_t bytes) {
-  if (!c || !dst || level < 0 || level >= eft::NUM_PYRS) return EF_EINVAL;
+int ef_get_tracker_buffer(ef_ctx* c, int which, int level, void* dst, size_t bytes) { return ef_get_tracker_buffer_of(c, 0, which, level, dst, bytes); }
+int ef_get_tracker_buffer_of(ef_ctx* c, int tracker, int which, int level, void* dst, size_t bytes) {
+  if (!c || !dst || level < 0 || level >= eft::NUM_PYRS || tracker < 0 || tracker > 1) return EF_EINVAL;
   DeviceGuard dg_(c);
   const size_t n = (size_t)(c->cam.cols >> level) * (c->cam.rows >> level);
   const void* src = nullptr;
   size_t need = 0;
-  const eft::Pyramid& p = c->pyr;
+  const eft::Pyramid& p = tracker == 0 ? c->pyr : c->pyr2;
+  if (!p.partials) { c->err = "ef_get_tracker_buffer_of: the model-to-model tracker only exists in a close_loops context"; return EF_ESTATE; }
   switch (which) {
     case 0: src = p.vmap_curr[level]; need = n * 12; break;
     case 1: src = p.nmap_curr[level]; need = n * 12; break;
     case 2: src = p.vmap_g_prev[level]; need = n * 12; break;
     case 3: src = p.nmap_g_prev[level]; need = n * 12; break;
-    case 4: case 5: src = p.lastDepth[level]; need = n * 4; break;
+    case 4: src = p.lastDepth[level]; need = n * 4; break;
+    case 5: src = p.nextDepth[level]; need = n * 4; break;   // (tracker 0: the same buffers as lastDepth, quirk Q1)
     case 6: src = p.lastImage[level]; need = n; break;
     case 7: src = p.nextImage[level]; need = n; break;
     case 8: src = p.lastNextImage[level]; need = n; break;
     case 9: src = p.dIdx[level]; need = n * 2; break;
     case 10: src = p.dIdy[level]; need = n * 2; break;
-    case 11: src = level == 0 ? c->img.depth_filtered : p.depth_tmp[level]; need = n * 2; break;
+    case 11: src = (level == 0 && tracker == 0) ? c->img.depth_filtered : p.depth_tmp[level]; need = n * 2; break;
+    case 12: src = p.rgbMask[level]; need = n; break;
+    case 13: src = p.corres[level]; need = n * 4; break;
     default: c->err = "ef_get_tracker_buffer: unknown buffer"; return EF_EINVAL;
   }
   if (bytes < need) { c->err = "ef_get_tracker_buffer: destination too small"; return EF_EINVAL; }

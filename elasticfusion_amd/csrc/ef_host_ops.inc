@@ -190,6 +190,50 @@ int ef_op_so3_step(const uint8_t* lastImage, const uint8_t* nextImage, const flo
   return EF_OK;
 }
 
+// ---- operator tier: the frame tier's fused input launches on caller-owned buffers ----
+int ef_op_model_maps(const ef_model_maps_op* a, unsigned* dense_count_left, void* s) {
+  if (!a || !dense_count_left || a->cols <= 0 || a->rows <= 0 || a->cols > 2048 || a->rows > 2048 || (a->cols & 3) || (a->rows & 3)) return EF_EINVAL;
+  if (!a->pred_vertex || !a->pred_normal || !a->fill_vertex || !a->fill_normal || !a->depth0) return EF_EINVAL;
+  if ((a->pred_image == nullptr) != (a->fill_image == nullptr) || (a->pred_image && !a->last0)) return EF_EINVAL;
+  for (int i = 0; i < eft::NUM_PYRS; ++i)
+    if (!a->vmap[i] || !a->nmap[i]) return EF_EINVAL;
+  if (a->joint && (!a->raw || !a->rgb3 || !a->filtered || !a->metric || !a->metric_filtered || !a->next0)) return EF_EINVAL;
+  eft::ModelMapsOp o{};
+  o.cols = a->cols; o.rows = a->rows;
+  o.pred_vertex = a->pred_vertex; o.pred_normal = a->pred_normal; o.fill_vertex = a->fill_vertex; o.fill_normal = a->fill_normal;
+  o.pred_image = a->pred_image; o.fill_image = a->fill_image;
+  memcpy(o.R, a->R, 36); memcpy(o.t, a->t, 12);
+  o.maxDepthRGB = a->max_depth_rgb;
+  o.camera_frame = a->camera_frame != 0; o.force_fill_image = a->force_fill_image != 0; o.tally = a->tally != 0;
+  o.dense_count = a->dense_count; o.dense_samples = a->dense_samples;
+  for (int i = 0; i < eft::NUM_PYRS; ++i) { o.vmap[i] = a->vmap[i]; o.nmap[i] = a->nmap[i]; }
+  o.depth0 = a->depth0; o.last0 = a->last0;
+  eft::FramePreprocess fp{};
+  if (a->joint) {
+    fp = eft::FramePreprocess{a->raw, a->depth_cut, efm::bilateral_table(), a->filtered, a->metric, a->metric_filtered, a->rgb3, nullptr};
+    if (!fp.table) { g_create_error = "bilateral weight table missing on this device"; return EF_EHIP; }
+    o.with = &fp; o.next0 = a->next0;
+  }
+  const hipError_t e = (hipError_t)eft::model_maps_op(o, dense_count_left, (hipStream_t)s);
+  if (e != hipSuccess) { g_create_error = hipGetErrorString(e); return e == hipErrorOutOfMemory ? EF_ENOMEM : EF_EHIP; }
+  return EF_OK;
+}
+int ef_op_sobel_mask(const uint8_t* const* nextImage, const float* const* nextDepth, int cols, int rows, int16_t* const* dIdx, int16_t* const* dIdy,
+                     uint8_t* const* mask, uint32_t* const* corres, void* s) {
+  if (!nextImage || !nextDepth || !dIdx || !dIdy || !mask || !corres || cols <= 0 || rows <= 0 || cols > 2048 || rows > 2048) return EF_EINVAL;
+  eft::SobelMaskOp o{};
+  o.cols = cols; o.rows = rows;
+  for (int i = 0; i < eft::NUM_PYRS; ++i) {
+    if (!nextImage[i] || !nextDepth[i] || !dIdx[i] || !dIdy[i] || !mask[i] || !corres[i]) return EF_EINVAL;
+    o.nextImage[i] = nextImage[i]; o.nextDepth[i] = nextDepth[i]; o.dIdx[i] = dIdx[i]; o.dIdy[i] = dIdy[i]; o.mask[i] = mask[i]; o.corres[i] = corres[i];
+  }
+  eft::sobel_mask_op(o, (hipStream_t)s);
+  const hipError_t le = hipGetLastError();   // (a launch that failed: reported as such, not as whatever the synchronise returns)
+  if (le != hipSuccess) { g_create_error = hipGetErrorString(le); return EF_EHIP; }
+  OP_SYNC(s);
+  return EF_OK;
+}
+
 // ---- operator tier: the driver's small linear algebra, evaluated on the device ----
 }  // extern "C"
 namespace {

@@ -269,6 +269,36 @@ void init_rgb_sobel(const Pyramid& p, hipStream_t s);
 void init_model_pair(const Pyramid& p, const float* model_vertex4, const float* model_normal4, const uint8_t* model_image_rgba,
                      const float* cur_vertex4, const float* cur_normal4, const uint8_t* cur_image_rgba, const TrackState* st, float maxDepthRGB,
                      hipStream_t s);
+// The two most heavily fused input launches on caller-owned device buffers (ef_op_model_maps / ef_op_sobel_mask): the launch code is the frame
+// tier's own (init_icp_model's and init_rgb_sobel's), only the buffers and the settings are the caller's.
+struct ModelMapsOp {
+  int cols, rows;                        // multiples of 4
+  const float *pred_vertex, *pred_normal, *fill_vertex, *fill_normal;   // float4 maps
+  const uint8_t *pred_image, *fill_image;                               // rgba, or both null (no last0 then)
+  float R[9], t[3], maxDepthRGB;
+  bool camera_frame, force_fill_image, tally;
+  unsigned dense_count;                  // TrackState::dense_count / dense_samples before the launch
+  int dense_samples;
+  float* vmap[NUM_PYRS];
+  float* nmap[NUM_PYRS];
+  float* depth0;
+  uint8_t* last0;
+  const FramePreprocess* with;           // given: k_frame_inputs (the pre-processing tiles in the same grid), null: k_model_maps
+  uint8_t* next0;                        // with `with`: the frame's level-0 intensity image
+};
+// allocates a TrackState, launches, synchronises and frees; *dense_count_left: TrackState::dense_count behind the launch.  Returns the hipError_t
+// of the first call that failed as an int, 0 = hipSuccess
+int model_maps_op(const ModelMapsOp& o, unsigned* dense_count_left, hipStream_t s);
+struct SobelMaskOp {
+  int cols, rows;                        // of level 0
+  const uint8_t* nextImage[NUM_PYRS];
+  const float* nextDepth[NUM_PYRS];
+  int16_t* dIdx[NUM_PYRS];
+  int16_t* dIdy[NUM_PYRS];
+  uint8_t* mask[NUM_PYRS];
+  uint32_t* corres[NUM_PYRS];
+};
+void sobel_mask_op(const SobelMaskOp& o, hipStream_t s);
 // initFirstRGB, RGBDOdometry.cpp:246-257
 void init_first_rgb(const Pyramid& p, const uint8_t* rgb3, hipStream_t s);
 // getIncrementalTransformation, RGBDOdometry.cpp:259-571, entirely enqueued.  The update step of an iteration is evaluated at the head of the

@@ -71,17 +71,19 @@ void build_vn_levels(const Pyramid& p, const uint16_t* depth_filtered, Intr k, f
   g.z = NUM_PYRS;
   hipLaunchKernelGGL(k_vmap_nmap_levels, g, tile_block(), 0, s, L);
 }
-}  // namespace
-
-void init_icp_model(const Pyramid& p, const float* pred_vertex, const float* pred_normal, const float* fill_vertex,
-                    const float* fill_normal, const TrackState* st, float maxDepthRGB, hipStream_t s, const uint8_t* pred_image_rgba,
-                    const uint8_t* fill_image_rgba, bool frameToFrameRGB, const FramePreprocess* with, bool tally) {
-  ModelMapsArgs A = model_maps_args(p, true, pred_vertex, pred_normal, maxDepthRGB);
+// the model side's arguments with the fill-in choice, the image and the tally (init_icp_model, model_maps_op)
+ModelMapsArgs model_maps_choice_args(const Pyramid& p, bool model_side, const float* pred_vertex, const float* pred_normal, const float* fill_vertex,
+                                     const float* fill_normal, const TrackState* st, float maxDepthRGB, const uint8_t* pred_image_rgba,
+                                     const uint8_t* fill_image_rgba, bool frameToFrameRGB, bool tally) {
+  ModelMapsArgs A = model_maps_args(p, model_side, pred_vertex, pred_normal, maxDepthRGB);
   A.fill_vertex = (const float4*)fill_vertex; A.fill_normal = (const float4*)fill_normal;
   A.pred_image = pred_image_rgba; A.fill_image = fill_image_rgba; A.force_fill_image = frameToFrameRGB;
   A.tally_image = (tally && pred_image_rgba) ? pred_image_rgba : nullptr;
   A.tally_out = const_cast<unsigned*>(&st->dense_count);
   A.last0 = pred_image_rgba ? p.lastImage[0] : nullptr;
+  return A;
+}
+void launch_model_maps(const Pyramid& p, const ModelMapsArgs& A, const TrackState* st, const FramePreprocess* with, hipStream_t s) {
   const dim3 mg = model_maps_grid(p);
   if (with) {   // the frame's depth pre-processing rides on this launch (k_frame_inputs)
     PreArgs P{};
@@ -95,6 +97,45 @@ void init_icp_model(const Pyramid& p, const float* pred_vertex, const float* pre
     return;
   }
   hipLaunchKernelGGL(k_model_maps, mg, dim3(64, 4), 0, s, A, st);
+}
+}  // namespace
+
+void init_icp_model(const Pyramid& p, const float* pred_vertex, const float* pred_normal, const float* fill_vertex,
+                    const float* fill_normal, const TrackState* st, float maxDepthRGB, hipStream_t s, const uint8_t* pred_image_rgba,
+                    const uint8_t* fill_image_rgba, bool frameToFrameRGB, const FramePreprocess* with, bool tally) {
+  launch_model_maps(p, model_maps_choice_args(p, true, pred_vertex, pred_normal, fill_vertex, fill_normal, st, maxDepthRGB, pred_image_rgba,
+                                               fill_image_rgba, frameToFrameRGB, tally), st, with, s);
+}
+// ef_op_model_maps: init_icp_model's launch on a caller's buffers — a Pyramid that holds nothing but them, a TrackState that holds nothing but
+// the pose and the tally
+int model_maps_op(const ModelMapsOp& o, unsigned* dense_count_left, hipStream_t s) {
+  Pyramid p{};
+  p.width = o.cols; p.height = o.rows;
+  for (int i = 0; i < NUM_PYRS; ++i) {
+    p.vmap_g_prev[i] = p.vmap_curr[i] = o.vmap[i];
+    p.nmap_g_prev[i] = p.nmap_curr[i] = o.nmap[i];
+  }
+  p.lastDepth[0] = p.nextDepth[0] = o.depth0;
+  p.lastImage[0] = o.last0;
+  p.nextImage[0] = o.next0;
+  TrackState* h = new TrackState();
+  for (int i = 0; i < 9; ++i) h->R_wc_f[i] = o.R[i];
+  for (int i = 0; i < 3; ++i) h->t_wc_f[i] = o.t[i];
+  h->dense_count = o.dense_count;
+  h->dense_samples = o.dense_samples;
+  TrackState* st = nullptr;
+  hipError_t e = hipMalloc((void**)&st, sizeof(TrackState));
+  if (e == hipSuccess) e = hipMemcpy(st, h, sizeof(TrackState), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    launch_model_maps(p, model_maps_choice_args(p, !o.camera_frame, o.pred_vertex, o.pred_normal, o.fill_vertex, o.fill_normal, st, o.maxDepthRGB,
+                                                 o.pred_image, o.fill_image, o.force_fill_image, o.tally), st, o.with, s);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = hipMemcpy(dense_count_left, &st->dense_count, sizeof(unsigned), hipMemcpyDeviceToHost);
+  if (st) (void)hipFree(st);
+  delete h;
+  return (int)e;
 }
 void init_icp_maps(const Pyramid& p, const float* vertex, const float* normal, const uint8_t* image_rgba, const TrackState* st,
                    float maxDepthRGB, hipStream_t s) {
@@ -153,6 +194,16 @@ void init_rgb_sobel(const Pyramid& p, hipStream_t s) {
   dim3 g = tile_grid(p.W(0), p.H(0));
   g.z = NUM_PYRS;
   hipLaunchKernelGGL(k_sobel_levels, g, tile_block(), 0, s, sobel_levels_of(p));
+}
+// ef_op_sobel_mask: init_rgb_sobel on a Pyramid that holds nothing but the caller's buffers
+void sobel_mask_op(const SobelMaskOp& o, hipStream_t s) {
+  Pyramid p{};
+  p.width = o.cols; p.height = o.rows;
+  for (int i = 0; i < NUM_PYRS; ++i) {
+    p.nextImage[i] = const_cast<uint8_t*>(o.nextImage[i]); p.nextDepth[i] = const_cast<float*>(o.nextDepth[i]);
+    p.dIdx[i] = o.dIdx[i]; p.dIdy[i] = o.dIdy[i]; p.rgbMask[i] = o.mask[i]; p.corres[i] = o.corres[i];
+  }
+  init_rgb_sobel(p, s);
 }
 
 void init_first_rgb(const Pyramid& p, const uint8_t* rgb3, hipStream_t s) {

@@ -1025,8 +1025,14 @@ int ef_get_image(ef_ctx* ctx, int which, void* host_dst, size_t bytes);
 int ef_get_image_resized(ef_ctx* ctx, int which, int factor, void* host_dst, size_t bytes);
 /* tracker pyramids (RGBDOdometry private state) for kernel-level parity tests:
  * which: 0 vmap_curr 1 nmap_curr 2 vmap_g_prev 3 nmap_g_prev 4 lastDepth 5 nextDepth 6 lastImage
- *        7 nextImage 8 lastNextImage 9 dIdx 10 dIdy 11 depth_tmp */
+ *        7 nextImage 8 lastNextImage 9 dIdx 10 dIdy 11 depth_tmp
+ *        12 rgbMask (u8: the frame-invariant half of residualKernel's gates, 1 = the iterations revisit the pixel)
+ *        13 corres (u32 packed photometric correspondence of the last iteration: bit 31 valid | (diff + 255) << 22 | v0 << 11 | u0)
+ * nextDepth is lastDepth on the frame-to-model tracker (quirk Q1).
+ * ef_get_tracker_buffer_of: tracker 0 = frameToModel (what ef_get_tracker_buffer reads), 1 = modelToModel (close_loops contexts only:
+ * EF_ESTATE otherwise; its nextDepth is a buffer of its own and its depth_tmp is never written) */
 int ef_get_tracker_buffer(ef_ctx* ctx, int which, int level, void* host_dst, size_t bytes);
+int ef_get_tracker_buffer_of(ef_ctx* ctx, int tracker, int which, int level, void* host_dst, size_t bytes);
 
 /* per-stage GPU time of the last ef_process_frame (hipEvent pairs; names follow the reference's
  * TICK/TOCK sites, Core/Utils/Stopwatch.h): fills up to max entries, returns count in *n */
@@ -1137,6 +1143,45 @@ int ef_op_rgb_step(const void* corres_img, float sigma, const float* cloud_f3, f
 int ef_op_so3_step(const uint8_t* last_image, const uint8_t* next_image, const float* image_basis9,
                    const float* kinv9, const float* krlr9, int cols, int rows, float* A_host9, float* b_host3,
                    float* residual_host2, void* stream);
+
+/* The frame tier's two most heavily fused input launches on caller-owned DEVICE buffers, for parity tests against the composition of
+ * reference operators each stands for.  No behaviour of a frame depends on these two entries.
+ * ef_op_model_maps: the shipped k_model_maps (copyMaps -> resizeVMap / resizeNMap x2 -> tranformMaps x3, verticesToDepth and the model's
+ * level-0 intensity in one launch, RGBDOdometry.cpp:171-239), or -- joint != 0 -- the model-map half of k_frame_inputs, whose grid also
+ * carries the depth pre-processing tiles of a raw frame (filtered / metric / metric_filtered / next0 come back as well).
+ * The source of the maps is the prediction or the fill-in: !(dense_count / dense_samples > 0.75) reads the fill-in
+ * (ElasticFusion.cpp:256-268,304-305); tally != 0: the count is first taken from pred_image's (cols / 20) x (rows / 20) sample texels
+ * (20 a + 10, 20 b + 10), and *dense_count_left receives it.  camera_frame != 0: copyMaps + resize only (initICP on predicted maps).
+ * cols and rows are multiples of 4.  vmap / nmap: 3 planes per level (levels 0-2); outputs keep what they held where the launch does
+ * not write (quirk Q3: y / z planes of an invalid texel of levels 1-2).  Synchronises. */
+typedef struct ef_model_maps_op {
+  int cols, rows;
+  const float *pred_vertex, *pred_normal, *fill_vertex, *fill_normal;   /* 4 floats per texel */
+  const uint8_t *pred_image, *fill_image;                               /* rgba, or both NULL: last0 is not written */
+  float R[9], t[3];                                                     /* T_wc as floats (RGBDOdometry.cpp:192-193) */
+  float max_depth_rgb;                                                  /* RGBDOdometry.cpp:42 */
+  int camera_frame, force_fill_image, tally;
+  unsigned dense_count;
+  int dense_samples;
+  float* vmap[3];
+  float* nmap[3];
+  float* depth0;                                                        /* lastDepth[0] (camera_frame: nextDepth[0]) */
+  uint8_t* last0;                                                       /* lastImage[0] */
+  int joint;
+  const uint16_t* raw;                                                  /* joint: the frame's raw depth and packed rgb */
+  const uint8_t* rgb3;
+  float depth_cut;
+  uint16_t* filtered;
+  float* metric;
+  float* metric_filtered;
+  uint8_t* next0;                                                       /* nextImage[0] */
+} ef_model_maps_op;
+int ef_op_model_maps(const ef_model_maps_op* args, unsigned* dense_count_left, void* stream);
+/* ef_op_sobel_mask: k_sobel_levels on a caller's nextImage / nextDepth pyramids (arrays of 3 device pointers, level l is
+ * (cols >> l) x (rows >> l)): computeDerivativeImages of every level, the frame-invariant half of residualKernel's gates
+ * (reduce.cu:631-667; minScale = 1600, 576, 64) as one byte per pixel, and the packed correspondences reset to 0.  Synchronises. */
+int ef_op_sobel_mask(const uint8_t* const* next_image3, const float* const* next_depth3, int cols, int rows, int16_t* const* dIdx3,
+                     int16_t* const* dIdy3, uint8_t* const* mask3, uint32_t* const* corres3, void* stream);
 
 /* The tracking driver's small linear algebra (Eigen / Sophus arithmetic of RGBDOdometry.cpp:356,526-534,566-570,
  * OdometryProvider.h:34-96, ElasticFusion.cpp:371-374) as the DEVICE evaluates it, host vectors in and out

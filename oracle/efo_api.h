@@ -177,6 +177,8 @@ const void* efo_fusion_old_buffer(const efo_fusion*, int which);
  * 7 indexMap(u32) 8 vertConf 9 colorTime 10 normRad 11 depthFiltered(u16) 12 depthMetric 13 depthMetricFiltered */
 const void* efo_fusion_buffer(const efo_fusion*, int which);
 efo_odometry* efo_fusion_odometry(efo_fusion*);
+/* which: 0 frameToModel (what efo_fusion_odometry returns), 1 modelToModel (the local loop closure's tracker); anything else: null */
+efo_odometry* efo_fusion_odometry_of(efo_fusion*, int which);
 /* tracking-only timing hook for bench.py cpu_baseline: runs initICP/initRGB/track on the current state */
 
 /* ---- fern keyframe database (Core/Ferns.cpp), efo_ferns.cpp; signatures as include/ef_hip.h ef_ferns_* ---- */

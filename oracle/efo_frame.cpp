@@ -652,6 +652,7 @@ const void* efo_fusion_buffer(const efo_fusion* f, int which) {
   return nullptr;
 }
 efo_odometry* efo_fusion_odometry(efo_fusion* f) { return f->frameToModel; }
+efo_odometry* efo_fusion_odometry_of(efo_fusion* f, int which) { return which == 0 ? f->frameToModel : which == 1 ? f->modelToModel : nullptr; }
 
 // ---- linalg exports for known-answer tests ----
 void efo_ldlt6(const double* A, const double* b, double* x) { ldlt_solve<double, 6>(A, b, x); }

@@ -142,6 +142,7 @@ def _load(path):
     so.efo_fusion_create.restype = P
     so.efo_fusion_buffer.restype = P
     so.efo_fusion_odometry.restype = P
+    so.efo_fusion_odometry_of.restype = P
     so.efo_se3_log_norm.restype = C.c_double
     so.efo_expf_spec.restype = c_f
     so.efo_expf_spec.argtypes = [c_f]
@@ -768,9 +769,10 @@ class Fusion:
         lib().efo_fusion_stats(self.h_, ptr(out))
         return out
 
-    def odometry(self):
+    def odometry(self, which=0):
+        """which: 0 frameToModel, 1 modelToModel (the local loop closure's tracker)"""
         return Odometry(self.p.width, self.p.height, self.p.cx, self.p.cy, self.p.fx, self.p.fy,
-                        handle=lib().efo_fusion_odometry(self.h_))
+                        handle=lib().efo_fusion_odometry_of(self.h_, c_i(which)))
 
     _BUF = {0: (np.uint8, 4), 1: (np.float32, 4), 2: (np.float32, 4), 3: (np.uint16, 1), 4: (np.uint8, 4),
             5: (np.float32, 4), 6: (np.float32, 4), 7: (np.uint32, 1), 8: (np.float32, 4), 9: (np.float32, 4),
