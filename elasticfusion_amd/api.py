@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
@@ -67,6 +68,10 @@ class ef_track_end_out(C.Structure):
 
 class ef_timing(C.Structure):
     _fields_ = [("name", C.c_char_p), ("ms", c_f)]
+
+
+class ef_kernel_time(C.Structure):   # ef_get_kernel_timing / ef_get_splat_timing / ef_get_tracker_timing
+    _fields_ = [("name", C.c_char_p), ("avg_us", c_f), ("launches", c_i), ("bytes_per_launch", C.c_double), ("bytes_per_launch_survey", C.c_double)]
 
 
 class ef_tracker_plan(C.Structure):
@@ -200,20 +205,61 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise EFError(f"{LIB_PATH} not built: run `python -m elasticfusion_amd.build` (hipcc, gfx950). "
                           "There is no CPU fallback for this engine.")
-        _lib = C.CDLL(LIB_PATH)
-        _lib.ef_last_error.restype = C.c_char_p
-        _lib.ef_last_error.argtypes = [P]
-        _lib.ef_stream.restype = P
-        _lib.ef_stream.argtypes = [P]
+        _lib = _bind(C.CDLL(LIB_PATH))
     return _lib
 
 
 def use_library(path: str | None = None):
-    """Rebinds this module to another build of the same C ABI (tests only: libefusion_hip_nofma.so, the -DEF_NO_FMA
-    variant that is compared bit for bit with the compiled reference).  None = back to the product library."""
+    """Rebinds this module to another build of the same C ABI (build.FAST_LIB, the opt-in fast-order build; an A/B build given by path).
+    None = back to the product library.  The next lib() loads it and declares its signatures anew."""
     global _lib, LIB_PATH
     _lib = None
     LIB_PATH = path or os.path.join(_HERE, "libefusion_hip.so")
+
+
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "ef_hip.h")
+_PROTOTYPE = re.compile(r"(?:^|[;}])\s*((?:const\s+)?\w+[\s*]+)(ef_\w+)\s*\(([^()]*)\)\s*;", re.M)
+_SCALARS = {"int": c_i, "unsigned": c_u32, "uint32_t": c_u32, "float": c_f, "size_t": C.c_size_t, "int64_t": C.c_int64}
+_RETURNS = {"int": c_i, "void": None, "float": c_f}
+_signatures = None
+
+
+def _kind(decl, table, max_words, prototype):
+    """the ctypes type of a return type (max_words 1) or of one parameter with or without its name (max_words 2)"""
+    words = re.sub(r"\*|\bconst\b", " ", decl).split()
+    if "*" in decl:
+        return C.c_char_p if table is _RETURNS and words == ["char"] else P
+    if not 1 <= len(words) <= max_words or words[0] not in table:
+        raise EFError(f"{HEADER}: no ctypes kind for '{decl.strip()}' of {prototype}")
+    return table[words[0]]
+
+
+def signatures() -> dict:
+    """name -> (restype, argtypes) of every ef_* function include/ef_hip.h declares.  The kinds form a closed set: any pointer is a
+    c_void_p (byref, arrays, None, a CFUNCTYPE object, an int at full width), scalars and callback typedefs go by the tables, a
+    const char* is returned as bytes; a prototype with anything else raises."""
+    global _signatures
+    if _signatures is None:
+        text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", open(HEADER).read(), flags=re.S)
+        text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+        params = dict(_SCALARS, ef_fern_tracker=FERN_TRACKER, ef_loop_solver=LOOP_SOLVER, ef_view_fetch=P)
+        found = {}
+        for ret, name, args in _PROTOTYPE.findall(text):
+            prototype = " ".join(f"{ret}{name}({args})".split())
+            args = [] if args.strip() in ("", "void") else args.split(",")
+            found[name] = (_kind(ret, _RETURNS, 1, prototype), [_kind(a, params, 2, prototype) for a in args])
+        _signatures = found
+    return _signatures
+
+
+def _bind(library, prefix="ef_", exported_as=None):
+    """the one place signatures are declared: restype and argtypes of every header prototype `prefix`* the library exports (a variant
+    build may lack a symbol; exported_as: the prefix another implementation of the same C interface exports them under)"""
+    for name, (restype, argtypes) in signatures().items():
+        fn = getattr(library, (exported_as or prefix) + name[len(prefix):], None) if name.startswith(prefix) else None
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
+    return library
 
 
 def _chk(rc: int, ctx=None):
@@ -233,29 +279,34 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(P)
 
 
+def _dev(v):
+    """a device pointer given as int, c_void_p or None, as a pointer parameter takes it (at full width)"""
+    return v if v is None or isinstance(v, P) else int(v)
+
+
 class DevBuf:
     """A raw HIP allocation owned through the C ABI (ef_dev_alloc / ef_dev_free)."""
 
     def __init__(self, nbytes: int, fill: int | None = 0):
         self.p = P()
         self.nbytes = int(nbytes)
-        _chk(lib().ef_dev_alloc(C.byref(self.p), C.c_size_t(self.nbytes)))
+        _chk(lib().ef_dev_alloc(C.byref(self.p), self.nbytes))
         if fill is not None:
-            _chk(lib().ef_dev_memset(self.p, c_i(fill), C.c_size_t(self.nbytes)))
+            _chk(lib().ef_dev_memset(self.p, fill, self.nbytes))
 
     @classmethod
     def from_array(cls, a: np.ndarray) -> "DevBuf":
         a = np.ascontiguousarray(a)
         b = cls(a.nbytes, fill=None)
         if a.nbytes:
-            _chk(lib().ef_dev_upload(b.p, _ptr(a), C.c_size_t(a.nbytes)))
+            _chk(lib().ef_dev_upload(b.p, _ptr(a), a.nbytes))
         return b
 
     def to_array(self, dtype, shape) -> np.ndarray:
         out = np.empty(shape, dtype)
         assert out.nbytes <= self.nbytes, (out.nbytes, self.nbytes)
         if out.nbytes:
-            _chk(lib().ef_dev_download(_ptr(out), self.p, C.c_size_t(out.nbytes)))
+            _chk(lib().ef_dev_download(_ptr(out), self.p, out.nbytes))
         return out
 
     def __del__(self):
@@ -282,7 +333,7 @@ def write_freiburg(path: str, T_wc, timestamps):
     T = np.ascontiguousarray(T_wc, np.float64).reshape(-1, 16)
     ts = np.ascontiguousarray(timestamps, np.int64)
     assert len(T) == len(ts)
-    _chk(lib().ef_write_freiburg(path.encode(), _ptr(T), _ptr(ts), c_i(len(T))))
+    _chk(lib().ef_write_freiburg(path.encode(), _ptr(T), _ptr(ts), len(T)))
 
 
 class GlobalLoop(C.Structure):   # ef_global_loop
@@ -296,8 +347,8 @@ class RelocState(C.Structure):   # ef_reloc_state
 
 class LocalLoop(C.Structure):   # ef_local_loop
     _fields_ = [("attempted", c_i), ("cov_ok", c_i), ("gates_ok", c_i), ("n_constraints", c_i), ("applied", c_i),
-                ("graph_nodes", c_i), ("graph_capacity", c_i), ("pad_", c_i), ("stats", c_f * 6), ("cov_diag", C.c_double * 6), ("T_wc_curr", C.c_double * 16),
-                ("T_wc_est", C.c_double * 16)]
+                ("graph_nodes", c_i), ("graph_capacity", c_i), ("reserved_", c_i), ("stats", c_f * 6), ("cov_diag", C.c_double * 6),
+                ("T_wc_curr", C.c_double * 16), ("T_wc_est", C.c_double * 16)]
 
 
 LOOP_SOLVER = C.CFUNCTYPE(c_i, C.c_void_p, C.POINTER(LocalLoop), C.POINTER(C.c_double), c_i, C.POINTER(c_f), C.POINTER(c_i))
@@ -309,8 +360,8 @@ def solve_local_deformation(nodes4, constraints, src_time, last_deform_time=0):
     cons = np.ascontiguousarray(constraints, np.float64).reshape(-1, 8)
     g = np.zeros((max(len(nodes4), 1), 16), np.float32)
     e, m = c_f(0), c_f(0)
-    rc = lib().ef_solve_local_deformation(_ptr(nodes4), c_i(len(nodes4)), _ptr(cons), c_i(len(cons)), C.c_int64(int(src_time)),
-                                          C.c_int64(int(last_deform_time)), _ptr(g), C.byref(e), C.byref(m))
+    rc = lib().ef_solve_local_deformation(_ptr(nodes4), len(nodes4), _ptr(cons), len(cons), int(src_time),
+                                          int(last_deform_time), _ptr(g), C.byref(e), C.byref(m))
     return (g[:len(nodes4)], e.value, m.value) if rc == 0 else None
 
 
@@ -340,8 +391,8 @@ def solve_deformation(nodes4, rows, fernMatch=False, last_deform_time=0, poses=N
     rel = (GraphConstraint * max(len(rows), 1))()
     n_rel, e, m = c_i(0), c_f(0), c_f(0)
     gz = None if gates is None else (c_f * 3)(*[float(x) for x in gates])
-    rc = lib().ef_solve_deformation_gated(_ptr(nodes4), c_i(len(nodes4)), cons, c_i(len(rows)), c_i(int(bool(fernMatch))), C.c_int64(int(last_deform_time)),
-                                          _ptr(P16) if len(P16) else None, _ptr(times) if len(P16) else None, c_i(len(P16)), _ptr(g), C.byref(e),
+    rc = lib().ef_solve_deformation_gated(_ptr(nodes4), len(nodes4), cons, len(rows), int(bool(fernMatch)), int(last_deform_time),
+                                          _ptr(P16) if len(P16) else None, _ptr(times) if len(P16) else None, len(P16), _ptr(g), C.byref(e),
                                           C.byref(m), rel, C.byref(n_rel), gz)
     if rc not in (0, -4):
         _chk(rc)
@@ -351,6 +402,22 @@ def solve_deformation(nodes4, rows, fernMatch=False, last_deform_time=0, poses=N
 
 FERN_TRACKER = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(c_f), C.POINTER(c_f), C.POINTER(C.c_double), C.POINTER(c_f), C.POINTER(c_f),
                            C.POINTER(C.c_double), C.POINTER(c_f), C.POINTER(c_f))
+
+
+def _fern_tracker(tracker, w, h):
+    """tracker(fern_verts, fern_norms, T_wc_fern, verts, norms, T_wc) -> (T_wc_est, icp_error, icp_count) on w x h views as an ef_fern_tracker"""
+    px = w * h * 4
+
+    def tramp(_user, fv, fn, Tf, cv, cn, Tio, err, cnt):
+        A = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n,)).astype(dt).copy()
+        Te, e, k = tracker(A(fv, px, np.float32).reshape(h, w, 4), A(fn, px, np.float32).reshape(h, w, 4), A(Tf, 16, np.float64).reshape(4, 4),
+                           A(cv, px, np.float32).reshape(h, w, 4), A(cn, px, np.float32).reshape(h, w, 4), A(Tio, 16, np.float64).reshape(4, 4))
+        Te = np.ascontiguousarray(Te, np.float64).reshape(16)
+        for i in range(16):
+            Tio[i] = Te[i]
+        err[0], cnt[0] = float(e), float(k)
+
+    return FERN_TRACKER(tramp)
 
 
 class Ferns:
@@ -371,21 +438,10 @@ class Ferns:
     def __init__(self, n=500, maxDepth=3000, photoThresh=115.0, width=640, height=480, fx=528.0, fy=528.0, cx=320.0, cy=240.0, seed=0):
         self._h = None
         self._L = self._library()
-        f = self._f
-        f("create").restype = P
-        f("create").argtypes = [c_i, c_i, c_f, c_i, c_i, c_f, c_f, c_f, c_f, C.c_uint]
-        f("block_hd_aware").restype = f("photometric_check").restype = c_f
-        f("destroy").argtypes = [P]
-        f("get_table").argtypes = f("set_table").argtypes = [P, P]
-        f("add_frame").argtypes = [P, P, c_i, P, P, P, c_i, c_f]
-        f("find_frame").argtypes = [P, P, c_i, P, P, P, c_i, c_i, FERN_TRACKER, P, P, P, c_i, P]
-        f("count").argtypes = f("last_closest").argtypes = [P]
-        f("get_frame").argtypes = [P, c_i, P, P, P, P, P, P, P]
-        f("set_frame_pose").argtypes = [P, c_i, P]
-        f("block_hd_aware").argtypes = [P, c_i, c_i]
-        f("photometric_check").argtypes = [P, P, c_i, P, P, c_i]
+        if self._L is not _lib:     # another implementation: the header's ef_ferns_* signatures, under its prefix
+            _bind(self._L, Ferns._prefix, self._prefix)
         self.num, self.w, self.h = int(n), width // 8, height // 8
-        self._h = f("create")(int(n), int(maxDepth), float(photoThresh), int(width), int(height), fx, fy, cx, cy, int(seed))
+        self._h = self._f("create")(int(n), int(maxDepth), photoThresh, int(width), int(height), fx, fy, cx, cy, int(seed))
         if not self._h:
             raise EFError("ef_ferns_create: bad arguments")
 
@@ -427,19 +483,7 @@ class Ferns:
     def findFrame(self, rgb, verts, norms, T_wc, time, lost, tracker):
         rgb, verts, norms = self._view(rgb, verts, norms)
         T = np.ascontiguousarray(T_wc, np.float64).reshape(4, 4)
-        px = self.w * self.h * 4
-
-        def tramp(_user, fv, fn, Tf, cv, cn, Tio, err, cnt):
-            A = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n,)).astype(dt).copy()
-            Te, e, k = tracker(A(fv, px, np.float32).reshape(self.h, self.w, 4), A(fn, px, np.float32).reshape(self.h, self.w, 4),
-                               A(Tf, 16, np.float64).reshape(4, 4), A(cv, px, np.float32).reshape(self.h, self.w, 4),
-                               A(cn, px, np.float32).reshape(self.h, self.w, 4), A(Tio, 16, np.float64).reshape(4, 4))
-            Te = np.ascontiguousarray(Te, np.float64).reshape(16)
-            for i in range(16):
-                Tio[i] = Te[i]
-            err[0], cnt[0] = float(e), float(k)
-
-        cb = FERN_TRACKER(tramp)
+        cb = _fern_tracker(tracker, self.w, self.h)
         T_est = np.zeros((4, 4), np.float64)
         cons = np.zeros((self.num, 6), np.float64)
         n = c_i(0)
@@ -487,16 +531,6 @@ class Closure:
                  _borrowed=None):
         L = lib()
         self._owned = _borrowed is None
-        L.ef_closure_create.restype = L.ef_closure_ferns.restype = P
-        L.ef_closure_create.argtypes = [c_i, c_f, c_f, c_f, c_i, c_i, c_f, c_f, c_f, c_f, C.c_uint]
-        L.ef_closure_destroy.argtypes = L.ef_closure_ferns.argtypes = [P]
-        L.ef_closure_global.argtypes = [P, P, c_i, P, P, P, c_i, FERN_TRACKER, P, P, c_i, P, P, P]
-        L.ef_closure_local.argtypes = [P, P, c_i, c_i, P, c_i, P, P]
-        L.ef_closure_end_frame.argtypes = [P, P, c_i, P, P, P, c_i]
-        L.ef_closure_counts.argtypes = [P, P, P, P, P]
-        L.ef_closure_last_rows.argtypes = [P, P, c_i, P, P]
-        L.ef_closure_relative.argtypes = [P, P, c_i]
-        L.ef_closure_trajectory.argtypes = [P, P, c_i]
         self.w, self.h = width // 8, height // 8
         self._h = _borrowed if _borrowed is not None else L.ef_closure_create(int(n), depthCut, photoThresh, fernThresh, int(width), int(height), fx, fy,
                                                                               cx, cy, int(seed))
@@ -505,11 +539,6 @@ class Closure:
         self.ferns = Ferns.__new__(Ferns)        # a view of the database the closure object owns
         self.ferns._L, self.ferns._h, self.ferns._owned = L, L.ef_closure_ferns(self._h), False
         self.ferns.num, self.ferns.w, self.ferns.h = int(n), self.w, self.h
-        for name, res in (("count", c_i), ("last_closest", c_i), ("block_hd_aware", c_f), ("photometric_check", c_f)):
-            self.ferns._f(name).restype = res
-        self.ferns._f("count").argtypes = self.ferns._f("last_closest").argtypes = [P]
-        self.ferns._f("get_frame").argtypes = [P, c_i, P, P, P, P, P, P, P]
-        self.ferns._f("get_table").argtypes = [P, P]
 
     def close(self):
         if self._h and self._owned:
@@ -527,19 +556,7 @@ class Closure:
         rgb, verts, norms = self._view(rgb, verts, norms)
         T = np.ascontiguousarray(T_wc, np.float64).reshape(4, 4)
         nodes4 = np.ascontiguousarray(nodes4, np.float32).reshape(-1, 4)
-        px = self.w * self.h * 4
-
-        def tramp(_user, fv, fn, Tf, cv, cn, Tio, err, cnt):
-            A = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n,)).astype(dt).copy()
-            Te, e, k = tracker(A(fv, px, np.float32).reshape(self.h, self.w, 4), A(fn, px, np.float32).reshape(self.h, self.w, 4),
-                               A(Tf, 16, np.float64).reshape(4, 4), A(cv, px, np.float32).reshape(self.h, self.w, 4),
-                               A(cn, px, np.float32).reshape(self.h, self.w, 4), A(Tio, 16, np.float64).reshape(4, 4))
-            Te = np.ascontiguousarray(Te, np.float64).reshape(16)
-            for i in range(16):
-                Tio[i] = Te[i]
-            err[0], cnt[0] = float(e), float(k)
-
-        cb = FERN_TRACKER(tramp)
+        cb = _fern_tracker(tracker, self.w, self.h)
         Tr = np.zeros((4, 4), np.float64)
         g = np.zeros((1024, 16), np.float32)
         n = c_i(0)
@@ -553,21 +570,8 @@ class Closure:
         """a LOST camera's mid-frame step (ef_closure_relocalise: Ferns::findFrame with lost = true) -> (found, T_recovery [4, 4])"""
         rgb, verts, norms = self._view(rgb, verts, norms)
         T = np.ascontiguousarray(T_wc, np.float64).reshape(4, 4)
-        px = self.w * self.h * 4
-
-        def tramp(_user, fv, fn, Tf, cv, cn, Tio, err, cnt):
-            A = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n,)).astype(dt).copy()
-            Te, e, k = tracker(A(fv, px, np.float32).reshape(self.h, self.w, 4), A(fn, px, np.float32).reshape(self.h, self.w, 4),
-                               A(Tf, 16, np.float64).reshape(4, 4), A(cv, px, np.float32).reshape(self.h, self.w, 4),
-                               A(cn, px, np.float32).reshape(self.h, self.w, 4), A(Tio, 16, np.float64).reshape(4, 4))
-            Te = np.ascontiguousarray(Te, np.float64).reshape(16)
-            for i in range(16):
-                Tio[i] = Te[i]
-            err[0], cnt[0] = float(e), float(k)
-
-        cb = FERN_TRACKER(tramp)
+        cb = _fern_tracker(tracker, self.w, self.h)
         Tr = np.zeros((4, 4), np.float64)
-        lib().ef_closure_relocalise.argtypes = [P, P, c_i, P, P, P, c_i, FERN_TRACKER, P, P]
         rc = lib().ef_closure_relocalise(self._h, _ptr(rgb), rgb.shape[2], _ptr(verts), _ptr(norms), _ptr(T), int(tick), cb, None, _ptr(Tr))
         if rc < 0:
             _chk(rc)
@@ -576,7 +580,6 @@ class Closure:
     def logPose(self, T_wc, tick):
         """the end of a lost camera's frame (ef_closure_log_pose): the pose joins the trajectory, no keyframe is stored"""
         T = np.ascontiguousarray(T_wc, np.float64).reshape(4, 4)
-        lib().ef_closure_log_pose.argtypes = [P, P, c_i]
         _chk(lib().ef_closure_log_pose(self._h, _ptr(T), int(tick)))
 
     def localClosure(self, constraints8, tick, nodes4):
@@ -599,7 +602,7 @@ class Closure:
 
     def setGates(self, entry=0.06, meanConsErr=3e-4, energy=0.12):
         """the three gates of the global deformation (ef_closure_set_gates); defaults = the reference's constants"""
-        _chk(lib().ef_closure_set_gates(P(self._h) if not isinstance(self._h, P) else self._h, c_f(entry), c_f(meanConsErr), c_f(energy)))
+        _chk(lib().ef_closure_set_gates(self._h, entry, meanConsErr, energy))
 
     def counts(self):
         v = [c_i(0) for _ in range(4)]
@@ -658,7 +661,7 @@ class ElasticFusion:
         _chk(lib().ef_create(C.byref(cfg), C.byref(self.h)))
         self._solver = None
         if closeLoops:
-            _chk(lib().ef_set_loop_thresholds(self.h, c_i(countThresh), c_f(errThresh), c_f(covThresh)), self.h)
+            _chk(lib().ef_set_loop_thresholds(self.h, countThresh, errThresh, covThresh), self.h)
         if reloc:
             self.setRelocalisation(True)
 
@@ -675,13 +678,13 @@ class ElasticFusion:
         depth = np.ascontiguousarray(depth, np.uint16)
         assert rgb.size == self.cfg.width * self.cfg.height * 3 and depth.size == self.cfg.width * self.cfg.height
         T = None if in_T_wc is None else np.ascontiguousarray(in_T_wc, np.float64).reshape(16)
-        _chk(lib().ef_process_frame(self.h, _ptr(rgb), _ptr(depth), C.c_int64(timestamp), c_f(weightMultiplier),
+        _chk(lib().ef_process_frame(self.h, _ptr(rgb), _ptr(depth), timestamp, weightMultiplier,
                                     _ptr(T) if T is not None else None), self.h)
 
     def processFrameDevice(self, rgb_dev, depth_dev, timestamp: int = 0, weightMultiplier: float = 1.0, in_T_wc=None):
         """rgb_dev / depth_dev: raw device pointers (int or c_void_p) of frames already resident in HBM."""
         T = None if in_T_wc is None else np.ascontiguousarray(in_T_wc, np.float64).reshape(16)
-        _chk(lib().ef_process_frame_dev(self.h, P(int(rgb_dev)), P(int(depth_dev)), C.c_int64(timestamp), c_f(weightMultiplier),
+        _chk(lib().ef_process_frame_dev(self.h, _dev(rgb_dev), _dev(depth_dev), timestamp, weightMultiplier,
                                         _ptr(T) if T is not None else None), self.h)
 
     # --- local loop closure, front half (ElasticFusion.cpp:447-527; closeLoops=True contexts) ---
@@ -690,7 +693,7 @@ class ElasticFusion:
         Stands where Deformation::constrain stands in the reference; called inside processFrame."""
         if fn is None:
             self._solver = None
-            _chk(lib().ef_set_loop_solver(self.h, None, None), self.h)
+            _chk(lib().ef_set_loop_solver(self.h, LOOP_SOLVER(), None), self.h)   # (a NULL callback: a CFUNCTYPE parameter takes no None)
             return
 
         def tramp(user, info, cons, n, graph_out, nodes_out):
@@ -709,7 +712,7 @@ class ElasticFusion:
 
     # --- relocalisation (the reference constructor's `reloc`; ElasticFusion.cpp:326-366, 411-413, 536, 601-604) ---
     def setRelocalisation(self, on=True):
-        _chk(lib().ef_set_relocalisation(self.h, c_i(int(on))), self.h)
+        _chk(lib().ef_set_relocalisation(self.h, int(on)), self.h)
 
     def relocState(self) -> RelocState:
         s = RelocState()
@@ -722,9 +725,7 @@ class ElasticFusion:
     # --- global loop closure (ElasticFusion.cpp:392-445, 609-618; closeLoops=True contexts) ---
     def enableGlobalClosure(self, n=500, photoThresh=115.0, fernThresh=0.3095, seed=0):
         """ef_enable_global_closure: the fern database, its 1/8-resolution tracker and the closure bookkeeping inside processFrame"""
-        _chk(lib().ef_enable_global_closure(self.h, c_i(int(n)), c_f(photoThresh), c_f(fernThresh), C.c_uint(int(seed))), self.h)
-        lib().ef_get_closure.restype = P
-        lib().ef_get_closure.argtypes = [P]
+        _chk(lib().ef_enable_global_closure(self.h, int(n), photoThresh, fernThresh, int(seed)), self.h)
         self._closure = Closure(n=n, width=self.cfg.width, height=self.cfg.height, _borrowed=lib().ef_get_closure(self.h))
         return self._closure
 
@@ -735,8 +736,6 @@ class ElasticFusion:
     def closure(self):
         # every look at the closure object goes through ef_get_closure: the engine defers the end-of-frame bookkeeping (keyframe decision,
         # trajectory entry) to its next synchronisation point, and ef_get_closure is one
-        lib().ef_get_closure.restype = P
-        lib().ef_get_closure.argtypes = [P]
         lib().ef_get_closure(self.h)
         return self._closure
 
@@ -747,14 +746,14 @@ class ElasticFusion:
 
     def useBuiltinLoopSolver(self, on=True):
         """the built-in deformation-graph optimiser where Deformation::constrain stands (ef_use_builtin_loop_solver)"""
-        _chk(lib().ef_use_builtin_loop_solver(self.h, c_i(int(on))), self.h)
+        _chk(lib().ef_use_builtin_loop_solver(self.h, int(on)), self.h)
 
     def localLoop(self):
         """(info, constraints [n, 8]) of the last processFrame."""
         info = LocalLoop()
         cons = np.zeros((4096, 8), np.float64)
         n = c_i(0)
-        _chk(lib().ef_get_local_loop(self.h, C.byref(info), _ptr(cons), c_i(len(cons)), C.byref(n)), self.h)
+        _chk(lib().ef_get_local_loop(self.h, C.byref(info), _ptr(cons), len(cons), C.byref(n)), self.h)
         return info, cons[:n.value].copy()
 
     def imageResized(self, name: str, factor: int) -> np.ndarray:
@@ -762,14 +761,14 @@ class ElasticFusion:
         which, dt, ch = self.IMAGES[name]
         h, w = self.cfg.height // factor, self.cfg.width // factor
         out = np.zeros((h, w, ch) if ch > 1 else (h, w), dt)
-        _chk(lib().ef_get_image_resized(self.h, c_i(which), c_i(factor), _ptr(out), C.c_size_t(out.nbytes)), self.h)
+        _chk(lib().ef_get_image_resized(self.h, which, factor, _ptr(out), out.nbytes), self.h)
         return out
 
     def sampleGraph(self, max_nodes=1024):
         """Deformation::sampleGraphModel: [n, 4] float32 {x, y, z, initTime} of every 5000th surfel."""
         out = np.zeros((max_nodes, 4), np.float32)
         n = c_i(0)
-        _chk(lib().ef_sample_graph(self.h, _ptr(out), c_i(max_nodes), C.byref(n)), self.h)
+        _chk(lib().ef_sample_graph(self.h, _ptr(out), max_nodes, C.byref(n)), self.h)
         return out[:n.value].copy()
 
     def predict(self):
@@ -777,19 +776,19 @@ class ElasticFusion:
 
     def setResidentLevels(self, on=True):
         """level-resident pixel data in the persistent tracker launch (ef_set_resident_levels; default on)"""
-        _chk(lib().ef_set_resident_levels(self.h, c_i(int(on))), self.h)
+        _chk(lib().ef_set_resident_levels(self.h, int(on)), self.h)
 
     def setFusedStep(self, on=True):
         """level-0 update step inside the correspondence-search launch (ef_set_fused_step)"""
-        _chk(lib().ef_set_fused_step(self.h, c_i(int(on))), self.h)
+        _chk(lib().ef_set_fused_step(self.h, int(on)), self.h)
 
     def setTrackOnly(self, on=True):
         """odometry on a frozen map: track + predict, no fusion (ef_set_track_only; BASELINE.json configs[4])"""
-        _chk(lib().ef_set_track_only(self.h, c_i(int(on))), self.h)
+        _chk(lib().ef_set_track_only(self.h, int(on)), self.h)
 
     def setPersistentTracker(self, on=True):
         """small pyramid levels + SO(3) in one persistent launch (default) or one launch per step (ef_set_persistent_tracker)"""
-        _chk(lib().ef_set_persistent_tracker(self.h, c_i(int(on))), self.h)
+        _chk(lib().ef_set_persistent_tracker(self.h, int(on)), self.h)
 
     def debugInjectTrackerAbort(self):
         """test hook (ef_debug_inject_tracker_abort): what a persistent tracker launch leaves when a wait timed out after admission"""
@@ -815,7 +814,7 @@ class ElasticFusion:
 
     def debugOccupy(self, workgroups: int, microseconds: int):
         """test hook: CU-filling workgroups spinning on a stream of their own (ef_debug_occupy)"""
-        _chk(lib().ef_debug_occupy(self.h, c_i(int(workgroups)), c_i(int(microseconds))), self.h)
+        _chk(lib().ef_debug_occupy(self.h, int(workgroups), int(microseconds)), self.h)
 
     def stream(self) -> int:
         return int(lib().ef_stream(self.h) or 0)
@@ -831,7 +830,7 @@ class ElasticFusion:
         return t.value
 
     def setTick(self, v: int):
-        _chk(lib().ef_set_tick(self.h, c_i(v)), self.h)
+        _chk(lib().ef_set_tick(self.h, v), self.h)
 
     def getTimeDelta(self) -> int:
         return self.cfg.time_delta
@@ -856,11 +855,11 @@ class ElasticFusion:
 
     def trajectory(self):
         n = c_i(0)
-        _chk(lib().ef_get_trajectory(self.h, None, None, c_i(2**31 - 1), C.byref(n)), self.h)   # how many poses are logged (one per processed frame)
+        _chk(lib().ef_get_trajectory(self.h, None, None, 2**31 - 1, C.byref(n)), self.h)   # how many poses are logged (one per processed frame)
         cap = max(int(n.value), 1)
         T = np.zeros((cap, 16), np.float64)
         ts = np.zeros(cap, np.int64)
-        _chk(lib().ef_get_trajectory(self.h, _ptr(T), _ptr(ts), c_i(cap), C.byref(n)), self.h)
+        _chk(lib().ef_get_trajectory(self.h, _ptr(T), _ptr(ts), cap, C.byref(n)), self.h)
         return T[:n.value].reshape(-1, 4, 4).copy(), ts[:n.value].copy()
 
     def lastCount(self) -> int:
@@ -872,7 +871,7 @@ class ElasticFusion:
         n = self.lastCount()
         out = np.zeros((max(n, 1), 12), np.float32)
         got = c_u32(0)
-        _chk(lib().ef_map_download(self.h, _ptr(out), c_u32(n), C.byref(got)), self.h)
+        _chk(lib().ef_map_download(self.h, _ptr(out), n, C.byref(got)), self.h)
         return out[:got.value].copy()
 
     # --- GlobalModel::renderPointCloud without OpenGL (ef_render_model) ---
@@ -924,7 +923,7 @@ class ElasticFusion:
 
     def renderPointCloudDevice(self, params: ef_render_params, rgba=None, depth=None, vertex=None, normal=None, index=None):
         """ef_render_model_dev: raw device pointers (int, c_void_p or None), enqueued on the context's stream without synchronising"""
-        args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (rgba, depth, vertex, normal, index)]
+        args = [_dev(v) for v in (rgba, depth, vertex, normal, index)]
         _chk(lib().ef_render_model_dev(self.h, C.byref(params), *args), self.h)
 
     # --- stable surfel IDs and per-surfel labels (ef_set_surfel_ids / ef_enable_labels / ef_fuse_labels) ---
@@ -936,19 +935,19 @@ class ElasticFusion:
 
     def setSurfelIds(self, on=True):
         """every surfel carries a uint32 ID >= 1 (downloadMap()[:, 5] viewed as uint32), unique for the context's lifetime"""
-        _chk(lib().ef_set_surfel_ids(self.h, c_i(int(bool(on)))), self.h)
+        _chk(lib().ef_set_surfel_ids(self.h, int(bool(on))), self.h)
 
     def surfelIds(self) -> np.ndarray:
         n = self.lastCount()
         out = np.zeros(max(n, 1), np.uint32)
         got = c_u32(0)
-        _chk(lib().ef_get_surfel_ids(self.h, _ptr(out), c_u32(n), C.byref(got)), self.h)
+        _chk(lib().ef_get_surfel_ids(self.h, _ptr(out), n, C.byref(got)), self.h)
         return out[:got.value].copy()
 
     def enableLabels(self, numClasses: int):
         """a float32 [rows][numClasses] table that follows the map by ID (0: off)"""
         self.numClasses = int(numClasses)
-        _chk(lib().ef_enable_labels(self.h, c_i(int(numClasses))), self.h)
+        _chk(lib().ef_enable_labels(self.h, int(numClasses)), self.h)
 
     def fuseLabels(self, probs: np.ndarray, **view):
         """one observation: probs C x H x W float32 for the view given by renderParams keywords (none: the frame camera, drawUnstable)"""
@@ -958,7 +957,7 @@ class ElasticFusion:
 
     def fuseLabelsDevice(self, probs_dev, params: ef_render_params | None = None):
         """ef_fuse_labels_dev: a raw device pointer to C x H x W float32, enqueued on the context's stream"""
-        _chk(lib().ef_fuse_labels_dev(self.h, None if params is None else C.byref(params), P(int(probs_dev.value if isinstance(probs_dev, P) else probs_dev))), self.h)
+        _chk(lib().ef_fuse_labels_dev(self.h, None if params is None else C.byref(params), _dev(probs_dev)), self.h)
 
     def labels(self):
         """(ids, probs): the current rows' IDs and their C floats each, in map row order"""
@@ -966,13 +965,13 @@ class ElasticFusion:
         ids = np.zeros(max(n, 1), np.uint32)
         probs = np.zeros((max(n, 1), max(getattr(self, "numClasses", 1), 1)), np.float32)
         got = c_u32(0)
-        _chk(lib().ef_get_labels(self.h, _ptr(ids), _ptr(probs), c_u32(n), C.byref(got)), self.h)
+        _chk(lib().ef_get_labels(self.h, _ptr(ids), _ptr(probs), n, C.byref(got)), self.h)
         return ids[:got.value].copy(), probs[:got.value].copy()
 
     def setLabels(self, probs: np.ndarray):
         """the whole table: one row of C floats per surfel, in surfelIds() order"""
         probs = np.ascontiguousarray(probs, np.float32).reshape(-1, getattr(self, "numClasses", 1))
-        _chk(lib().ef_set_labels(self.h, _ptr(probs), c_u32(len(probs))), self.h)
+        _chk(lib().ef_set_labels(self.h, _ptr(probs), len(probs)), self.h)
 
     def renderLabels(self, **view):
         """(label H x W int32, prob H x W float32) of the view given by renderParams keywords; -1 / 0 where nothing is drawn"""
@@ -984,7 +983,7 @@ class ElasticFusion:
 
     def renderLabelsDevice(self, params: ef_render_params, label=None, prob=None):
         """ef_render_labels_dev: raw device pointers (int, c_void_p or None), enqueued on the context's stream"""
-        args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (label, prob)]
+        args = [_dev(v) for v in (label, prob)]
         _chk(lib().ef_render_labels_dev(self.h, C.byref(params), *args), self.h)
 
     # --- spatial index and nearest-surfel / kNN queries (ef_query_nearest / ef_query_knn) ---
@@ -992,34 +991,27 @@ class ElasticFusion:
 
     def setQueryCell(self, cell_m: float):
         """the index grid's cell edge in metres; results never depend on it"""
-        _chk(lib().ef_set_query_cell(self.h, c_f(cell_m)), self.h)
+        _chk(lib().ef_set_query_cell(self.h, cell_m), self.h)
 
     def debugQueryLanes(self, lanes: int):
-        _chk(lib().ef_debug_query_lanes(self.h, c_i(lanes)), self.h)
+        _chk(lib().ef_debug_query_lanes(self.h, lanes), self.h)
 
     def queryNearest(self, points, max_dist: float, min_conf: float = -1.0, ids: bool = False):
         """per point (n x 3) the nearest surfel with confidence > min_conf within max_dist, ties to the lower row: (rows uint32, dist = sqrt(d2),
         plane distance along the surfel's normal[, ids]); a miss is row 0xFFFFFFFF, dist inf, plane 0, id 0.  min_conf < 0: every surfel."""
+        row, d2, *rest = self.queryNearestRaw(points, max_dist, min_conf, ids)
+        return (row, np.sqrt(d2), *rest)
+
+    def queryNearestRaw(self, points, max_dist: float, min_conf: float = -1.0, ids: bool = False):
+        """(rows, dist2, plane[, ids]) exactly as ef_query_nearest writes them (dist2 not rooted)"""
         pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
         n = len(pts)
         row = np.zeros(max(n, 1), np.uint32)
         d2 = np.zeros(max(n, 1), np.float32)
         plane = np.zeros(max(n, 1), np.float32)
         sid = np.zeros(max(n, 1), np.uint32) if ids else None
-        _chk(lib().ef_query_nearest(self.h, _ptr(pts), c_u32(n), c_f(max_dist), c_f(min_conf), _ptr(row), None if sid is None else _ptr(sid),
-                                    _ptr(d2), _ptr(plane)), self.h)
-        out = (row[:n], np.sqrt(d2[:n]), plane[:n])
-        return out + (sid[:n],) if ids else out
-
-    def queryNearestRaw(self, points, max_dist: float, min_conf: float = -1.0):
-        """(rows, dist2, plane) exactly as ef_query_nearest writes them (dist2 not rooted)"""
-        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
-        n = len(pts)
-        row = np.zeros(max(n, 1), np.uint32)
-        d2 = np.zeros(max(n, 1), np.float32)
-        plane = np.zeros(max(n, 1), np.float32)
-        _chk(lib().ef_query_nearest(self.h, _ptr(pts), c_u32(n), c_f(max_dist), c_f(min_conf), _ptr(row), None, _ptr(d2), _ptr(plane)), self.h)
-        return row[:n], d2[:n], plane[:n]
+        _chk(lib().ef_query_nearest(self.h, _ptr(pts), n, max_dist, min_conf, _ptr(row), _ptr(sid) if ids else None, _ptr(d2), _ptr(plane)), self.h)
+        return (row[:n], d2[:n], plane[:n], sid[:n]) if ids else (row[:n], d2[:n], plane[:n])
 
     def queryKnn(self, points, k: int, max_dist: float, min_conf: float = -1.0):
         """per point the first min(k, eligible) surfels in (d2, row) order: (rows n x k uint32, dist2 n x k float32, count n uint32); unused slots
@@ -1030,18 +1022,18 @@ class ElasticFusion:
         rows = np.zeros((max(n, 1), kk), np.uint32)
         d2 = np.zeros((max(n, 1), kk), np.float32)
         cnt = np.zeros(max(n, 1), np.uint32)
-        _chk(lib().ef_query_knn(self.h, _ptr(pts), c_u32(n), c_i(k), c_f(max_dist), c_f(min_conf), _ptr(rows), _ptr(d2), _ptr(cnt)), self.h)
+        _chk(lib().ef_query_knn(self.h, _ptr(pts), n, k, max_dist, min_conf, _ptr(rows), _ptr(d2), _ptr(cnt)), self.h)
         return rows[:n], d2[:n], cnt[:n]
 
     def queryNearestDevice(self, points_dev, n: int, max_dist: float, min_conf: float = -1.0, row=None, ids=None, dist2=None, plane=None):
         """ef_query_nearest_dev: raw device pointers (int, c_void_p or None), enqueued on the context's stream"""
-        args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (points_dev, row, ids, dist2, plane)]
-        _chk(lib().ef_query_nearest_dev(self.h, args[0], c_u32(n), c_f(max_dist), c_f(min_conf), *args[1:]), self.h)
+        args = [_dev(v) for v in (points_dev, row, ids, dist2, plane)]
+        _chk(lib().ef_query_nearest_dev(self.h, args[0], n, max_dist, min_conf, *args[1:]), self.h)
 
     def queryKnnDevice(self, points_dev, n: int, k: int, max_dist: float, min_conf: float = -1.0, rows=None, dist2=None, count=None):
         """ef_query_knn_dev: raw device pointers (int, c_void_p or None), enqueued on the context's stream"""
-        args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (points_dev, rows, dist2, count)]
-        _chk(lib().ef_query_knn_dev(self.h, args[0], c_u32(n), c_i(int(k)), c_f(max_dist), c_f(min_conf), *args[1:]), self.h)
+        args = [_dev(v) for v in (points_dev, rows, dist2, count)]
+        _chk(lib().ef_query_knn_dev(self.h, args[0], n, int(k), max_dist, min_conf, *args[1:]), self.h)
 
     # --- rigid registration of a point set against the map (ef_register_step / ef_register_cloud) ---
     def registerParams(self, **kw) -> ef_register_params:
@@ -1077,7 +1069,7 @@ class ElasticFusion:
         s = ef_register_sums()
         row = np.zeros(max(n, 1), np.uint32) if pairs else None
         plane = np.zeros(max(n, 1), np.float32) if pairs else None
-        _chk(lib().ef_register_step(self.h, _ptr(pts), None if nrm is None else _ptr(nrm), c_u32(n), C.byref(params), pT, C.byref(s),
+        _chk(lib().ef_register_step(self.h, _ptr(pts), None if nrm is None else _ptr(nrm), n, C.byref(params), pT, C.byref(s),
                                     None if row is None else _ptr(row), None if plane is None else _ptr(plane)), self.h)
         out = _sums_dict(s)
         if pairs:
@@ -1100,7 +1092,7 @@ class ElasticFusion:
         res = ef_register_result()
         row = np.zeros(max(n, 1), np.uint32) if pairs else None
         plane = np.zeros(max(n, 1), np.float32) if pairs else None
-        _chk(lib().ef_register_cloud(self.h, _ptr(pts), None if nrm is None else _ptr(nrm), c_u32(n), C.byref(params), pT, _ptr(T),
+        _chk(lib().ef_register_cloud(self.h, _ptr(pts), None if nrm is None else _ptr(nrm), n, C.byref(params), pT, _ptr(T),
                                      C.byref(res), None if row is None else _ptr(row), None if plane is None else _ptr(plane)), self.h)
         out = self._registerResult(res)
         if pairs:
@@ -1111,21 +1103,21 @@ class ElasticFusion:
                            **kw):
         """ef_register_step_dev: raw device pointers (int, c_void_p or None) for points / normals / row / plane; waits for the sums"""
         params = params if params is not None else self.registerParams(**kw)
-        args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (points_dev, normals_dev, row, plane)]
+        args = [_dev(v) for v in (points_dev, normals_dev, row, plane)]
         keep, pT = _pose16(T)
         s = ef_register_sums()
-        _chk(lib().ef_register_step_dev(self.h, args[0], args[1], c_u32(n), C.byref(params), pT, C.byref(s), args[2], args[3]), self.h)
+        _chk(lib().ef_register_step_dev(self.h, args[0], args[1], n, C.byref(params), pT, C.byref(s), args[2], args[3]), self.h)
         return _sums_dict(s)
 
     def registerCloudDevice(self, points_dev, n: int, normals_dev=None, T_init=None, params: ef_register_params | None = None, row=None,
                             plane=None, **kw):
         """ef_register_cloud_dev: raw device pointers (int, c_void_p or None) for points / normals / row / plane"""
         params = params if params is not None else self.registerParams(**kw)
-        args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (points_dev, normals_dev, row, plane)]
+        args = [_dev(v) for v in (points_dev, normals_dev, row, plane)]
         keep, pT = _pose16(T_init)
         T = np.zeros(16, np.float64)
         res = ef_register_result()
-        _chk(lib().ef_register_cloud_dev(self.h, args[0], args[1], c_u32(n), C.byref(params), pT, _ptr(T), C.byref(res), args[2], args[3]),
+        _chk(lib().ef_register_cloud_dev(self.h, args[0], args[1], n, C.byref(params), pT, _ptr(T), C.byref(res), args[2], args[3]),
              self.h)
         return T.reshape(4, 4), self._registerResult(res)
 
@@ -1160,7 +1152,7 @@ class ElasticFusion:
         cap = self.lastCount() if max_rows is None else int(max_rows)
         rows = np.zeros(max(cap, 1), np.uint32)
         total = c_u32(0)
-        _chk(lib().ef_map_select(self.h, C.byref(sel), _ptr(rows) if cap else None, c_u32(cap), C.byref(total)), self.h)
+        _chk(lib().ef_map_select(self.h, C.byref(sel), _ptr(rows) if cap else None, cap, C.byref(total)), self.h)
         out = rows[:min(cap, total.value)].copy()
         return (out, total.value) if count else out
 
@@ -1168,26 +1160,26 @@ class ElasticFusion:
         """the number of selected rows (ef_map_select without a list)"""
         sel = self._selection(sel, kw)
         total = c_u32(0)
-        _chk(lib().ef_map_select(self.h, C.byref(sel), None, c_u32(0), C.byref(total)), self.h)
+        _chk(lib().ef_map_select(self.h, C.byref(sel), None, 0, C.byref(total)), self.h)
         return total.value
 
     def selectSurfelsDevice(self, sel: ef_map_selection, rows_dev, max_rows: int, count_dev):
         """ef_map_select_dev: raw device pointers (int, c_void_p or None for rows with max_rows 0), enqueued on the context's stream"""
-        args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (rows_dev, count_dev)]
-        _chk(lib().ef_map_select_dev(self.h, C.byref(sel), args[0], c_u32(int(max_rows)), args[1]), self.h)
+        args = [_dev(v) for v in (rows_dev, count_dev)]
+        _chk(lib().ef_map_select_dev(self.h, C.byref(sel), args[0], int(max_rows), args[1]), self.h)
 
     def gatherSurfels(self, rows) -> np.ndarray:
         """downloadMap()[rows] without the download: n x 12 float32 in the order of rows (duplicates allowed; a row past the map gives zeros)"""
         rows = np.ascontiguousarray(rows, np.uint32).reshape(-1)
         n = len(rows)
         out = np.zeros((max(n, 1), 12), np.float32)
-        _chk(lib().ef_map_gather(self.h, _ptr(rows) if n else None, c_u32(n), _ptr(out)), self.h)
+        _chk(lib().ef_map_gather(self.h, _ptr(rows) if n else None, n, _ptr(out)), self.h)
         return out[:n].copy()
 
     def gatherSurfelsDevice(self, rows_dev, n: int, surfels_dev):
         """ef_map_gather_dev: raw device pointers (int or c_void_p), enqueued on the context's stream"""
-        args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (rows_dev, surfels_dev)]
-        _chk(lib().ef_map_gather_dev(self.h, args[0], c_u32(int(n)), args[1]), self.h)
+        args = [_dev(v) for v in (rows_dev, surfels_dev)]
+        _chk(lib().ef_map_gather_dev(self.h, args[0], int(n), args[1]), self.h)
 
     def eraseSurfels(self, sel: ef_map_selection | None = None, **kw) -> int:
         """removes the selected surfels from the map (stable; the prediction is renewed once frames have run); returns how many went"""
@@ -1200,14 +1192,13 @@ class ElasticFusion:
         """removes the named rows of downloadMap() (any order; duplicates and rows past the map are ignored); returns how many went"""
         rows = np.ascontiguousarray(rows, np.uint32).reshape(-1)
         removed = c_u32(0)
-        _chk(lib().ef_map_erase_rows(self.h, _ptr(rows) if len(rows) else None, c_u32(len(rows)), C.byref(removed)), self.h)
+        _chk(lib().ef_map_erase_rows(self.h, _ptr(rows) if len(rows) else None, len(rows), C.byref(removed)), self.h)
         return removed.value
 
     def eraseRowsDevice(self, rows_dev, n: int) -> int:
         """ef_map_erase_rows_dev: a raw device pointer (int or c_void_p) to n uint32 rows; synchronises like every erase"""
         removed = c_u32(0)
-        p = None if rows_dev is None else P(int(rows_dev.value if isinstance(rows_dev, P) else rows_dev))
-        _chk(lib().ef_map_erase_rows_dev(self.h, p, c_u32(int(n)), C.byref(removed)), self.h)
+        _chk(lib().ef_map_erase_rows_dev(self.h, _dev(rows_dev), int(n), C.byref(removed)), self.h)
         return removed.value
 
     # --- insert surfels (ef_map_insert) ---
@@ -1237,13 +1228,13 @@ class ElasticFusion:
             n = surfels.nbytes // 48 if n is None else int(n)
             assert n * 48 <= surfels.nbytes, (n, surfels.nbytes)
             devs = [DevBuf(max(n, 1) * np.dtype(t).itemsize) for t, _ in kinds] if rows else [None] * len(kinds)
-            rc = fn_dev(self.h, surfels.p if n else None, c_u32(n), pT, C.byref(params), C.byref(res), *[d.p if rows else None for d in devs])
+            rc = fn_dev(self.h, surfels.p if n else None, n, pT, C.byref(params), C.byref(res), *[d.p if rows else None for d in devs])
             arrays = [d.to_array(t, (n,)) if rows and rc == 0 else None for d, (t, _) in zip(devs, kinds)]
         else:
             rec = np.ascontiguousarray(surfels, np.float32).reshape(-1, 12)
             n = len(rec)
             arrays = [np.full(max(n, 1), fill, t) if rows else None for t, fill in kinds]
-            rc = fn_host(self.h, _ptr(rec) if n else None, c_u32(n), pT, C.byref(params), C.byref(res), *[_ptr(a) if rows else None for a in arrays])
+            rc = fn_host(self.h, _ptr(rec) if n else None, n, pT, C.byref(params), C.byref(res), *[_ptr(a) if rows else None for a in arrays])
             if rows:
                 arrays = [a[:n] for a in arrays]
         out = {k: int(getattr(res, k)) for k, _ in result_type._fields_}
@@ -1298,16 +1289,16 @@ class ElasticFusion:
         rows = np.zeros(max(cap, 1), np.uint32)
         total = c_u32(0)
         what = THIN_ROWS_REPRESENTATIVES if representatives else THIN_ROWS_REMOVED
-        _chk(lib().ef_map_thin_select(self.h, C.byref(params), pa, c_i(what), _ptr(rows) if cap else None, c_u32(cap), C.byref(total)), self.h)
+        _chk(lib().ef_map_thin_select(self.h, C.byref(params), pa, what, _ptr(rows) if cap else None, cap, C.byref(total)), self.h)
         out = rows[:min(cap, total.value)].copy()
         return (out, total.value) if count else out
 
     def thinSelectDevice(self, params: ef_thin_params, among, representatives: bool, rows_dev, max_rows: int, count_dev):
         """ef_map_thin_select_dev: raw device pointers (int, c_void_p or None for rows with max_rows 0), enqueued on the context's stream"""
         params, among, pa = self._thinArgs(params, among, {})
-        args = [None if v is None else P(int(v.value if isinstance(v, P) else v)) for v in (rows_dev, count_dev)]
+        args = [_dev(v) for v in (rows_dev, count_dev)]
         what = THIN_ROWS_REPRESENTATIVES if representatives else THIN_ROWS_REMOVED
-        _chk(lib().ef_map_thin_select_dev(self.h, C.byref(params), pa, c_i(what), args[0], c_u32(int(max_rows)), args[1]), self.h)
+        _chk(lib().ef_map_thin_select_dev(self.h, C.byref(params), pa, what, args[0], int(max_rows), args[1]), self.h)
 
     def thinSurfels(self, params: ef_thin_params | None = None, among=None, **kw) -> dict:
         """removes every participant that is not the representative of its cell (ef_map_thin: what eraseRows(thinSelect(...)) leaves):
@@ -1340,7 +1331,7 @@ class ElasticFusion:
             keep = np.ascontiguousarray(depths, np.uint16).reshape(-1, params.height, params.width)
             assert len(keep) == len(T), (keep.shape, T.shape)
             dp = _ptr(keep)
-        views = ef_carve_views(len(T), C.cast(_ptr(T), C.c_void_p), C.cast(dp, C.c_void_p))
+        views = ef_carve_views(len(T), _ptr(T), dp)
         if isinstance(among, dict):
             among = self.mapSelection(**among)
         return params, views, (C.byref(among) if among is not None else None), (T, keep, among)
@@ -1358,7 +1349,7 @@ class ElasticFusion:
         rows = np.zeros(max(cap, 1), np.uint32)
         v2 = np.zeros((max(n, 1), 2), np.uint8) if votes else None
         total = c_u32(0)
-        _chk(lib().ef_map_carve_select(self.h, C.byref(params), C.byref(views), pa, _ptr(rows) if cap else None, c_u32(cap), C.byref(total),
+        _chk(lib().ef_map_carve_select(self.h, C.byref(params), C.byref(views), pa, _ptr(rows) if cap else None, cap, C.byref(total),
                                        _ptr(v2) if votes else None), self.h)
         out = (rows[:min(cap, total.value)].copy(),) + ((total.value,) if count else ()) + ((v2[:n],) if votes else ())
         return out if len(out) > 1 else out[0]
@@ -1369,10 +1360,9 @@ class ElasticFusion:
         T = np.ascontiguousarray(poses, np.float64).reshape(-1, 16)
         if isinstance(among, dict):
             among = self.mapSelection(**among)
-        args = [None if v is None else int(v.value if isinstance(v, P) else v) for v in (depths_dev, rows_dev, count_dev, votes_dev)]
-        views = ef_carve_views(len(T), C.cast(_ptr(T), C.c_void_p), C.c_void_p(args[0]))
+        views = ef_carve_views(len(T), _ptr(T), _dev(depths_dev))
         _chk(lib().ef_map_carve_select_dev(self.h, C.byref(params), C.byref(views), C.byref(among) if among is not None else None,
-                                           P(args[1]), c_u32(int(max_rows)), P(args[2]), P(args[3])), self.h)
+                                           _dev(rows_dev), int(max_rows), _dev(count_dev), _dev(votes_dev)), self.h)
 
     def carveSurfels(self, depths, poses=None, params: ef_carve_params | None = None, among=None, **kw) -> dict:
         """removes the surfels the views see through (ef_map_carve; depths a DevBuf: ef_map_carve_dev): what eraseRows(carveSelect(...))
@@ -1385,11 +1375,11 @@ class ElasticFusion:
 
     def setReferenceDownload(self, on=True):
         """downloadMap / savePly read what GlobalModel::downloadMap reads (the pre-clean buffer, quirk Q14) instead of model()"""
-        _chk(lib().ef_set_reference_download(self.h, c_i(int(on))), self.h)
+        _chk(lib().ef_set_reference_download(self.h, int(on)), self.h)
 
     def uploadMap(self, surfels: np.ndarray):
         s = np.ascontiguousarray(surfels, np.float32).reshape(-1, 12)
-        _chk(lib().ef_map_upload(self.h, _ptr(s), c_u32(len(s))), self.h)
+        _chk(lib().ef_map_upload(self.h, _ptr(s), len(s)), self.h)
 
     def getPoseQT(self) -> np.ndarray:
         """T_wc as the engine holds it: unit quaternion x y z w + translation (7 doubles), no matrix round trip (ef_get_pose_qt)"""
@@ -1406,7 +1396,7 @@ class ElasticFusion:
         """resume from ``checkpoint()`` in a fresh context (ef_map_upload + ef_restore_state): the next processFrame continues the replay"""
         self.uploadMap(ck["map"])
         qt = np.ascontiguousarray(ck["qt"], np.float64).reshape(7)
-        _chk(lib().ef_restore_state(self.h, c_i(int(ck["tick"])), _ptr(qt), _ptr(ck["rgb"]), _ptr(ck["depth"])), self.h)
+        _chk(lib().ef_restore_state(self.h, int(ck["tick"]), _ptr(qt), _ptr(ck["rgb"]), _ptr(ck["depth"])), self.h)
 
     def savePly(self, path: str):
         _chk(lib().ef_save_ply(self.h, path.encode()), self.h)
@@ -1414,27 +1404,27 @@ class ElasticFusion:
     def saveFreiburg(self, path: str):
         _chk(lib().ef_save_freiburg(self.h, path.encode()), self.h)
 
-    def setRgbOnly(self, v): _chk(lib().ef_set_rgb_only(self.h, c_i(int(v))), self.h)
-    def setIcpWeight(self, v): _chk(lib().ef_set_icp_weight(self.h, c_f(v)), self.h)
-    def setPyramid(self, v): _chk(lib().ef_set_pyramid(self.h, c_i(int(v))), self.h)
-    def setFastOdom(self, v): _chk(lib().ef_set_fast_odom(self.h, c_i(int(v))), self.h)
-    def setSo3(self, v): _chk(lib().ef_set_so3(self.h, c_i(int(v))), self.h)
-    def setFrameToFrameRGB(self, v): _chk(lib().ef_set_frame_to_frame_rgb(self.h, c_i(int(v))), self.h)
-    def setConfidenceThreshold(self, v): _chk(lib().ef_set_confidence_threshold(self.h, c_f(v)), self.h)
-    def setDepthCutoff(self, v): _chk(lib().ef_set_depth_cutoff(self.h, c_f(v)), self.h)
-    def setInputOverlap(self, on): _chk(lib().ef_set_input_overlap(self.h, c_i(int(on))), self.h)
-    def setInputCuMask(self, one_in_n): _chk(lib().ef_set_input_cu_mask(self.h, c_i(int(one_in_n))), self.h)
+    def setRgbOnly(self, v): _chk(lib().ef_set_rgb_only(self.h, int(v)), self.h)
+    def setIcpWeight(self, v): _chk(lib().ef_set_icp_weight(self.h, v), self.h)
+    def setPyramid(self, v): _chk(lib().ef_set_pyramid(self.h, int(v)), self.h)
+    def setFastOdom(self, v): _chk(lib().ef_set_fast_odom(self.h, int(v)), self.h)
+    def setSo3(self, v): _chk(lib().ef_set_so3(self.h, int(v)), self.h)
+    def setFrameToFrameRGB(self, v): _chk(lib().ef_set_frame_to_frame_rgb(self.h, int(v)), self.h)
+    def setConfidenceThreshold(self, v): _chk(lib().ef_set_confidence_threshold(self.h, v), self.h)
+    def setDepthCutoff(self, v): _chk(lib().ef_set_depth_cutoff(self.h, v), self.h)
+    def setInputOverlap(self, on): _chk(lib().ef_set_input_overlap(self.h, int(on)), self.h)
+    def setInputCuMask(self, one_in_n): _chk(lib().ef_set_input_cu_mask(self.h, int(one_in_n)), self.h)
     def setDeformation(self, graph, isFern=False):
         g = np.ascontiguousarray(graph, np.float32).reshape(-1, 16)
-        _chk(lib().ef_set_deformation(self.h, _ptr(g), c_i(len(g)), c_i(int(isFern))), self.h)
+        _chk(lib().ef_set_deformation(self.h, _ptr(g), len(g), int(isFern)), self.h)
 
-    def setGraphReplay(self, on): _chk(lib().ef_set_graph_replay(self.h, c_i(int(on))), self.h)
+    def setGraphReplay(self, on): _chk(lib().ef_set_graph_replay(self.h, int(on)), self.h)
 
     def image(self, name: str) -> np.ndarray:
         which, dt, ch = self.IMAGES[name]
         W, H = self.cfg.width, self.cfg.height
         out = np.zeros((H, W, ch) if ch > 1 else (H, W), dt)
-        _chk(lib().ef_get_image(self.h, c_i(which), _ptr(out), C.c_size_t(out.nbytes)), self.h)
+        _chk(lib().ef_get_image(self.h, which, _ptr(out), out.nbytes), self.h)
         return out
 
     def trackerBuffer(self, name: str, level: int = 0, tracker: int = 0) -> np.ndarray:
@@ -1442,16 +1432,16 @@ class ElasticFusion:
         which, dt, planes = self.TRACKER[name]
         w, h = self.cfg.width >> level, self.cfg.height >> level
         out = np.zeros((h * planes, w), dt)
-        _chk(lib().ef_get_tracker_buffer_of(self.h, c_i(tracker), c_i(which), c_i(level), _ptr(out), C.c_size_t(out.nbytes)), self.h)
+        _chk(lib().ef_get_tracker_buffer_of(self.h, tracker, which, level, _ptr(out), out.nbytes), self.h)
         return out
 
     def enableTiming(self, on=True):
-        _chk(lib().ef_enable_timing(self.h, c_i(int(on))), self.h)
+        _chk(lib().ef_enable_timing(self.h, int(on)), self.h)
 
     def timings(self) -> dict:
         arr = (ef_timing * 32)()
         n = c_i(0)
-        _chk(lib().ef_get_timings(self.h, arr, c_i(32), C.byref(n)), self.h)
+        _chk(lib().ef_get_timings(self.h, arr, 32, C.byref(n)), self.h)
         return {arr[i].name.decode(): arr[i].ms for i in range(n.value)}
 
 
@@ -1464,11 +1454,18 @@ class ops:
         return np.ascontiguousarray(a, np.float32)
 
     @staticmethod
+    def _image_op(name, src, dtype, scale, *scalars):
+        """the single-image operators: src (H x W [x C]) uploaded, ef_op_<name>(src, W, H, *scalars, dst, stream 0) run, dst (H / scale x
+        W / scale of dtype) downloaded"""
+        h, w = src.shape[:2]
+        shape = (h // scale, w // scale)
+        s, d = DevBuf.from_array(src), DevBuf(shape[0] * shape[1] * np.dtype(dtype).itemsize)
+        _chk(getattr(lib(), "ef_op_" + name)(s.p, w, h, *scalars, d.p, None))
+        return d.to_array(dtype, shape)
+
+    @staticmethod
     def pyr_down(src):
-        h, w = src.shape
-        s, d = DevBuf.from_array(src), DevBuf((h // 2) * (w // 2) * 2)
-        _chk(lib().ef_op_pyr_down(s.p, c_i(w), c_i(h), d.p, None))
-        return d.to_array(np.uint16, (h // 2, w // 2))
+        return ops._image_op("pyr_down", src, np.uint16, 2)
 
     @staticmethod
     def create_vmap(depth, fx, fy, cx, cy, cutoff, init=None):
@@ -1476,7 +1473,7 @@ class ops:
         d = DevBuf.from_array(depth)
         v = DevBuf.from_array(np.zeros((3 * h, w), np.float32) if init is None else init)
         k = ef_intr(fx, fy, cx, cy)
-        _chk(lib().ef_op_create_vmap(C.byref(k), d.p, c_i(w), c_i(h), c_f(cutoff), v.p, None))
+        _chk(lib().ef_op_create_vmap(C.byref(k), d.p, w, h, cutoff, v.p, None))
         return v.to_array(np.float32, (3 * h, w))
 
     @staticmethod
@@ -1484,7 +1481,7 @@ class ops:
         h3, w = vmap.shape
         v = DevBuf.from_array(vmap)
         n = DevBuf.from_array(np.zeros((h3, w), np.float32) if init is None else init)
-        _chk(lib().ef_op_create_nmap(v.p, c_i(w), c_i(h3 // 3), n.p, None))
+        _chk(lib().ef_op_create_nmap(v.p, w, h3 // 3, n.p, None))
         return n.to_array(np.float32, (h3, w))
 
     @staticmethod
@@ -1492,7 +1489,7 @@ class ops:
         h3, w = vmap.shape
         v, n = DevBuf.from_array(vmap), DevBuf.from_array(nmap)
         R9, t3 = ops._f32(R).reshape(9), ops._f32(t).reshape(3)
-        _chk(lib().ef_op_transform_maps(v.p, n.p, c_i(w), c_i(h3 // 3), _ptr(R9), _ptr(t3), v.p, n.p, None))
+        _chk(lib().ef_op_transform_maps(v.p, n.p, w, h3 // 3, _ptr(R9), _ptr(t3), v.p, n.p, None))
         return v.to_array(np.float32, (h3, w)), n.to_array(np.float32, (h3, w))
 
     @staticmethod
@@ -1500,7 +1497,7 @@ class ops:
         h, w, _ = vtex.shape
         v4, n4 = DevBuf.from_array(ops._f32(vtex)), DevBuf.from_array(ops._f32(ntex))
         tmp, vm, nm = DevBuf(h * w * 16), DevBuf(h * w * 12), DevBuf(h * w * 12)
-        _chk(lib().ef_op_copy_maps(v4.p, n4.p, c_i(w), c_i(h), tmp.p, vm.p, nm.p, None))
+        _chk(lib().ef_op_copy_maps(v4.p, n4.p, w, h, tmp.p, vm.p, nm.p, None))
         return tmp.to_array(np.float32, (h, w, 4)), vm.to_array(np.float32, (3 * h, w)), nm.to_array(np.float32, (3 * h, w))
 
     @staticmethod
@@ -1509,42 +1506,30 @@ class ops:
         s = DevBuf.from_array(src)
         o = DevBuf.from_array(np.zeros((h3 // 2, w // 2), np.float32) if init is None else init)
         fn = lib().ef_op_resize_nmap if normalize else lib().ef_op_resize_vmap
-        _chk(fn(s.p, c_i(w), c_i(h3 // 3), o.p, None))
+        _chk(fn(s.p, w, h3 // 3, o.p, None))
         return o.to_array(np.float32, (h3 // 2, w // 2))
 
     @staticmethod
     def pyr_down_gauss_f(src):
-        h, w = src.shape
-        s, d = DevBuf.from_array(src), DevBuf((h // 2) * (w // 2) * 4)
-        _chk(lib().ef_op_pyr_down_gauss_f(s.p, c_i(w), c_i(h), d.p, None))
-        return d.to_array(np.float32, (h // 2, w // 2))
+        return ops._image_op("pyr_down_gauss_f", src, np.float32, 2)
 
     @staticmethod
     def pyr_down_uchar_gauss(src):
-        h, w = src.shape
-        s, d = DevBuf.from_array(src), DevBuf((h // 2) * (w // 2))
-        _chk(lib().ef_op_pyr_down_uchar_gauss(s.p, c_i(w), c_i(h), d.p, None))
-        return d.to_array(np.uint8, (h // 2, w // 2))
+        return ops._image_op("pyr_down_uchar_gauss", src, np.uint8, 2)
 
     @staticmethod
     def vertices_to_depth(vmaps_tmp, cutoff):
-        h, w, _ = vmaps_tmp.shape
-        s, d = DevBuf.from_array(ops._f32(vmaps_tmp)), DevBuf(h * w * 4)
-        _chk(lib().ef_op_vertices_to_depth(s.p, c_i(w), c_i(h), c_f(cutoff), d.p, None))
-        return d.to_array(np.float32, (h, w))
+        return ops._image_op("vertices_to_depth", ops._f32(vmaps_tmp), np.float32, 1, cutoff)
 
     @staticmethod
     def bgr_to_intensity(rgba):
-        h, w, _ = rgba.shape
-        s, d = DevBuf.from_array(rgba), DevBuf(h * w)
-        _chk(lib().ef_op_image_bgr_to_intensity(s.p, c_i(w), c_i(h), d.p, None))
-        return d.to_array(np.uint8, (h, w))
+        return ops._image_op("image_bgr_to_intensity", rgba, np.uint8, 1)
 
     @staticmethod
     def derivative_images(img):
         h, w = img.shape
         s, dx, dy = DevBuf.from_array(img), DevBuf(h * w * 2), DevBuf(h * w * 2)
-        _chk(lib().ef_op_compute_derivative_images(s.p, c_i(w), c_i(h), dx.p, dy.p, None))
+        _chk(lib().ef_op_compute_derivative_images(s.p, w, h, dx.p, dy.p, None))
         return dx.to_array(np.int16, (h, w)), dy.to_array(np.int16, (h, w))
 
     @staticmethod
@@ -1552,7 +1537,7 @@ class ops:
         h, w = depth.shape
         s, d = DevBuf.from_array(depth), DevBuf(h * w * 12)
         k = ef_intr(fx, fy, cx, cy)
-        _chk(lib().ef_op_project_to_point_cloud(s.p, c_i(w), c_i(h), C.byref(k), c_i(level), d.p, None))
+        _chk(lib().ef_op_project_to_point_cloud(s.p, w, h, C.byref(k), level, d.p, None))
         return d.to_array(np.float32, (h, w, 3))
 
     @staticmethod
@@ -1563,7 +1548,7 @@ class ops:
         k = ef_intr(*intr)
         _chk(lib().ef_op_icp_step(_ptr(ops._f32(Rcurr).reshape(9)), _ptr(ops._f32(tcurr)), bufs[0].p, bufs[1].p,
                                   _ptr(ops._f32(Rprev_inv).reshape(9)), _ptr(ops._f32(tprev)), C.byref(k), bufs[2].p, bufs[3].p,
-                                  c_f(distThres), c_f(angleThres), c_i(w), c_i(h3 // 3), _ptr(A), _ptr(b), _ptr(res), None))
+                                  distThres, angleThres, w, h3 // 3, _ptr(A), _ptr(b), _ptr(res), None))
         return A, b, res
 
     @staticmethod
@@ -1572,8 +1557,8 @@ class ops:
         bufs = [DevBuf.from_array(a) for a in (dIdx, dIdy, lastDepth, nextDepth, lastImage, nextImage)]
         corres = DevBuf(h * w * 16)
         sigma, count = c_i(0), c_i(0)
-        _chk(lib().ef_op_compute_rgb_residual(c_f(minScale), bufs[0].p, bufs[1].p, bufs[2].p, bufs[3].p, bufs[4].p, bufs[5].p, corres.p,
-                                              c_f(maxDepthDelta), _ptr(ops._f32(kt)), _ptr(ops._f32(krkinv).reshape(9)), c_i(w), c_i(h),
+        _chk(lib().ef_op_compute_rgb_residual(minScale, bufs[0].p, bufs[1].p, bufs[2].p, bufs[3].p, bufs[4].p, bufs[5].p, corres.p,
+                                              maxDepthDelta, _ptr(ops._f32(kt)), _ptr(ops._f32(krkinv).reshape(9)), w, h,
                                               C.byref(sigma), C.byref(count), None))
         return corres.to_array(DATATERM, (h, w)), sigma.value, count.value
 
@@ -1582,7 +1567,7 @@ class ops:
         h, w = corres.shape
         bufs = [DevBuf.from_array(a) for a in (corres, ops._f32(cloud), dIdx, dIdy)]
         A, b = np.zeros((6, 6), np.float32), np.zeros(6, np.float32)
-        _chk(lib().ef_op_rgb_step(bufs[0].p, c_f(sigma), bufs[1].p, c_f(fx), c_f(fy), bufs[2].p, bufs[3].p, c_f(sobelScale), c_i(w), c_i(h),
+        _chk(lib().ef_op_rgb_step(bufs[0].p, sigma, bufs[1].p, fx, fy, bufs[2].p, bufs[3].p, sobelScale, w, h,
                                   _ptr(A), _ptr(b), None))
         return A, b
 
@@ -1592,7 +1577,7 @@ class ops:
         li, ni = DevBuf.from_array(lastImage), DevBuf.from_array(nextImage)
         A, b, res = np.zeros((3, 3), np.float32), np.zeros(3, np.float32), np.zeros(2, np.float32)
         _chk(lib().ef_op_so3_step(li.p, ni.p, _ptr(ops._f32(imageBasis).reshape(9)), _ptr(ops._f32(kinv).reshape(9)),
-                                  _ptr(ops._f32(krlr).reshape(9)), c_i(w), c_i(h), _ptr(A), _ptr(b), _ptr(res), None))
+                                  _ptr(ops._f32(krlr).reshape(9)), w, h, _ptr(A), _ptr(b), _ptr(res), None))
         return A, b, res
 
     @staticmethod
@@ -1654,7 +1639,7 @@ class ops:
         # (outputs start from a pattern no result can be mistaken for: 0xA5 bytes)
         outs = [[DevBuf((h >> l) * (w >> l) * sz, fill=0xA5) for l in range(3)] for sz in (2, 2, 1, 4)]
         arr = lambda bufs: (P * 3)(*[b.p for b in bufs])
-        _chk(lib().ef_op_sobel_mask(arr(img), arr(dep), c_i(w), c_i(h), arr(outs[0]), arr(outs[1]), arr(outs[2]), arr(outs[3]), None))
+        _chk(lib().ef_op_sobel_mask(arr(img), arr(dep), w, h, arr(outs[0]), arr(outs[1]), arr(outs[2]), arr(outs[3]), None))
         return tuple([b.to_array(dt, (h >> l, w >> l)) for l, b in enumerate(bufs)] for bufs, dt in zip(outs, (np.int16, np.int16, np.uint8, np.uint32)))
 
     @staticmethod
@@ -1666,9 +1651,9 @@ class ops:
         sb, nb = DevBuf.from_array(s), DevBuf.from_array(nu if len(nu) else np.zeros((1, 12), np.float32))
         out = DevBuf((len(s) + len(nu) + 1) * 48)
         n = c_u32(0)
-        _chk(lib().ef_op_clean_deform(C.byref(cam), _ptr(ops._T(T_wc)), c_i(time), bufs[0].p, bufs[1].p, bufs[2].p, bufs[3].p,
-                                      c_f(confThreshold), c_i(timeDelta), c_f(maxDepth), sb.p, c_u32(len(s)), nb.p, c_u32(len(nu)),
-                                      bufs[4].p, c_i(len(g)), bufs[5].p, c_i(int(isFern)), out.p, C.byref(n), None))
+        _chk(lib().ef_op_clean_deform(C.byref(cam), _ptr(ops._T(T_wc)), time, bufs[0].p, bufs[1].p, bufs[2].p, bufs[3].p,
+                                      confThreshold, timeDelta, maxDepth, sb.p, len(s), nb.p, len(nu),
+                                      bufs[4].p, len(g), bufs[5].p, int(isFern), out.p, C.byref(n), None))
         return out.to_array(np.float32, (n.value, 12))
 
     LINALG = dict(ldlt6=0, ldlt3f=1, polar3=2, rodrigues=3, se3_inverse=4, se3_log_norm=5, scalar=6, ldlt6_wave=7, ldlt6_every_lane=8,
@@ -1679,7 +1664,7 @@ class ops:
         """The driver's Eigen/Sophus arithmetic as the device evaluates it (ef_op_linalg)."""
         v = np.ascontiguousarray(np.asarray(vec, np.float64).reshape(-1))
         out = np.zeros(n_out, np.float64)
-        _chk(lib().ef_op_linalg(c_i(ops.LINALG[which]), _ptr(v), c_i(v.size), _ptr(out), c_i(n_out)))
+        _chk(lib().ef_op_linalg(ops.LINALG[which], _ptr(v), v.size, _ptr(out), n_out))
         return out
 
     GN_STATE = ("Rcurr", "tcurr", "resultRt", "krkinv", "kt", "lastRGBErrorLevel", "rgb_broken")
@@ -1716,24 +1701,18 @@ class ops:
         qp = np.ascontiguousarray(np.asarray(q_prev, np.float64).reshape(4))
         tp = np.ascontiguousarray(np.asarray(t_prev, np.float64).reshape(3))
         _chk(lib().ef_op_track_end_tail(_ptr(ops._f32(Rcurr).reshape(9)), _ptr(ops._f32(tcurr).reshape(3)), _ptr(ops._f32(Rprev).reshape(9)),
-                                        _ptr(ops._f32(tprev).reshape(3)), _ptr(qp), _ptr(tp), c_i(int(rgb)), c_f(weightMultiplier), C.byref(o)))
+                                        _ptr(ops._f32(tprev).reshape(3)), _ptr(qp), _ptr(tp), int(rgb), weightMultiplier, C.byref(o)))
         out = {n: np.array(getattr(o, n)) for n in ("q", "t", "logged", "T_cw", "pose_f", "R_wc_f", "t_wc_f")}
         out["weighting"] = np.float32(o.weighting)
         return out
 
     @staticmethod
     def filter_depth(raw, maxD):
-        h, w = raw.shape
-        s, d = DevBuf.from_array(raw), DevBuf(h * w * 2)
-        _chk(lib().ef_op_filter_depth(s.p, c_i(w), c_i(h), c_f(maxD), d.p, None))
-        return d.to_array(np.uint16, (h, w))
+        return ops._image_op("filter_depth", raw, np.uint16, 1, maxD)
 
     @staticmethod
     def metricise_depth(d_in, maxD):
-        h, w = d_in.shape
-        s, d = DevBuf.from_array(d_in), DevBuf(h * w * 4)
-        _chk(lib().ef_op_metricise_depth(s.p, c_i(w), c_i(h), c_f(maxD), d.p, None))
-        return d.to_array(np.float32, (h, w))
+        return ops._image_op("metricise_depth", d_in, np.float32, 1, maxD)
 
     @staticmethod
     def seed_map(cam, rgb, dm, dmf, time, maxDepth):
@@ -1741,7 +1720,7 @@ class ops:
         bufs = [DevBuf.from_array(a) for a in (rgb, dm, dmf)]
         out = DevBuf(Pn * 48)
         n = c_u32(0)
-        _chk(lib().ef_op_seed_map(C.byref(cam), bufs[0].p, bufs[1].p, bufs[2].p, c_i(time), c_f(maxDepth), out.p, C.byref(n), None))
+        _chk(lib().ef_op_seed_map(C.byref(cam), bufs[0].p, bufs[1].p, bufs[2].p, time, maxDepth, out.p, C.byref(n), None))
         return out.to_array(np.float32, (n.value, 12))
 
     @staticmethod
@@ -1754,7 +1733,7 @@ class ops:
         Pn = cam.cols * cam.rows
         sb = DevBuf.from_array(s)
         idx, vc, ct, nr = DevBuf(Pn * 4), DevBuf(Pn * 16), DevBuf(Pn * 16), DevBuf(Pn * 16)
-        _chk(lib().ef_op_predict_indices(C.byref(cam), _ptr(ops._T(T_wc)), c_i(time), sb.p, c_u32(len(s)), c_f(maxDepth), c_i(timeDelta),
+        _chk(lib().ef_op_predict_indices(C.byref(cam), _ptr(ops._T(T_wc)), time, sb.p, len(s), maxDepth, timeDelta,
                                          idx.p, vc.p, ct.p, nr.p, None))
         shp = (cam.rows, cam.cols)
         return (idx.to_array(np.uint32, shp), vc.to_array(np.float32, shp + (4,)), ct.to_array(np.float32, shp + (4,)),
@@ -1766,8 +1745,8 @@ class ops:
         Pn = cam.cols * cam.rows
         sb = DevBuf.from_array(s)
         img, vt, nm, tm = DevBuf(Pn * 4), DevBuf(Pn * 16), DevBuf(Pn * 16), DevBuf(Pn * 2)
-        _chk(lib().ef_op_combined_predict(C.byref(cam), _ptr(ops._T(T_wc)), sb.p, c_u32(len(s)), c_f(maxDepth), c_f(confThreshold),
-                                          c_i(time), c_i(maxTime), c_i(timeDelta), img.p, vt.p, nm.p, tm.p, None))
+        _chk(lib().ef_op_combined_predict(C.byref(cam), _ptr(ops._T(T_wc)), sb.p, len(s), maxDepth, confThreshold,
+                                          time, maxTime, timeDelta, img.p, vt.p, nm.p, tm.p, None))
         shp = (cam.rows, cam.cols)
         return (img.to_array(np.uint8, shp + (4,)), vt.to_array(np.float32, shp + (4,)), nm.to_array(np.float32, shp + (4,)),
                 tm.to_array(np.uint16, shp))
@@ -1777,8 +1756,8 @@ class ops:
         s = ops._f32(surfels).reshape(-1, 12)
         Pn = cam.cols * cam.rows
         sb, d = DevBuf.from_array(s), DevBuf(Pn * 4)
-        _chk(lib().ef_op_synthesize_depth(C.byref(cam), _ptr(ops._T(T_wc)), sb.p, c_u32(len(s)), c_f(maxDepth), c_f(confThreshold),
-                                          c_i(time), c_i(maxTime), c_i(timeDelta), d.p, None))
+        _chk(lib().ef_op_synthesize_depth(C.byref(cam), _ptr(ops._T(T_wc)), sb.p, len(s), maxDepth, confThreshold,
+                                          time, maxTime, timeDelta, d.p, None))
         return d.to_array(np.float32, (cam.rows, cam.cols))
 
     @staticmethod
@@ -1786,7 +1765,7 @@ class ops:
         bufs = [DevBuf.from_array(a) for a in (image, ops._f32(vertex), ops._f32(normal), depthFiltered, rgb)]
         Pn = cam.cols * cam.rows
         fi, fv, fn = DevBuf(Pn * 4), DevBuf(Pn * 16), DevBuf(Pn * 16)
-        _chk(lib().ef_op_fill_in(C.byref(cam), bufs[0].p, bufs[1].p, bufs[2].p, bufs[3].p, bufs[4].p, c_i(passthrough), c_i(passthroughImage),
+        _chk(lib().ef_op_fill_in(C.byref(cam), bufs[0].p, bufs[1].p, bufs[2].p, bufs[3].p, bufs[4].p, passthrough, passthroughImage,
                                  fi.p, fv.p, fn.p, None))
         shp = (cam.rows, cam.cols)
         return fi.to_array(np.uint8, shp + (4,)), fv.to_array(np.float32, shp + (4,)), fn.to_array(np.float32, shp + (4,))
@@ -1805,8 +1784,8 @@ class ops:
         sb = DevBuf.from_array(s)
         nu = DevBuf((cam.cols // 2) * (cam.rows // 2) * 48)
         n = c_u32(0)
-        _chk(lib().ef_op_fuse(C.byref(cam), _ptr(ops._T(T_wc)), c_i(time), bufs[0].p, bufs[1].p, bufs[2].p, bufs[3].p, bufs[4].p, bufs[5].p,
-                              bufs[6].p, c_f(maxDepth), c_f(weighting), sb.p, c_u32(len(s)), nu.p, C.byref(n), None))
+        _chk(lib().ef_op_fuse(C.byref(cam), _ptr(ops._T(T_wc)), time, bufs[0].p, bufs[1].p, bufs[2].p, bufs[3].p, bufs[4].p, bufs[5].p,
+                              bufs[6].p, maxDepth, weighting, sb.p, len(s), nu.p, C.byref(n), None))
         return sb.to_array(np.float32, (len(s), 12)), nu.to_array(np.float32, (n.value, 12))
 
     @staticmethod
@@ -1817,6 +1796,6 @@ class ops:
         sb, nb = DevBuf.from_array(s), DevBuf.from_array(nu if len(nu) else np.zeros((1, 12), np.float32))
         out = DevBuf((len(s) + len(nu) + 1) * 48)
         n = c_u32(0)
-        _chk(lib().ef_op_clean(C.byref(cam), _ptr(ops._T(T_wc)), c_i(time), bufs[0].p, bufs[1].p, bufs[2].p, bufs[3].p, c_f(confThreshold),
-                               c_i(timeDelta), c_f(maxDepth), sb.p, c_u32(len(s)), nb.p, c_u32(len(nu)), out.p, C.byref(n), None))
+        _chk(lib().ef_op_clean(C.byref(cam), _ptr(ops._T(T_wc)), time, bufs[0].p, bufs[1].p, bufs[2].p, bufs[3].p, confThreshold,
+                               timeDelta, maxDepth, sb.p, len(s), nb.p, len(nu), out.p, C.byref(n), None))
         return out.to_array(np.float32, (n.value, 12))

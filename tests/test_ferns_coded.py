@@ -35,9 +35,6 @@ def test_coded_entry_points_answer_like_the_compiled_reference():
     f = api.Ferns(500, 3000, 115.0, W, H, FX, FY, CX, CY, seed=int(g["seed"]))
     table = f.conservatory
     assert np.array_equal(table, g["table"])
-    L.ef_ferns_add_frame_coded.argtypes = [P, P, C.c_int, VIEW_FETCH, P, P, C.c_int, C.c_float]
-    L.ef_ferns_find_frame_coded.argtypes = [P, P, C.c_int, VIEW_FETCH, P, P, C.c_int, C.c_int, api.FERN_TRACKER, P, P, P, C.c_int, P]
-    L.ef_ferns_candidate_possible.argtypes = [P, C.c_int]
     ptr = lambda a: a.ctypes.data_as(P)
     fetches = []
 

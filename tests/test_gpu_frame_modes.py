@@ -7,8 +7,6 @@ must leave the same trajectory, map count and map, bit for bit: the modes change
   (d) input overlap 2 on a quarter of the CUs with the persistent tracker on (mode 2 is demoted to mode 1);
   (e) a pose handed in for one middle frame, single-stream against overlapped;
   (f) loop closure with the built-in solver, single-stream against overlapped."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -73,9 +71,7 @@ def test_stage_timers_every_frame(hip, scene, baseline):
 def test_sampled_frames_leave_the_graph_replay(hip, scene, baseline):
     def setup(ef):
         ef.setGraphReplay(True)
-        L = hip.lib()
-        L.ef_kernel_timing.argtypes = [C.c_void_p, C.c_int]
-        hip._chk(L.ef_kernel_timing(ef.h, 2), ef.h)
+        hip._chk(hip.lib().ef_kernel_timing(ef.h, 2), ef.h)
     assert_same(run(hip, scene, setup), baseline)
 
 

@@ -21,18 +21,9 @@ TRACKED = FUSED = FRAMES - 1
 LEVEL0_ITERATIONS = 10          # RGBDOdometry.cpp:371-373, fastOdom off
 
 
-class ef_kernel_time(C.Structure):   # include/ef_hip.h
-    _fields_ = [("name", C.c_char_p), ("avg_us", C.c_float), ("launches", C.c_int), ("bytes_per_launch", C.c_double),
-                ("bytes_per_launch_survey", C.c_double)]
-
-
 @pytest.fixture(scope="module")
 def hip():
     from elasticfusion_amd import api
-    L = api.lib()
-    L.ef_kernel_timing.argtypes = [C.c_void_p, C.c_int]
-    for name in ("ef_get_kernel_timing", "ef_get_tracker_timing", "ef_get_splat_timing"):
-        getattr(L, name).argtypes = [C.c_void_p, C.POINTER(ef_kernel_time)]
     return api
 
 
@@ -56,7 +47,7 @@ def start(hip, scene, persistent, every):
 def sampled(hip, ef):
     out = {}
     for key, fn in (("step", "ef_get_kernel_timing"), ("tracker", "ef_get_tracker_timing"), ("splat", "ef_get_splat_timing")):
-        t = ef_kernel_time()
+        t = hip.ef_kernel_time()
         hip._chk(getattr(hip.lib(), fn)(ef.h, C.byref(t)), ef.h)
         assert t.name
         print(key, t.launches, t.avg_us, t.bytes_per_launch, t.bytes_per_launch_survey)
