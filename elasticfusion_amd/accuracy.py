@@ -108,6 +108,16 @@ def carved_map(ef: "api.ElasticFusion", depths, poses=None, **kw) -> np.ndarray:
     return ef.gatherSurfels(np.nonzero(kept)[0].astype(np.uint32))
 
 
+def without_outliers(ef: "api.ElasticFusion", **params) -> np.ndarray:
+    """ef's map without its outlier surfels, [k, 12] float32 as downloadMap() gives them, without a download of the whole map and without
+    changing it: outlierSelect + gatherSurfels of the other rows (ef_map_outliers_select + ef_map_gather), which is what removeOutliers with
+    the same arguments would leave.  The keywords (params, among, ef_outlier_params fields) as outlierSelect takes them."""
+    removed = ef.outlierSelect(**params)
+    kept = np.ones(ef.lastCount(), bool)
+    kept[removed] = False
+    return ef.gatherSurfels(np.nonzero(kept)[0].astype(np.uint32))
+
+
 def map_accuracy(ef: "api.ElasticFusion", gt_surfels: np.ndarray, max_dist: float = 0.05, map_rows=None, gt_rows=None, device: int = 0,
                  align: bool = False, align_schedule=REGISTER_SCHEDULE) -> dict:
     """ef: a context with a map; gt_surfels: [m, 12] float32, laid out as downloadMap() gives them (synth.sample_surfels), in the map's world

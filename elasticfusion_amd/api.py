@@ -143,7 +143,19 @@ class ef_carve_result(C.Structure):
                 ("count_after", c_u32)]
 
 
+class ef_outlier_params(C.Structure):
+    _fields_ = [("mode", c_i), ("radius", c_f), ("cell", c_f), ("min_conf", c_f), ("min_neighbors", c_i), ("k", c_i), ("std_ratio", c_f),
+                ("max_mean_dist", c_f), ("flag_sparse", c_i)]
+
+
+class ef_outlier_result(C.Structure):
+    _fields_ = [("sum", C.c_double), ("sum_sq", C.c_double), ("participants", c_u32), ("measured", c_u32), ("sparse", c_u32),
+                ("outliers", c_u32), ("count_after", c_u32), ("threshold", c_f)]
+
+
 CARVE_MAX_VIEWS = 32   # EF_CARVE_MAX_VIEWS of include/ef_hip.h
+OUTLIER_RADIUS, OUTLIER_STATISTICAL = 0, 1   # EF_OUTLIER_* of include/ef_hip.h: the two filters
+OUTLIER_SUM_LANES = 4096                     # EF_OUTLIER_SUM_LANES: P of the summation order
 THIN_KEEP_MAX_CONF, THIN_KEEP_NEWEST, THIN_KEEP_FIRST = 0, 1, 2   # EF_THIN_KEEP_* of include/ef_hip.h
 THIN_ROWS_REMOVED, THIN_ROWS_REPRESENTATIVES = 0, 1               # EF_THIN_ROWS_*
 INSERT_KEEP = -1   # EF_INSERT_KEEP of include/ef_hip.h
@@ -1372,6 +1384,71 @@ class ElasticFusion:
         fn = lib().ef_map_carve_dev if isinstance(depths, DevBuf) else lib().ef_map_carve
         _chk(fn(self.h, C.byref(params), C.byref(views), pa, C.byref(res)), self.h)
         return {k: int(getattr(res, k)) for k, _ in ef_carve_result._fields_}
+
+    # --- remove outlier surfels: neighbourhood statistics of the map (ef_map_neighbor_stats / ef_map_outliers_select / ef_map_remove_outliers) ---
+    def outlierParams(self, **kw) -> ef_outlier_params:
+        """ef_default_outlier_params (OUTLIER_STATISTICAL, k 8, std_ratio 2, max_mean_dist 0, flag_sparse 1, radius 0.03, min_neighbors 4,
+        min_conf -1, cell 0.03) with fields replaced by keyword"""
+        return self._params(ef_outlier_params, lib().ef_default_outlier_params, kw, "outlier")
+
+    def _outlierArgs(self, params, among, kw):
+        if params is None:
+            params = self.outlierParams(**kw)
+        else:
+            assert not kw, "give params or keywords, not both"
+        if isinstance(among, dict):
+            among = self.mapSelection(**among)
+        return params, among, (C.byref(among) if among is not None else None)
+
+    @staticmethod
+    def _outlierResult(res: ef_outlier_result) -> dict:
+        return {k: (float if k in ("sum", "sum_sq") else np.float32 if k == "threshold" else int)(getattr(res, k)) for k, _ in ef_outlier_result._fields_}
+
+    def neighborStats(self, params: ef_outlier_params | None = None, among=None, **kw):
+        """(mean_dist float32, count uint32) per row of downloadMap(): the mean distance to the k nearest other surfels within radius (+inf
+        with fewer than k of them, and for a row that takes no part) and the number of ALL of them; the map does not change.  among: an
+        ef_map_selection, a dict of mapSelection keywords or None (every surfel participates); other keywords are ef_outlier_params fields"""
+        params, among, pa = self._outlierArgs(params, among, kw)
+        n = self.lastCount()
+        mean = np.zeros(max(n, 1), np.float32)
+        count = np.zeros(max(n, 1), np.uint32)
+        _chk(lib().ef_map_neighbor_stats(self.h, C.byref(params), pa, _ptr(mean), _ptr(count), n), self.h)
+        return mean[:n], count[:n]
+
+    def outlierSelect(self, params: ef_outlier_params | None = None, among=None, max_rows: int | None = None, count: bool = False,
+                      result: bool = False, **kw):
+        """the rows removeOutliers with these parameters would remove, in ascending order (uint32), at most max_rows of them (None: all); the
+        map does not change.  among and the keywords as neighborStats takes them.  count=True adds the total, result=True the dict of
+        ef_outlier_result: rows[, total][, result]"""
+        params, among, pa = self._outlierArgs(params, among, kw)
+        cap = self.lastCount() if max_rows is None else int(max_rows)
+        rows = np.zeros(max(cap, 1), np.uint32)
+        total = c_u32(0)
+        res = ef_outlier_result()
+        _chk(lib().ef_map_outliers_select(self.h, C.byref(params), pa, _ptr(rows) if cap else None, cap, C.byref(total),
+                                          C.byref(res) if result else None), self.h)
+        out = (rows[:min(cap, total.value)].copy(),) + ((total.value,) if count else ()) + ((self._outlierResult(res),) if result else ())
+        return out if len(out) > 1 else out[0]
+
+    def outlierSelectDevice(self, params: ef_outlier_params, among, rows_dev, max_rows: int, count_dev, result_dev=None):
+        """ef_map_outliers_select_dev: raw device pointers (int, c_void_p or None for rows with max_rows 0 and for the result), enqueued on
+        the context's stream"""
+        params, among, pa = self._outlierArgs(params, among, {})
+        _chk(lib().ef_map_outliers_select_dev(self.h, C.byref(params), pa, _dev(rows_dev), int(max_rows), _dev(count_dev), _dev(result_dev)), self.h)
+
+    def neighborStatsDevice(self, params: ef_outlier_params, among, mean_dev, count_dev, max_rows: int):
+        """ef_map_neighbor_stats_dev: raw device pointers (int, c_void_p or None) for max_rows floats and max_rows uint32"""
+        params, among, pa = self._outlierArgs(params, among, {})
+        _chk(lib().ef_map_neighbor_stats_dev(self.h, C.byref(params), pa, _dev(mean_dev), _dev(count_dev), int(max_rows)), self.h)
+
+    def removeOutliers(self, params: ef_outlier_params | None = None, among=None, **kw) -> dict:
+        """removes the outlier surfels (ef_map_remove_outliers: what eraseRows(outlierSelect(...)) leaves); not idempotent: what is left has
+        another mean and deviation.  The dict of ef_outlier_result: {"sum", "sum_sq", "participants", "measured", "sparse", "outliers",
+        "count_after", "threshold"}"""
+        params, among, pa = self._outlierArgs(params, among, kw)
+        res = ef_outlier_result()
+        _chk(lib().ef_map_remove_outliers(self.h, C.byref(params), pa, C.byref(res)), self.h)
+        return self._outlierResult(res)
 
     def setReferenceDownload(self, on=True):
         """downloadMap / savePly read what GlobalModel::downloadMap reads (the pre-clean buffer, quirk Q14) instead of model()"""

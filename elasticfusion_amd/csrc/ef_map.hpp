@@ -372,6 +372,40 @@ void carve_flags(const CarveArgs& a, hipStream_t s);
 // offsets and *total of per-chunk counts that a kernel has already written into sc.chunk_count (the scan select_flags and flags_count end with)
 void chunk_totals(const SelectScratch& sc, unsigned n, uint32_t* total, hipStream_t s);
 
+// ---- remove outlier surfels: neighbourhood statistics of the map (ef_outlier.inc; ef_map_remove_outliers of include/ef_hip.h) ----
+constexpr int OUTLIER_RADIUS = 0, OUTLIER_STATISTICAL = 1;   // EF_OUTLIER_*
+constexpr int OUTLIER_SUM_LANES = 4096;                      // EF_OUTLIER_SUM_LANES
+struct OutlierResult {      // ef_outlier_result, field for field (ef_host_outlier.inc asserts the layout)
+  double sum, sum_sq;
+  uint32_t participants, measured, sparse, outliers, count_after;
+  float threshold;
+};
+struct OutlierArgs {
+  QueryArgs q;              // the index built at the call's cell and the live map; max_dist = radius, r2, min_conf (points, n, k, outputs unused)
+  unsigned n;               // rows of the map: the length of the per-row arrays below
+  int mode;                 // OUTLIER_*
+  int k;                    // neighbours of the mean: 1 .. 16 (1 in RADIUS mode)
+  unsigned min_neighbors;
+  int flag_sparse;
+  float std_ratio, max_mean_dist;
+  const uint8_t* part_in;   // one byte per row, non-zero = the row passes the selection (may be `part` itself); null: every row does
+  uint8_t* part;            // one byte per row: 1 = participant (selected and finite); every row is written by the join
+  uint2* stat;              // per row {bits of mean_dist, count}; every row is written by the join
+  double* partial;          // 2 x OUTLIER_SUM_LANES: the lanes' partial sums of term1 and term2
+  uint32_t* tally;          // 3 x OUTLIER_SUM_LANES: the lanes' participants, measured and sparse rows
+  OutlierResult* res;       // the call's result on the device; its threshold is what the flags compare with
+};
+// stat and part of every row: one lane per record of the index, in index order; nothing is launched for an empty map
+void outlier_join(const OutlierArgs& a, hipStream_t s);
+// the fixed-order sums, the counts and the threshold into *a.res (outliers and count_after are outlier_tally's)
+void outlier_reduce(const OutlierArgs& a, hipStream_t s);
+// flags[row] = 1 for every outlier, 0 for every other row (every row is written)
+void outlier_flags(const OutlierArgs& a, uint8_t* flags, hipStream_t s);
+// res->outliers = *total, res->count_after = n - *total; then *copy_to = *res unless copy_to is null
+void outlier_tally(const OutlierArgs& a, const uint32_t* total, OutlierResult* copy_to, hipStream_t s);
+// mean[r] / count[r] of the rows r < min(rows, n) from stat (either may be null)
+void outlier_split(const OutlierArgs& a, float* mean, uint32_t* count, unsigned rows, hipStream_t s);
+
 // ---- fuse surfels into the map (ef_fuse.inc; ef_map_fuse of include/ef_hip.h) ----
 constexpr unsigned long long FUSE_KEY_EMPTY = 0xFFFFFFFFFFFFFFFFull;
 constexpr unsigned FUSE_SKIPPED = 0, FUSE_NOVEL = 1, FUSE_WEIGHTLESS = 2, FUSE_ABSORBED = 3, FUSE_FUSED = 4, FUSE_INSERTED = 5;   // EF_FUSE_*

@@ -1521,6 +1521,7 @@ void sample_graph(SurfelSoA map, const unsigned* count_dev, int stride, int max_
 #include "ef_insert.inc"
 #include "ef_thin.inc"
 #include "ef_carve.inc"
+#include "ef_outlier.inc"
 #include "ef_fuse.inc"
 
 }  // namespace efm

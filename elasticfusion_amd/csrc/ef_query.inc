@@ -69,10 +69,12 @@ __device__ __forceinline__ bool query_less(float da, unsigned ra, float db, unsi
 
 // The cell walk of one lane: lane `sub` of the L that share the query q visits cells sub, sub + L, ... of the query's box (flattened z fastest)
 // and keeps its own K best as sorted (d2, row) keys in bd / br (initialised by the caller), counting every eligible surfel in cnt.  Shared by
-// k_query and k_register (ef_register.inc): the argument below is the only proof that no eligible surfel is missed.
-template <int L, int K>
+// k_query, k_register (ef_register.inc) and k_outlier_join (ef_outlier.inc): the argument below is the only proof that no eligible surfel is
+// missed.  SELF (the self-join only): the query is the index's own record `self`, which is passed over: a map row has exactly one record, so
+// this excludes the query's own ROW and nothing else (a coincident surfel in another row stays a candidate).
+template <int L, int K, bool SELF = false>
 __device__ __forceinline__ void query_walk(const QueryArgs& A, float qx, float qy, float qz, unsigned sub, float (&bd)[K], unsigned (&br)[K],
-                                           unsigned& cnt) {
+                                           unsigned& cnt, unsigned self = 0u) {
   if (A.n_sorted && query_finite3(qx, qy, qz)) {
     // The box: the cells of q -+ rw, rw = max_dist widened by 2^-21 of (max_dist + |q|) per axis.  It cannot miss an eligible surfel p:
     //   d2 <= r2 is decided in f32.  Adding non-negative terms never rounds below a term, so fl(fl(qx-px)^2) <= d2 <= r2 <= max_dist^2 (1+u),
@@ -95,6 +97,7 @@ __device__ __forceinline__ void query_walk(const QueryArgs& A, float qx, float q
       const unsigned b = query_hash(cx, cy, cz, A.mask);
       const unsigned e1 = A.cells[b], e0 = b ? A.cells[b - 1] : 0u;
       for (unsigned k = e0; k < e1; ++k) {
+        if (SELF && k == self) continue;
         const float4 p = A.sorted[k];
         const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
         const float d2 = ((dx * dx + dy * dy) + dz * dz);

@@ -997,6 +997,93 @@ int ef_map_carve(ef_ctx* ctx, const ef_carve_params* params, const ef_carve_view
 int ef_map_carve_dev(ef_ctx* ctx, const ef_carve_params* params, const ef_carve_views* views_depth_dev, const ef_map_selection* among_or_null,
                      ef_carve_result* result);
 
+/* ---- Remove outlier surfels: neighbourhood statistics of the map (the radius and the statistical outlier filters of point-cloud toolkits).  A
+ * speck that became stable stands alone: no frame's clean drops it, and a thin keeps it because it is alone in its cell.  Off until first used:
+ * no outlier call, nothing allocated, nothing run, and no frame kernel knows of it.
+ *
+ * "Row" and the layout of a surfel are those of the section "Select, extract and erase surfels": position = floats 0 .. 2, confidence = float 3.
+ * All arithmetic is f32, one rounding per operation, no contraction, in the written order, except where double is named.  d2(q, t) and the rule
+ * "t is ELIGIBLE for q iff conf_t > min_conf and d2 <= r2" are those of the section "Spatial index and nearest-surfel / kNN queries", with
+ * r2 = radius * radius computed once in f32 on the host and the queries' rule for min_conf (negative: every surfel; NaN is refused).
+ *
+ * PARTICIPANTS, as in the thin.  With among NULL, every row whose position has three finite coordinates.  With a selection, the rows that are
+ * SELECTED by it (the predicate of ef_map_select, unchanged, EF_SEL_INVERT included) and have a finite position.  A row that does not
+ * participate is never an outlier, and its outputs are count = 0, mean_dist = +inf.
+ *
+ * NEIGHBOURS of the participant in row s are all rows t != s that are eligible for the query point p_s (the position of row s), whether or not
+ * t participates.  Self is excluded by ROW, not by distance: a coincident surfel in another row is a neighbour at d2 = 0.  Neighbours are ordered
+ * by (d2, row) ascending.  count_s = the number of ALL neighbours; it may exceed 16.
+ *
+ * MEAN DISTANCE.  k lies in 1 .. 16.  If count_s >= k, row s is MEASURED and, with d2_1 .. d2_k the first k neighbours' d2 in that order,
+ *   mean_s = (((sqrt(d2_1) + sqrt(d2_2)) + ...) + sqrt(d2_k)) / (float)k
+ * summed in neighbour order; every square root and the quotient are the CORRECTLY ROUNDED f32 operations (IEEE 754; no approximate instruction,
+ * whatever the build's flags).  Otherwise row s is SPARSE and mean_s = +inf.  In EF_OUTLIER_RADIUS mode the field k is ignored, mean_dist is
+ * computed with k = 1, and nothing is summed (sum = sum_sq = 0).
+ *
+ * SUMS, in double, pure functions of the per-row values BY ROW (they depend on no order in which anything was evaluated).  For a measured row r,
+ * term1(r) = (double)mean_r and term2(r) = (double)mean_r * (double)mean_r (both exact); every other row of the map contributes +0.0.  With
+ * P = EF_OUTLIER_SUM_LANES, for each of the two terms:
+ *   partial[j] = ((term(j) + term(j + P)) + term(j + 2P)) + ...   for j = 0 .. P-1, rows ascending, starting from +0.0;
+ *   then twelve rounds of a[i] = a[2i] + a[2i+1] over a = partial (4096 -> 2048 -> ... -> 1); the sum is a[0].
+ * S1 = the sum of term1, S2 = the sum of term2, N = the number of measured rows.
+ *
+ * THRESHOLD, in double:  mu = S1 / N;  var = S2 / N - mu * mu, set to 0 if it is negative;  t = mu + (double)std_ratio * sqrt(var) (correctly
+ * rounded);  thr = (float)t.  If N = 0, thr = +inf.  If max_mean_dist > 0, thr = max_mean_dist and the sums are only reported.  In
+ * EF_OUTLIER_RADIUS mode thr = +inf.
+ *
+ * OUTLIERS.  EF_OUTLIER_STATISTICAL: a measured row is an outlier iff mean_s > thr, compared in f32; a sparse row is an outlier iff
+ * flag_sparse != 0.  EF_OUTLIER_RADIUS: a participant is an outlier iff count_s < (uint32_t)min_neighbors.
+ *
+ * ef_map_neighbor_stats changes nothing.  It writes mean_dist[r] and count[r] of the rows r < min(max_rows, map count) (either array may be NULL;
+ * entries past that are left as they were).  ef_map_outliers_select changes nothing.  It writes the outlier rows with ef_map_select's
+ * conventions: the first min(max_rows, total) of them in ASCENDING order, *count = total however small max_rows is, rows may be NULL with
+ * max_rows 0, entries past min(max_rows, total) are left as they were.  The list is what ef_map_erase_rows takes.  result (optional): sum = S1,
+ * sum_sq = S2, participants, measured = N, sparse (in EF_OUTLIER_RADIUS mode both by k = 1), outliers = total, count_after = the map count
+ * minus total, threshold = thr.  The _dev variants take DEVICE pointers for the arrays, count and result and only enqueue on the context's stream
+ * (the threshold is formed on the device), except for what the selection needs (ID numbering, label alignment, the count after a call that can
+ * change the map) and except that they wait for the device once when the index has to be rebuilt or the scratch grows.
+ *
+ * ef_map_remove_outliers removes the outlier rows and leaves everything exactly as ef_map_erase_rows(the list of ef_map_outliers_select) would:
+ * see "What an erase leaves behind" above (the map, the context, the index, IDs, labels, the shadow buffer), with the same two synchronisations.
+ * result (HOST memory, required): as above for the map as it WAS, outliers = the rows removed, count_after = the map count the call leaves.
+ * Unlike the thin it is NOT idempotent: removing specks changes mu and sigma of what is left, so a second call may remove more.
+ *
+ * cell is the cell of the queries' index, which is built at that cell where needed; a later query at another cell (ef_set_query_cell's) rebuilds
+ * it, as after ef_set_query_cell.  No result depends on it.  Defaults (ef_default_outlier_params): EF_OUTLIER_STATISTICAL, k 8, std_ratio 2,
+ * max_mean_dist 0, flag_sparse 1, radius 0.03 m, min_neighbors 4, min_conf -1, cell 0.03 m (= radius, chosen by measurement among radius / 2,
+ * radius and 2 radius: DESIGN.md §8i).
+ *
+ * EF_EINVAL, before any GPU work (the arguments are checked before the context, so with a NULL context ef_last_error(NULL) names what is wrong
+ * with them): a NULL context, params, count or (ef_map_remove_outliers) result; a mode outside its two values; radius or cell not finite and
+ * positive, or 1 / cell not finite; radius / cell above EF_QUERY_MAX_RATIO; k outside 1 .. 16 in EF_OUTLIER_STATISTICAL mode; min_neighbors < 0;
+ * NaN min_conf or std_ratio, a negative std_ratio, a negative or NaN max_mean_dist; max_rows > 0 with NULL rows; with among given, everything
+ * ef_map_select refuses for a selection.
+ * EF_ESTATE: the context's stream is being captured; with among given, what ef_map_select answers with EF_ESTATE.  ef_map_remove_outliers only:
+ * a context created with close_loops = 1 (the erase's reason; the map is unchanged); the select variants and the stats work on such contexts. */
+#define EF_OUTLIER_RADIUS       0   /* outlier iff fewer than min_neighbors neighbours within radius      */
+#define EF_OUTLIER_STATISTICAL  1   /* outlier iff mean distance to the k nearest neighbours > threshold  */
+#define EF_OUTLIER_SUM_LANES 4096   /* P of the summation order above */
+typedef struct ef_outlier_params {
+  int mode; float radius; float cell; float min_conf;
+  int min_neighbors;                 /* RADIUS */
+  int k; float std_ratio; float max_mean_dist; int flag_sparse;   /* STATISTICAL */
+} ef_outlier_params;
+typedef struct ef_outlier_result {
+  double sum, sum_sq;                /* S1, S2 above (0 in RADIUS mode) */
+  uint32_t participants, measured, sparse, outliers, count_after;
+  float threshold;                   /* thr above (+inf in RADIUS mode) */
+} ef_outlier_result;
+int ef_default_outlier_params(ef_ctx* ctx, ef_outlier_params* params);
+int ef_map_neighbor_stats(ef_ctx* ctx, const ef_outlier_params* params, const ef_map_selection* among_or_null, float* mean_dist_or_null,
+                          uint32_t* count_or_null, uint32_t max_rows);
+int ef_map_neighbor_stats_dev(ef_ctx* ctx, const ef_outlier_params* params, const ef_map_selection* among_or_null, float* mean_dist_dev_or_null,
+                              uint32_t* count_dev_or_null, uint32_t max_rows);
+int ef_map_outliers_select(ef_ctx* ctx, const ef_outlier_params* params, const ef_map_selection* among_or_null, uint32_t* rows, uint32_t max_rows,
+                           uint32_t* count, ef_outlier_result* result_or_null);
+int ef_map_outliers_select_dev(ef_ctx* ctx, const ef_outlier_params* params, const ef_map_selection* among_or_null, uint32_t* rows_dev,
+                               uint32_t max_rows, uint32_t* count_dev, ef_outlier_result* result_dev_or_null);
+int ef_map_remove_outliers(ef_ctx* ctx, const ef_outlier_params* params, const ef_map_selection* among_or_null, ef_outlier_result* result);
+
 /* named internal images, copied to HOST (synchronises); for tests and for a front-end's drawing code */
 enum ef_image {
   EF_IMG_DEPTH_FILTERED = 0,      /* u16  */
