@@ -118,6 +118,28 @@ def without_outliers(ef: "api.ElasticFusion", **params) -> np.ndarray:
     return ef.gatherSurfels(np.nonzero(kept)[0].astype(np.uint32))
 
 
+def segments(ef: "api.ElasticFusion", min_size: int = 50, max_segments: int | None = None, **params) -> list:
+    """ef's map cut into its connected components under "closer than radius": a list of [k, 12] float32 arrays as downloadMap() gives them,
+    one per component of at least min_size nodes, LARGEST FIRST with ties by label (the component's smallest row), at most max_segments of
+    them; the map does not change and is not downloaded: components + one gatherSurfels per segment (ef_map_components + ef_map_gather).
+    The keywords (params, among, ef_component_params fields) as components takes them."""
+    label, size = ef.components(**params)
+    roots = np.nonzero((label == np.arange(len(label), dtype=np.uint32)) & (size >= max(int(min_size), 1)))[0]
+    roots = roots[np.lexsort((roots, -size[roots].astype(np.int64)))]
+    if max_segments is not None:
+        roots = roots[:max_segments]
+    order = np.argsort(label, kind="stable")                # one pass: the rows of every label, ascending within it
+    first = np.searchsorted(label[order], roots)
+    return [ef.gatherSurfels(order[a:a + int(size[r])].astype(np.uint32)) for r, a in zip(roots, first)]
+
+
+def largest_component(ef: "api.ElasticFusion", **params) -> np.ndarray:
+    """the surfels of ef's largest connected component (ties: the lowest label), [k, 12] float32, [0, 12] for a map without nodes; the map
+    does not change.  The keywords as segments takes them."""
+    got = segments(ef, min_size=1, max_segments=1, **params)
+    return got[0] if got else np.zeros((0, 12), np.float32)
+
+
 def map_accuracy(ef: "api.ElasticFusion", gt_surfels: np.ndarray, max_dist: float = 0.05, map_rows=None, gt_rows=None, device: int = 0,
                  align: bool = False, align_schedule=REGISTER_SCHEDULE) -> dict:
     """ef: a context with a map; gt_surfels: [m, 12] float32, laid out as downloadMap() gives them (synth.sample_surfels), in the map's world

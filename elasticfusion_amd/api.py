@@ -153,7 +153,18 @@ class ef_outlier_result(C.Structure):
                 ("outliers", c_u32), ("count_after", c_u32), ("threshold", c_f)]
 
 
+class ef_component_params(C.Structure):
+    _fields_ = [("radius", c_f), ("cell", c_f), ("min_conf", c_f), ("min_size", c_u32), ("max_size", c_u32)]
+
+
+class ef_component_result(C.Structure):
+    _fields_ = [("nodes", c_u32), ("components", c_u32), ("largest", c_u32), ("rejected_rows", c_u32), ("rejected_components", c_u32),
+                ("count_after", c_u32), ("status", c_u32)]
+
+
 CARVE_MAX_VIEWS = 32   # EF_CARVE_MAX_VIEWS of include/ef_hip.h
+COMPONENT_NONE = 0xFFFFFFFF                          # EF_COMPONENT_NONE of include/ef_hip.h: the label of a row that is no node
+COMPONENTS_REJECTED, COMPONENTS_ACCEPTED = 0, 1     # EF_COMPONENTS_*: which nodes ef_map_components_select lists
 OUTLIER_RADIUS, OUTLIER_STATISTICAL = 0, 1   # EF_OUTLIER_* of include/ef_hip.h: the two filters
 OUTLIER_SUM_LANES = 4096                     # EF_OUTLIER_SUM_LANES: P of the summation order
 THIN_KEEP_MAX_CONF, THIN_KEEP_NEWEST, THIN_KEEP_FIRST = 0, 1, 2   # EF_THIN_KEEP_* of include/ef_hip.h
@@ -1449,6 +1460,74 @@ class ElasticFusion:
         res = ef_outlier_result()
         _chk(lib().ef_map_remove_outliers(self.h, C.byref(params), pa, C.byref(res)), self.h)
         return self._outlierResult(res)
+
+    # --- connected components of the map under "closer than r" (ef_map_components / ef_map_components_select / ef_map_remove_components) ---
+    def componentParams(self, **kw) -> ef_component_params:
+        """ef_default_component_params (radius 0.03, cell 0.03, min_conf -1, min_size 50, max_size 0) with fields replaced by keyword"""
+        return self._params(ef_component_params, lib().ef_default_component_params, kw, "component")
+
+    def _componentArgs(self, params, among, kw):
+        if params is None:
+            params = self.componentParams(**kw)
+        else:
+            assert not kw, "give params or keywords, not both"
+        if isinstance(among, dict):
+            among = self.mapSelection(**among)
+        return params, among, (C.byref(among) if among is not None else None)
+
+    @staticmethod
+    def _componentResult(res: ef_component_result) -> dict:
+        return {k: int(getattr(res, k)) for k, _ in ef_component_result._fields_}
+
+    def components(self, params: ef_component_params | None = None, among=None, result: bool = False, **kw):
+        """(label uint32, size uint32) per row of downloadMap(): the smallest row of the surfel's connected component under "closer than
+        radius" and the component's number of nodes; COMPONENT_NONE and 0 for a row that is no node; the map does not change.  among: an
+        ef_map_selection, a dict of mapSelection keywords or None (every surfel participates); other keywords are ef_component_params
+        fields.  result=True adds the dict of ef_component_result"""
+        params, among, pa = self._componentArgs(params, among, kw)
+        n = self.lastCount()
+        label = np.zeros(max(n, 1), np.uint32)
+        size = np.zeros(max(n, 1), np.uint32)
+        res = ef_component_result()
+        _chk(lib().ef_map_components(self.h, C.byref(params), pa, _ptr(label), _ptr(size), n, C.byref(res)), self.h)
+        return (label[:n], size[:n]) + ((self._componentResult(res),) if result else ())
+
+    def componentSelect(self, params: ef_component_params | None = None, among=None, what: int = COMPONENTS_REJECTED, max_rows: int | None = None,
+                        count: bool = False, result: bool = False, **kw):
+        """the nodes of the rejected components (what = COMPONENTS_REJECTED: fewer than min_size or, with max_size != 0, more than max_size
+        nodes; the rows removeComponents with these parameters would remove) or of the accepted ones (COMPONENTS_ACCEPTED), in ascending order
+        (uint32), at most max_rows of them (None: all); the map does not change.  among and the keywords as components takes them.
+        count=True adds the total, result=True the dict of ef_component_result: rows[, total][, result]"""
+        params, among, pa = self._componentArgs(params, among, kw)
+        cap = self.lastCount() if max_rows is None else int(max_rows)
+        rows = np.zeros(max(cap, 1), np.uint32)
+        total = c_u32(0)
+        res = ef_component_result()
+        _chk(lib().ef_map_components_select(self.h, C.byref(params), pa, int(what), _ptr(rows) if cap else None, cap, C.byref(total),
+                                            C.byref(res) if result else None), self.h)
+        out = (rows[:min(cap, total.value)].copy(),) + ((total.value,) if count else ()) + ((self._componentResult(res),) if result else ())
+        return out if len(out) > 1 else out[0]
+
+    def componentSelectDevice(self, params: ef_component_params, among, what: int, rows_dev, max_rows: int, count_dev, result_dev=None):
+        """ef_map_components_select_dev: raw device pointers (int, c_void_p or None for rows with max_rows 0 and for the result), enqueued on
+        the context's stream"""
+        params, among, pa = self._componentArgs(params, among, {})
+        _chk(lib().ef_map_components_select_dev(self.h, C.byref(params), pa, int(what), _dev(rows_dev), int(max_rows), _dev(count_dev),
+                                                _dev(result_dev)), self.h)
+
+    def componentsDevice(self, params: ef_component_params, among, label_dev, size_dev, max_rows: int, result_dev=None):
+        """ef_map_components_dev: raw device pointers (int, c_void_p or None) for max_rows uint32 each and for the result"""
+        params, among, pa = self._componentArgs(params, among, {})
+        _chk(lib().ef_map_components_dev(self.h, C.byref(params), pa, _dev(label_dev), _dev(size_dev), int(max_rows), _dev(result_dev)), self.h)
+
+    def removeComponents(self, params: ef_component_params | None = None, among=None, **kw) -> dict:
+        """removes the nodes of the rejected components (ef_map_remove_components: what eraseRows(componentSelect(...)) leaves); idempotent: a
+        second call with the same arguments removes nothing.  The dict of ef_component_result: {"nodes", "components", "largest",
+        "rejected_rows", "rejected_components", "count_after", "status"}"""
+        params, among, pa = self._componentArgs(params, among, kw)
+        res = ef_component_result()
+        _chk(lib().ef_map_remove_components(self.h, C.byref(params), pa, C.byref(res)), self.h)
+        return self._componentResult(res)
 
     def setReferenceDownload(self, on=True):
         """downloadMap / savePly read what GlobalModel::downloadMap reads (the pre-clean buffer, quirk Q14) instead of model()"""

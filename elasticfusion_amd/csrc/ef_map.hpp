@@ -406,6 +406,34 @@ void outlier_tally(const OutlierArgs& a, const uint32_t* total, OutlierResult* c
 // mean[r] / count[r] of the rows r < min(rows, n) from stat (either may be null)
 void outlier_split(const OutlierArgs& a, float* mean, uint32_t* count, unsigned rows, hipStream_t s);
 
+// ---- connected components of the map under "closer than r" (ef_components.inc; ef_map_components of include/ef_hip.h) ----
+constexpr unsigned COMPONENT_NONE = 0xFFFFFFFFu;                    // EF_COMPONENT_NONE
+constexpr int COMPONENTS_REJECTED = 0, COMPONENTS_ACCEPTED = 1;     // EF_COMPONENTS_*
+struct ComponentResult {    // ef_component_result, field for field (ef_host_components.inc asserts the layout)
+  uint32_t nodes, components, largest, rejected_rows, rejected_components, count_after, status;
+};
+struct ComponentArgs {
+  QueryArgs q;              // the index built at the call's cell and the live map; max_dist = radius, r2, min_conf (points, n, k, outputs unused)
+  unsigned n;               // rows of the map: the length of the per-row arrays below
+  unsigned min_size, max_size;
+  const uint8_t* sel;       // one byte per row, non-zero = the row passes the selection (may be `node` itself); null: every row does
+  uint8_t* node;            // one byte per row: 1 = node (selected, finite, conf > min_conf); every row is written by component_hook
+  uint32_t* parent;         // the union-find's word per row (ef_unionfind.hpp); COMPONENT_NONE for a row that is no node
+  uint32_t* label;          // per row the smallest row of its component, COMPONENT_NONE for a row that is no node
+  uint32_t* members;        // members[l] = nodes of the component labelled l (0 at every row that is no label)
+  ComponentResult* res;     // the call's result on the device, zeroed by component_hook's caller; status != 0: a loop cap tripped
+};
+// node, parent and members of every row, the link to the smallest lower neighbour, then every edge's union (one lane per record of the index, in
+// index order), with pointer-jumping passes after each of the two (nothing for an empty map)
+void component_hook(const ComponentArgs& a, hipStream_t s);
+// label and members; then nodes, components, largest, rejected_rows, rejected_components into *a.res and, unless flags is null,
+// flags[row] = 1 for every rejected (what = COMPONENTS_REJECTED) or accepted (COMPONENTS_ACCEPTED) node, 0 for every other row
+void component_label(const ComponentArgs& a, int what, uint8_t* flags, hipStream_t s);
+// res->count_after = n - res->rejected_rows; then *copy_to = *res unless copy_to is null
+void component_tally(const ComponentArgs& a, ComponentResult* copy_to, hipStream_t s);
+// label[r] / size[r] of the rows r < min(rows, n) (either may be null)
+void component_split(const ComponentArgs& a, uint32_t* label, uint32_t* size, unsigned rows, hipStream_t s);
+
 // ---- fuse surfels into the map (ef_fuse.inc; ef_map_fuse of include/ef_hip.h) ----
 constexpr unsigned long long FUSE_KEY_EMPTY = 0xFFFFFFFFFFFFFFFFull;
 constexpr unsigned FUSE_SKIPPED = 0, FUSE_NOVEL = 1, FUSE_WEIGHTLESS = 2, FUSE_ABSORBED = 3, FUSE_FUSED = 4, FUSE_INSERTED = 5;   // EF_FUSE_*

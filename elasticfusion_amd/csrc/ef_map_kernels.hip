@@ -10,6 +10,7 @@
 #include <hip/hip_ext.h>
 #include "ef_map.hpp"
 #include "ef_zkey.hpp"
+#include "ef_unionfind.hpp"
 
 using namespace ef;
 
@@ -1522,6 +1523,7 @@ void sample_graph(SurfelSoA map, const unsigned* count_dev, int stride, int max_
 #include "ef_thin.inc"
 #include "ef_carve.inc"
 #include "ef_outlier.inc"
+#include "ef_components.inc"
 #include "ef_fuse.inc"
 
 }  // namespace efm

@@ -68,13 +68,13 @@ __global__ void __launch_bounds__(BLK) k_query_scatter(const float4* __restrict_
 __device__ __forceinline__ bool query_less(float da, unsigned ra, float db, unsigned rb) { return da < db || (da == db && ra < rb); }
 
 // The cell walk of one lane: lane `sub` of the L that share the query q visits cells sub, sub + L, ... of the query's box (flattened z fastest)
-// and keeps its own K best as sorted (d2, row) keys in bd / br (initialised by the caller), counting every eligible surfel in cnt.  Shared by
-// k_query, k_register (ef_register.inc) and k_outlier_join (ef_outlier.inc): the argument below is the only proof that no eligible surfel is
-// missed.  SELF (the self-join only): the query is the index's own record `self`, which is passed over: a map row has exactly one record, so
-// this excludes the query's own ROW and nothing else (a coincident surfel in another row stays a candidate).
-template <int L, int K, bool SELF = false>
-__device__ __forceinline__ void query_walk(const QueryArgs& A, float qx, float qy, float qz, unsigned sub, float (&bd)[K], unsigned (&br)[K],
-                                           unsigned& cnt, unsigned self = 0u) {
+// and calls visit(d2, k) for every record k of the index that is eligible for q, once, in the visit of the record's own cell.  The one
+// statement of the walk: query_walk below (k_query, k_register of ef_register.inc, k_outlier_join of ef_outlier.inc) and k_comp_hook
+// (ef_components.inc) differ in the visitor only, and the argument below is the only proof that no eligible surfel is missed.  SELF (the
+// self-joins only): the query is the index's own record `self`, which is passed over: a map row has exactly one record, so this excludes the
+// query's own ROW and nothing else (a coincident surfel in another row stays a candidate).
+template <int L, bool SELF, class Visit>
+__device__ __forceinline__ void query_visit(const QueryArgs& A, float qx, float qy, float qz, unsigned sub, unsigned self, Visit&& visit) {
   if (A.n_sorted && query_finite3(qx, qy, qz)) {
     // The box: the cells of q -+ rw, rw = max_dist widened by 2^-21 of (max_dist + |q|) per axis.  It cannot miss an eligible surfel p:
     //   d2 <= r2 is decided in f32.  Adding non-negative terms never rounds below a term, so fl(fl(qx-px)^2) <= d2 <= r2 <= max_dist^2 (1+u),
@@ -103,22 +103,31 @@ __device__ __forceinline__ void query_walk(const QueryArgs& A, float qx, float q
         const float d2 = ((dx * dx + dy * dy) + dz * dz);
         if (!(p.w > A.min_conf && d2 <= A.r2)) continue;
         if (query_cell(p.x, A.inv_cell) != cx || query_cell(p.y, A.inv_cell) != cy || query_cell(p.z, A.inv_cell) != cz) continue;
-        ++cnt;
-        float d = d2;
-        unsigned r = A.rows[k];
-        if (!query_less(d, r, bd[K - 1], br[K - 1])) continue;
-        bd[K - 1] = d;
-        br[K - 1] = r;
-#pragma unroll
-        for (int j = K - 1; j > 0; --j) {
-          if (query_less(bd[j], br[j], bd[j - 1], br[j - 1])) {
-            d = bd[j]; bd[j] = bd[j - 1]; bd[j - 1] = d;
-            r = br[j]; br[j] = br[j - 1]; br[j - 1] = r;
-          }
-        }
+        visit(d2, k);
       }
     }
   }
+}
+
+// query_visit with the top-K visitor: the lane keeps its own K best as sorted (d2, row) keys in bd / br (initialised by the caller) and counts
+// every eligible surfel in cnt.
+template <int L, int K, bool SELF = false>
+__device__ __forceinline__ void query_walk(const QueryArgs& A, float qx, float qy, float qz, unsigned sub, float (&bd)[K], unsigned (&br)[K],
+                                           unsigned& cnt, unsigned self = 0u) {
+  query_visit<L, SELF>(A, qx, qy, qz, sub, self, [&](float d, unsigned k) {
+    ++cnt;
+    unsigned r = A.rows[k];
+    if (!query_less(d, r, bd[K - 1], br[K - 1])) return;
+    bd[K - 1] = d;
+    br[K - 1] = r;
+#pragma unroll
+    for (int j = K - 1; j > 0; --j) {
+      if (query_less(bd[j], br[j], bd[j - 1], br[j - 1])) {
+        d = bd[j]; bd[j] = bd[j - 1]; bd[j - 1] = d;
+        r = br[j]; br[j] = br[j - 1]; br[j - 1] = r;
+      }
+    }
+  });
 }
 
 // L lanes share a query: every lane walks its share of the box (query_walk) and keeps its own K best in registers (K is a template parameter:

@@ -1084,6 +1084,81 @@ int ef_map_outliers_select_dev(ef_ctx* ctx, const ef_outlier_params* params, con
                                uint32_t max_rows, uint32_t* count_dev, ef_outlier_result* result_dev_or_null);
 int ef_map_remove_outliers(ef_ctx* ctx, const ef_outlier_params* params, const ef_map_selection* among_or_null, ef_outlier_result* result);
 
+/* ---- Connected components of the map under "closer than r" (the Euclidean cluster extraction of point-cloud toolkits).  A detached blob of a
+ * few hundred surfels (a ghost a loop closure left, the far side of a carve) survives the statistical filter, because every member has k close
+ * neighbours; "this component has fewer than m members" removes it.  After an erase of the floor's box the components are the objects.  Off
+ * until first used: no component call, nothing allocated, nothing run, and no frame kernel knows of it.
+ *
+ * "Row", the layout of a surfel, d2(q, t) = ((dx * dx + dy * dy) + dz * dz) in f32 with dx = q.x - t.x (one rounding per operation, no
+ * contraction, in the written order) and r2 = radius * radius computed once in f32 on the host are those of the sections "Spatial index and
+ * nearest-surfel / kNN queries" and "Remove outlier surfels".  d2 is SYMMETRIC in f32: q - p and p - q differ in sign only, and the squares
+ * and their sums do not see the sign, so d2(p_s, p_t) and d2(p_t, p_s) are the same bits and the graph below is undirected by construction.
+ *
+ * PARTICIPANTS are the thin's and the outliers'.  With among NULL, every row whose position has three finite coordinates.  With a selection, the
+ * rows that are SELECTED by it (the predicate of ef_map_select, unchanged, EF_SEL_INVERT included) and have a finite position.
+ * A NODE is a participant whose confidence passes the queries' rule conf > min_conf (negative min_conf: every surfel; NaN is refused;
+ * comparisons with a NaN confidence are false).
+ *
+ * An EDGE joins two distinct nodes s != t iff d2(p_s, p_t) <= r2.  Coincident surfels in different rows are joined at d2 = 0; a row is never
+ * its own neighbour; a row that is no node never carries an edge, so a surfel that is not selected (or below min_conf) does not bridge two
+ * groups that are.  COMPONENTS are the connected components of that graph.  label[s] = the SMALLEST ROW of the component of s: canonical, a
+ * function of the graph alone, whatever order anything was evaluated in.  size[s] = the number of nodes of that component.  A row that is no
+ * node has label = EF_COMPONENT_NONE and size = 0.
+ *
+ * A node is REJECTED iff size < min_size or (max_size != 0 and size > max_size), otherwise ACCEPTED; all nodes of a component share the
+ * verdict.  A row that is no node is neither.
+ *
+ * ef_component_result: nodes; components = the number of rows r with label[r] == r; largest = the greatest size (0 without nodes);
+ * rejected_rows and rejected_components = the rejected nodes and their components; count_after = the map count minus rejected_rows; status =
+ * 0, or non-zero if one of the device loops ran into its step bound, which no input can cause (the host variants then return EF_EHIP and
+ * ef_map_remove_components removes nothing; the _dev variants can only report it here).
+ *
+ * ef_map_components changes nothing.  It writes label[r] and size[r] of the rows r < min(max_rows, map count) (either array may be NULL;
+ * entries past that are left as they were) and the optional result; min_size and max_size only reach the result.
+ * ef_map_components_select changes nothing.  what = EF_COMPONENTS_REJECTED or EF_COMPONENTS_ACCEPTED: it writes those rows with ef_map_select's
+ * conventions: the first min(max_rows, total) of them in ASCENDING order, *count = total however small max_rows is, rows may be NULL with
+ * max_rows 0, entries past min(max_rows, total) are left as they were.  The list is what ef_map_erase_rows and ef_map_gather take.  The
+ * result does not depend on what.  The _dev variants take DEVICE pointers for the arrays, count and result and only enqueue on the context's
+ * stream, except for what the selection needs (ID numbering, label alignment, the count after a call that can change the map) and except that
+ * they wait for the device once when the index has to be rebuilt or the scratch grows.
+ *
+ * ef_map_remove_components removes the rejected rows and leaves everything exactly as ef_map_erase_rows(the EF_COMPONENTS_REJECTED list) would:
+ * see "What an erase leaves behind" above, with one more synchronisation (the result is read before a row changes).  result (HOST memory,
+ * required): as above for the map as it WAS, rejected_rows = the rows removed, count_after = the map count the call leaves.  Unlike the
+ * outlier filters it is IDEMPOTENT: whole components go, no edge joined them to a node that stays, so every other component keeps its nodes,
+ * its size and its verdict (its label's VALUE may drop with the row numbers), and a second call with the same arguments removes nothing.
+ *
+ * cell is the cell of the queries' index, which is built at that cell where needed; a later query at another cell rebuilds it, as after
+ * ef_set_query_cell.  No result depends on it.  Defaults (ef_default_component_params): radius 0.03 m, cell 0.03 m, min_conf -1, min_size 50,
+ * max_size 0 (no upper bound).
+ *
+ * EF_EINVAL, before any GPU work (the arguments are checked before the context, so with a NULL context ef_last_error(NULL) names what is wrong
+ * with them): a NULL context, params, count or (ef_map_remove_components) result; radius or cell not finite and positive, or 1 / cell not
+ * finite; radius / cell above EF_QUERY_MAX_RATIO; NaN min_conf; what outside its two values; max_rows > 0 with NULL rows; with among given,
+ * everything ef_map_select refuses for a selection.
+ * EF_ESTATE: the context's stream is being captured; with among given, what ef_map_select answers with EF_ESTATE.  ef_map_remove_components
+ * only: a context created with close_loops = 1 (the erase's reason; the map is unchanged); the other calls work on such contexts. */
+#define EF_COMPONENT_NONE 0xFFFFFFFFu   /* label of a row that is no node */
+#define EF_COMPONENTS_REJECTED 0        /* the nodes of components below min_size or above max_size */
+#define EF_COMPONENTS_ACCEPTED 1        /* every other node */
+typedef struct ef_component_params {
+  float radius; float cell; float min_conf;
+  uint32_t min_size; uint32_t max_size;   /* max_size 0: no upper bound */
+} ef_component_params;
+typedef struct ef_component_result {
+  uint32_t nodes, components, largest, rejected_rows, rejected_components, count_after, status;
+} ef_component_result;
+int ef_default_component_params(ef_ctx* ctx, ef_component_params* params);
+int ef_map_components(ef_ctx* ctx, const ef_component_params* params, const ef_map_selection* among_or_null, uint32_t* label_or_null,
+                      uint32_t* size_or_null, uint32_t max_rows, ef_component_result* result_or_null);
+int ef_map_components_dev(ef_ctx* ctx, const ef_component_params* params, const ef_map_selection* among_or_null, uint32_t* label_dev_or_null,
+                          uint32_t* size_dev_or_null, uint32_t max_rows, ef_component_result* result_dev_or_null);
+int ef_map_components_select(ef_ctx* ctx, const ef_component_params* params, const ef_map_selection* among_or_null, int what, uint32_t* rows,
+                             uint32_t max_rows, uint32_t* count, ef_component_result* result_or_null);
+int ef_map_components_select_dev(ef_ctx* ctx, const ef_component_params* params, const ef_map_selection* among_or_null, int what,
+                                 uint32_t* rows_dev, uint32_t max_rows, uint32_t* count_dev, ef_component_result* result_dev_or_null);
+int ef_map_remove_components(ef_ctx* ctx, const ef_component_params* params, const ef_map_selection* among_or_null, ef_component_result* result);
+
 /* named internal images, copied to HOST (synchronises); for tests and for a front-end's drawing code */
 enum ef_image {
   EF_IMG_DEPTH_FILTERED = 0,      /* u16  */
