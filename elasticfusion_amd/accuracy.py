@@ -140,6 +140,22 @@ def largest_component(ef: "api.ElasticFusion", **params) -> np.ndarray:
     return got[0] if got else np.zeros((0, 12), np.float32)
 
 
+def plane_segments(ef: "api.ElasticFusion", **params) -> list:
+    """ef's map cut into its planes: a list of (model dict, [k, 12] float32 surfels as downloadMap() gives them), one per plane found, in
+    the order they were found; the map does not change and is not downloaded: planes + one gatherSurfels per plane (ef_map_planes +
+    ef_map_gather).  The keywords (params, among, ef_plane_params fields) as planes takes them."""
+    plane, models = ef.planes(**params)
+    order = np.argsort(plane, kind="stable")                # one pass: the rows of every plane, ascending within it
+    first = np.searchsorted(plane[order], np.arange(len(models), dtype=np.uint32))
+    return [(m, ef.gatherSurfels(order[a:a + m["inliers"]].astype(np.uint32))) for m, a in zip(models, first)]
+
+
+def without_planes(ef: "api.ElasticFusion", **params) -> np.ndarray:
+    """a gathered copy of the participants that lie on no found plane (the PLANES_OFF rows: what removePlanes leaves of them), [k, 12] float32;
+    the map does not change and is not downloaded.  The keywords as plane_segments takes them."""
+    return ef.gatherSurfels(ef.planeSelect(what=api.PLANES_OFF, **params))
+
+
 def map_accuracy(ef: "api.ElasticFusion", gt_surfels: np.ndarray, max_dist: float = 0.05, map_rows=None, gt_rows=None, device: int = 0,
                  align: bool = False, align_schedule=REGISTER_SCHEDULE) -> dict:
     """ef: a context with a map; gt_surfels: [m, 12] float32, laid out as downloadMap() gives them (synth.sample_surfels), in the map's world

@@ -162,7 +162,25 @@ class ef_component_result(C.Structure):
                 ("count_after", c_u32), ("status", c_u32)]
 
 
+class ef_plane_params(C.Structure):
+    _fields_ = [("distance", c_f), ("normal_cos", c_f), ("min_conf", c_f), ("hypotheses", c_u32), ("seed", c_u32), ("max_planes", c_u32),
+                ("min_inliers", c_u32), ("refine", c_u32), ("axis_mode", c_u32), ("axis", c_f * 3), ("axis_bound", c_f)]
+
+
+class ef_plane_model(C.Structure):
+    _fields_ = [("normal", c_f * 3), ("d", c_f), ("inliers", c_u32), ("sampled_inliers", c_u32), ("hypothesis", c_u32),
+                ("valid_hypotheses", c_u32), ("participants", c_u32), ("thickness", c_f)]
+
+
+class ef_plane_result(C.Structure):
+    _fields_ = [("nodes", c_u32), ("planes", c_u32), ("on_rows", c_u32), ("off_rows", c_u32), ("count_after", c_u32)]
+
+
 CARVE_MAX_VIEWS = 32   # EF_CARVE_MAX_VIEWS of include/ef_hip.h
+PLANE_NONE = 0xFFFFFFFF                              # EF_PLANE_NONE of include/ef_hip.h: plane[] of a row on no found plane
+PLANE_MAX_PLANES, PLANE_MAX_HYPOTHESES = 16, 4096   # EF_PLANE_MAX_*
+PLANE_AXIS_OFF, PLANE_AXIS_NORMAL, PLANE_AXIS_INPLANE = 0, 1, 2   # EF_PLANE_AXIS_*: the constraint on a plane's normal
+PLANES_ON, PLANES_OFF = 0, 1                        # EF_PLANES_*: which nodes ef_map_planes_select lists
 COMPONENT_NONE = 0xFFFFFFFF                          # EF_COMPONENT_NONE of include/ef_hip.h: the label of a row that is no node
 COMPONENTS_REJECTED, COMPONENTS_ACCEPTED = 0, 1     # EF_COMPONENTS_*: which nodes ef_map_components_select lists
 OUTLIER_RADIUS, OUTLIER_STATISTICAL = 0, 1   # EF_OUTLIER_* of include/ef_hip.h: the two filters
@@ -1528,6 +1546,90 @@ class ElasticFusion:
         res = ef_component_result()
         _chk(lib().ef_map_remove_components(self.h, C.byref(params), pa, C.byref(res)), self.h)
         return self._componentResult(res)
+
+    # --- planes of the map by sequential RANSAC (ef_map_planes / ef_map_planes_select / ef_map_remove_planes) ---
+    def planeParams(self, **kw) -> ef_plane_params:
+        """ef_default_plane_params (distance 0.01, normal_cos 0, min_conf -1, hypotheses 1024, seed 0, max_planes 4, min_inliers 500, refine 1,
+        axis_mode PLANE_AXIS_OFF, axis (0, 0, 1), axis_bound 0.95) with fields replaced by keyword; axis: three floats"""
+        if "axis" in kw:
+            kw = dict(kw, axis=(c_f * 3)(*[float(v) for v in kw["axis"]]))
+        return self._params(ef_plane_params, lib().ef_default_plane_params, kw, "plane")
+
+    def _planeArgs(self, params, among, kw):
+        if params is None:
+            params = self.planeParams(**kw)
+        else:
+            assert not kw, "give params or keywords, not both"
+        if isinstance(among, dict):
+            among = self.mapSelection(**among)
+        return params, among, (C.byref(among) if among is not None else None)
+
+    @staticmethod
+    def _planeResult(res: ef_plane_result) -> dict:
+        return {k: int(getattr(res, k)) for k, _ in ef_plane_result._fields_}
+
+    @staticmethod
+    def _planeModels(models, planes: int) -> list:
+        """the first `planes` entries of an ef_plane_model array as dicts: normal (float32 [3]), d and thickness (numpy float32), the integers"""
+        out = []
+        for m in models[:planes]:
+            d = {k: int(getattr(m, k)) for k in ("inliers", "sampled_inliers", "hypothesis", "valid_hypotheses", "participants")}
+            d.update(normal=np.array(list(m.normal), np.float32), d=np.float32(m.d), thickness=np.float32(m.thickness))
+            out.append(d)
+        return out
+
+    def planes(self, params: ef_plane_params | None = None, among=None, result: bool = False, **kw):
+        """(plane uint32 per row of downloadMap(), list of model dicts[, result]): the index of the plane the surfel lies on, PLANE_NONE for
+        a surfel on none, and per found plane {"normal", "d", "inliers", "sampled_inliers", "hypothesis", "valid_hypotheses", "participants",
+        "thickness"}; the map does not change.  among: an ef_map_selection, a dict of mapSelection keywords or None (every surfel
+        participates); other keywords are ef_plane_params fields.  result=True adds the dict of ef_plane_result"""
+        params, among, pa = self._planeArgs(params, among, kw)
+        n = self.lastCount()
+        plane = np.zeros(max(n, 1), np.uint32)
+        models = (ef_plane_model * PLANE_MAX_PLANES)()
+        res = ef_plane_result()
+        _chk(lib().ef_map_planes(self.h, C.byref(params), pa, _ptr(plane), n, models, C.byref(res)), self.h)
+        return (plane[:n], self._planeModels(models, res.planes)) + ((self._planeResult(res),) if result else ())
+
+    def planeSelect(self, params: ef_plane_params | None = None, among=None, what: int = PLANES_ON, which: int = -1, max_rows: int | None = None,
+                    count: bool = False, models: bool = False, result: bool = False, **kw):
+        """the rows on plane `which` (what = PLANES_ON; which = -1: on any found plane; the rows removePlanes with these arguments would
+        remove) or every other participant (PLANES_OFF), in ascending order (uint32), at most max_rows of them (None: all); the map does not
+        change.  among and the keywords as planes takes them.  count=True adds the total, models=True the list of model dicts, result=True
+        the dict of ef_plane_result: rows[, total][, models][, result]"""
+        params, among, pa = self._planeArgs(params, among, kw)
+        cap = self.lastCount() if max_rows is None else int(max_rows)
+        rows = np.zeros(max(cap, 1), np.uint32)
+        total = c_u32(0)
+        mods = (ef_plane_model * PLANE_MAX_PLANES)()
+        res = ef_plane_result()
+        _chk(lib().ef_map_planes_select(self.h, C.byref(params), pa, int(what), int(which), _ptr(rows) if cap else None, cap, C.byref(total), mods,
+                                        C.byref(res)), self.h)
+        out = ((rows[:min(cap, total.value)].copy(),) + ((total.value,) if count else ()) + ((self._planeModels(mods, res.planes),) if models else ())
+               + ((self._planeResult(res),) if result else ()))
+        return out if len(out) > 1 else out[0]
+
+    def planeSelectDevice(self, params: ef_plane_params, among, what: int, which: int, rows_dev, max_rows: int, count_dev, models_dev=None,
+                          result_dev=None):
+        """ef_map_planes_select_dev: raw device pointers (int, c_void_p or None for rows with max_rows 0, for the models and for the result),
+        enqueued on the context's stream"""
+        params, among, pa = self._planeArgs(params, among, {})
+        _chk(lib().ef_map_planes_select_dev(self.h, C.byref(params), pa, int(what), int(which), _dev(rows_dev), int(max_rows), _dev(count_dev),
+                                            _dev(models_dev), _dev(result_dev)), self.h)
+
+    def planesDevice(self, params: ef_plane_params, among, plane_dev, max_rows: int, models_dev=None, result_dev=None):
+        """ef_map_planes_dev: raw device pointers (int, c_void_p or None) for max_rows uint32, params.max_planes models and the result"""
+        params, among, pa = self._planeArgs(params, among, {})
+        _chk(lib().ef_map_planes_dev(self.h, C.byref(params), pa, _dev(plane_dev), int(max_rows), _dev(models_dev), _dev(result_dev)), self.h)
+
+    def removePlanes(self, params: ef_plane_params | None = None, among=None, which: int = -1, models: bool = False, **kw):
+        """removes the rows on plane `which` (-1: on any found plane) (ef_map_remove_planes: what eraseRows(planeSelect(...)) leaves).  The
+        dict of ef_plane_result: {"nodes", "planes", "on_rows", "off_rows", "count_after"}; models=True: (result, list of model dicts)"""
+        params, among, pa = self._planeArgs(params, among, kw)
+        mods = (ef_plane_model * PLANE_MAX_PLANES)()
+        res = ef_plane_result()
+        _chk(lib().ef_map_remove_planes(self.h, C.byref(params), pa, int(which), mods, C.byref(res)), self.h)
+        return (self._planeResult(res), self._planeModels(mods, res.planes)) if models else self._planeResult(res)
 
     def setReferenceDownload(self, on=True):
         """downloadMap / savePly read what GlobalModel::downloadMap reads (the pre-clean buffer, quirk Q14) instead of model()"""

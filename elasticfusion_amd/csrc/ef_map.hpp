@@ -434,6 +434,61 @@ void component_tally(const ComponentArgs& a, ComponentResult* copy_to, hipStream
 // label[r] / size[r] of the rows r < min(rows, n) (either may be null)
 void component_split(const ComponentArgs& a, uint32_t* label, uint32_t* size, unsigned rows, hipStream_t s);
 
+// ---- segment the map into planes by sequential RANSAC (ef_planes.inc; ef_map_planes of include/ef_hip.h) ----
+constexpr unsigned PLANE_NONE = 0xFFFFFFFFu;                        // EF_PLANE_NONE
+constexpr int PLANE_MAX_PLANES = 16, PLANE_MAX_HYPOTHESES = 4096;   // EF_PLANE_MAX_*
+constexpr int PLANE_AXIS_OFF = 0, PLANE_AXIS_NORMAL = 1, PLANE_AXIS_INPLANE = 2;   // EF_PLANE_AXIS_*
+constexpr int PLANES_ON = 0, PLANES_OFF = 1;                        // EF_PLANES_*
+constexpr int PLANE_CHUNK = 2048;                                   // compacted participants per workgroup of the scoring kernel
+struct PlaneModel {         // ef_plane_model, field for field (ef_host_planes.inc asserts the layout)
+  float normal[3], d;
+  uint32_t inliers, sampled_inliers, hypothesis, valid_hypotheses, participants;
+  float thickness;
+};
+struct PlaneResult {        // ef_plane_result, field for field
+  uint32_t nodes, planes, on_rows, off_rows, count_after;
+};
+struct PlaneRound {         // what one round's kernels hand to the next ones, on the device
+  uint32_t done;            // non-zero: the extraction has ended; every later kernel of the call returns at once
+  uint32_t count, h, valid, M;   // the winner's count and index, the round's valid hypotheses and participants
+  float hn[3], hd;          // the winning hypothesis
+  float a[3];               // its first sample: the anchor of the refinement
+  float n[3], d;            // the final plane: what the labels are tested against
+};
+struct PlaneArgs {
+  SurfelSoA map;
+  unsigned n;               // rows of the map: the length of the per-row arrays below
+  float distance, normal_cos, min_conf;
+  unsigned H, seed, max_planes, min_inliers, refine;
+  int axis_mode;
+  float axis[3], axis_bound;
+  const uint8_t* sel;       // one byte per row, non-zero = the row passes the selection (may be `node` itself); null: every row does
+  uint8_t* node;            // one byte per row: 1 = node (selected, finite, conf > min_conf); every row is written by plane_init
+  uint8_t* part;            // one byte per row: 1 = participant of the current round (a node no earlier round labelled); = sc.flags
+  uint32_t* label;          // per row the plane's index, PLANE_NONE for every other row
+  SelectScratch sc;         // the participants' bytes, their chunk counts and offsets
+  uint32_t* M;              // the current round's number of participants (the scan's total)
+  float4* cpos;             // the participants' {x, y, z, conf}, compacted in ascending row order
+  float4* cnrm;             // their {nx, ny, nz, radius} (normal_cos > 0 only)
+  float4* hyp;              // H hypotheses {n, d}; an invalid one is four NaNs (it then scores 0 by itself)
+  uint32_t* hyp_a;          // H: the compacted index of each hypothesis's first sample
+  uint32_t* counts;         // H inlier counts
+  double* partial;          // 9 x OUTLIER_SUM_LANES: the lanes' partial sums of the refinement
+  PlaneRound* st;
+  PlaneModel* models;       // PLANE_MAX_PLANES, zeroed by the caller
+  PlaneResult* res;         // zeroed by the caller
+};
+// node and label of every row (nothing for an empty map)
+void plane_init(const PlaneArgs& a, hipStream_t s);
+// round k: participants, compaction, hypotheses, scores, the pick, the refinement, the labels.  Grids are sized by a.n; the kernels read the
+// round's M and the done word from device memory, so nothing here waits for the device
+void plane_round(const PlaneArgs& a, unsigned k, hipStream_t s);
+// flags[row] = 1 for the rows of the list (what = PLANES_ON: labelled `which`, any plane for which < 0; PLANES_OFF: every other node), 0 for
+// every other row (every row is written; flags null: nothing), then res->off_rows and res->count_after = n - the PLANES_ON rows of `which`
+void plane_finish(const PlaneArgs& a, int what, int which, uint8_t* flags, hipStream_t s);
+// label[r] of the rows r < min(rows, n), the max_planes models and the result (each may be null)
+void plane_split(const PlaneArgs& a, uint32_t* label, unsigned rows, PlaneModel* models, PlaneResult* res, hipStream_t s);
+
 // ---- fuse surfels into the map (ef_fuse.inc; ef_map_fuse of include/ef_hip.h) ----
 constexpr unsigned long long FUSE_KEY_EMPTY = 0xFFFFFFFFFFFFFFFFull;
 constexpr unsigned FUSE_SKIPPED = 0, FUSE_NOVEL = 1, FUSE_WEIGHTLESS = 2, FUSE_ABSORBED = 3, FUSE_FUSED = 4, FUSE_INSERTED = 5;   // EF_FUSE_*

@@ -11,6 +11,7 @@
 #include "ef_map.hpp"
 #include "ef_zkey.hpp"
 #include "ef_unionfind.hpp"
+#include "ef_plane_fit.hpp"
 
 using namespace ef;
 
@@ -1524,6 +1525,7 @@ void sample_graph(SurfelSoA map, const unsigned* count_dev, int stride, int max_
 #include "ef_carve.inc"
 #include "ef_outlier.inc"
 #include "ef_components.inc"
+#include "ef_planes.inc"
 #include "ef_fuse.inc"
 
 }  // namespace efm

@@ -1159,6 +1159,117 @@ int ef_map_components_select_dev(ef_ctx* ctx, const ef_component_params* params,
                                  uint32_t* rows_dev, uint32_t max_rows, uint32_t* count_dev, ef_component_result* result_dev_or_null);
 int ef_map_remove_components(ef_ctx* ctx, const ef_component_params* params, const ef_map_selection* among_or_null, ef_component_result* result);
 
+/* ---- Segment the map into planes (the sequential RANSAC plane segmentation of point-cloud toolkits).  A reconstructed room is one connected
+ * component until its floor and walls are taken out; this finds them, lists them, and removes them, so that ef_map_components then separates
+ * the objects that stood on the floor.  Off until first used: no plane call, nothing allocated, nothing run, and no frame kernel knows of it.
+ *
+ * Up to max_planes ROUNDS k = 0, 1, ...; each finds one plane n.p + d = 0 among the participants that no earlier round claimed.  Everything
+ * below is specified completely: all f32 arithmetic rounds once per operation, without contraction, in the written order; square roots and
+ * quotients are the correctly rounded IEEE ones.  Every decisive quantity is an integer, and the results are the same bits on every run.
+ *
+ * NODES are the components' (see above): the rows selected by among (every row with among NULL) that have a finite position and
+ * conf > min_conf; their number is result.nodes.  The PARTICIPANTS of round k are the nodes that rounds 0 .. k-1 did not label, in ascending
+ * row order; M is their number, and participant i is the i-th of them.
+ *
+ * SAMPLING.  h32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 on uint32.  base = h32(seed + 0x9E3779B9 * (k + 1)).
+ * Sample j in {0, 1, 2} of hypothesis h in [0, hypotheses) is participant i = ((uint64)h32(base ^ (3 h + j)) * M) >> 32.
+ *
+ * HYPOTHESIS.  From the three sampled positions a, b, c: u = b - a, v = c - a, cr = u x v with cr.x = u.y * v.z - u.z * v.y and so on,
+ * l2 = (cr.x * cr.x + cr.y * cr.y) + cr.z * cr.z.  The hypothesis is INVALID if two of its indices coincide, or if l2 is not finite or not > 0.
+ * Otherwise n = cr / sqrt(l2) (per component) and d = -((n.x * a.x + n.y * a.y) + n.z * a.z).  With an axis mode on, t = (n.x * axis.x +
+ * n.y * axis.y) + n.z * axis.z; if t < 0, n and d are negated; the hypothesis is invalid unless |t| >= axis_bound (EF_PLANE_AXIS_NORMAL) or
+ * |t| <= axis_bound (EF_PLANE_AXIS_INPLANE).
+ *
+ * SCORE.  e = ((n.x * p.x + n.y * p.y) + n.z * p.z) + d.  A participant is an INLIER of a plane iff |e| <= distance and, with normal_cos > 0,
+ * also |(n.x * m.x + n.y * m.y) + n.z * m.z| >= normal_cos for its stored normal m.  A NaN fails either test.  An invalid hypothesis scores 0.
+ * The WINNER has the greatest number of inliers, ties to the lowest h.  If M is 0, or the winner's count is 0 or below min_inliers, the
+ * extraction ends and this round finds no plane.
+ *
+ * REFINEMENT (refine = 1 and the winner's count m >= 3).  With the anchor a = the winner's first sample and q = (double)p - (double)a per inlier,
+ * nine sums are taken in double: q.x, q.y, q.z, and q_i * q_j for xx, xy, xz, yy, yz, zz.  Each is summed BY MAP ROW in the order of "Remove
+ * outlier surfels": lane j of EF_OUTLIER_SUM_LANES adds the rows j, j + P, j + 2P, ... from +0.0, a row that is no inlier adding +0.0, then
+ * twelve rounds of a[i] = a[2i] + a[2i+1].  mean = S1 / m, C_ij = S2_ij / m - mean_i * mean_j; a cyclic Jacobi eigen-decomposition of C with a
+ * fixed number of sweeps in plain double (csrc/ef_plane_fit.hpp is the definition); the normal is the unit eigenvector of the smallest
+ * eigenvalue lambda (ties: the lowest index), flipped so that its double dot product with the hypothesis's normal is >= 0;
+ * d = -(n . (a + mean)); both are rounded to f32, thickness = (float)sqrt(max(lambda, 0)) (the RMS distance of the inliers from the plane).
+ * If anything along the way is not finite, the hypothesis's plane stays.  Without refinement the FINAL plane is the hypothesis's, thickness 0.
+ *
+ * LABELLING.  The participants of round k that are inliers of the FINAL plane get plane[row] = k; inliers is their number.  Every other row
+ * keeps EF_PLANE_NONE.
+ *
+ * ef_plane_model: the final plane, its inliers, the winning hypothesis's count (sampled_inliers) and index, the round's valid hypotheses and
+ * participants, the thickness.  ef_plane_result: nodes; planes = the rounds that found one; on_rows = the labelled rows; off_rows = nodes -
+ * on_rows; count_after = the map count minus the EF_PLANES_ON rows of `which` (ef_map_planes: of all planes).
+ *
+ * ef_map_planes changes nothing.  It writes plane[r] of the rows r < min(max_rows, map count) (plane may be NULL; entries past that are left
+ * as they were), params->max_planes models (entries from result.planes on are all zero bytes) and the optional result.
+ * ef_map_planes_select changes nothing.  what = EF_PLANES_ON: the rows labelled `which` (which = -1: labelled at all); EF_PLANES_OFF: every
+ * OTHER node (which = -1: the nodes on no plane), so that for any `which` the two lists partition the nodes.  which < max_planes; a plane
+ * that was not found has no rows.  The list has ef_map_select's conventions: the first min(max_rows, total) rows in ASCENDING order, *count =
+ * total however small max_rows is, rows may be NULL with max_rows 0, entries past min(max_rows, total) are left as they were.  The _dev
+ * variants take DEVICE pointers for the arrays, count, models and result and only enqueue on the context's stream (all rounds are enqueued
+ * without a host wait), except for what the selection needs and except that they wait for the device once when the scratch grows.
+ * ef_map_remove_planes removes the EF_PLANES_ON rows of `which` and leaves everything exactly as ef_map_erase_rows(that list) would: see "What
+ * an erase leaves behind" above, with one more synchronisation.  result (HOST memory, required): as above for the map as it WAS; count_after
+ * = the map count the call leaves.
+ *
+ * Defaults (ef_default_plane_params): distance 0.01 m, normal_cos 0, min_conf -1, hypotheses 1024, seed 0, max_planes 4, min_inliers 500,
+ * refine 1, axis_mode EF_PLANE_AXIS_OFF, axis (0, 0, 1), axis_bound 0.95.
+ *
+ * EF_EINVAL, before any GPU work (the arguments are checked before the context, so with a NULL context ef_last_error(NULL) names what is wrong
+ * with them): a NULL context, params, count or (ef_map_remove_planes) result; distance not finite and positive; normal_cos or axis_bound
+ * outside [0, 1] or NaN; NaN min_conf; hypotheses outside 1 .. EF_PLANE_MAX_HYPOTHESES; max_planes outside 1 .. EF_PLANE_MAX_PLANES; refine
+ * > 1; axis_mode outside its three values; with an axis mode on, an axis whose f32 squared norm (x * x + y * y) + z * z is outside
+ * [0.99, 1.01] (it is used as given, not normalised); what outside its two values; which outside -1 .. max_planes - 1; max_rows > 0 with NULL
+ * rows; with among given, everything ef_map_select refuses for a selection.
+ * EF_ESTATE: the context's stream is being captured; with among given, what ef_map_select answers with EF_ESTATE.  ef_map_remove_planes only:
+ * a context created with close_loops = 1 (the erase's reason; the map is unchanged); the other calls work on such contexts. */
+#define EF_PLANE_NONE 0xFFFFFFFFu      /* plane[] of a row that lies on no found plane */
+#define EF_PLANE_MAX_PLANES 16
+#define EF_PLANE_MAX_HYPOTHESES 4096
+#define EF_PLANE_AXIS_OFF 0            /* no constraint */
+#define EF_PLANE_AXIS_NORMAL 1         /* |n . axis| >= axis_bound: planes perpendicular to axis (a floor, axis = up) */
+#define EF_PLANE_AXIS_INPLANE 2        /* |n . axis| <= axis_bound: planes parallel to axis (walls) */
+#define EF_PLANES_ON 0                 /* rows that lie on a found plane */
+#define EF_PLANES_OFF 1                /* participants that lie on none */
+typedef struct ef_plane_params {
+  float distance;         /* inlier iff |n.p + d| <= distance */
+  float normal_cos;       /* > 0: also |n . surfel normal| >= normal_cos; 0: off */
+  float min_conf;         /* as ef_component_params */
+  uint32_t hypotheses;    /* H per round, 1 .. EF_PLANE_MAX_HYPOTHESES */
+  uint32_t seed;
+  uint32_t max_planes;    /* 1 .. EF_PLANE_MAX_PLANES */
+  uint32_t min_inliers;   /* a round whose best hypothesis has fewer ends the extraction */
+  uint32_t refine;        /* 0 / 1: least-squares plane through the winner's inliers */
+  uint32_t axis_mode;     /* EF_PLANE_AXIS_* */
+  float axis[3];          /* used as given; must be unit (see EF_EINVAL) */
+  float axis_bound;
+} ef_plane_params;
+typedef struct ef_plane_model {
+  float normal[3]; float d;     /* n.p + d = 0 */
+  uint32_t inliers;             /* rows labelled with this plane (final plane) */
+  uint32_t sampled_inliers;     /* the winning hypothesis's count */
+  uint32_t hypothesis;          /* its index h */
+  uint32_t valid_hypotheses;
+  uint32_t participants;        /* M of this round */
+  float thickness;              /* refine: (float)sqrt(max(lambda_min, 0)); else 0 */
+} ef_plane_model;
+typedef struct ef_plane_result {
+  uint32_t nodes, planes, on_rows, off_rows, count_after;
+} ef_plane_result;
+int ef_default_plane_params(ef_ctx* ctx, ef_plane_params* params);
+int ef_map_planes(ef_ctx* ctx, const ef_plane_params* params, const ef_map_selection* among_or_null, uint32_t* plane_or_null, uint32_t max_rows,
+                  ef_plane_model* models_or_null, ef_plane_result* result_or_null);
+int ef_map_planes_dev(ef_ctx* ctx, const ef_plane_params* params, const ef_map_selection* among_or_null, uint32_t* plane_dev_or_null,
+                      uint32_t max_rows, ef_plane_model* models_dev_or_null, ef_plane_result* result_dev_or_null);
+int ef_map_planes_select(ef_ctx* ctx, const ef_plane_params* params, const ef_map_selection* among_or_null, int what, int which, uint32_t* rows,
+                         uint32_t max_rows, uint32_t* count, ef_plane_model* models_or_null, ef_plane_result* result_or_null);
+int ef_map_planes_select_dev(ef_ctx* ctx, const ef_plane_params* params, const ef_map_selection* among_or_null, int what, int which,
+                             uint32_t* rows_dev, uint32_t max_rows, uint32_t* count_dev, ef_plane_model* models_dev_or_null,
+                             ef_plane_result* result_dev_or_null);
+int ef_map_remove_planes(ef_ctx* ctx, const ef_plane_params* params, const ef_map_selection* among_or_null, int which,
+                         ef_plane_model* models_or_null, ef_plane_result* result);
+
 /* named internal images, copied to HOST (synchronises); for tests and for a front-end's drawing code */
 enum ef_image {
   EF_IMG_DEPTH_FILTERED = 0,      /* u16  */
