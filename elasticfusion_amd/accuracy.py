@@ -156,6 +156,61 @@ def without_planes(ef: "api.ElasticFusion", **params) -> np.ndarray:
     return ef.gatherSurfels(ef.planeSelect(what=api.PLANES_OFF, **params))
 
 
+def estimated_normals(ef: "api.ElasticFusion", **params) -> np.ndarray:
+    """a gathered copy of the surfels whose normal the map's own geometry determines (the ESTIMATED rows, ascending), [k, 12] float32 as
+    downloadMap() gives them with floats 8 .. 10 replaced by the estimate and, with set_radius, float 11 by radius_scale * spacing: what
+    reestimateNormals with the same arguments would leave of those rows.  The map does not change and is not downloaded: estimateNormals +
+    gatherSurfels (ef_map_normals + ef_map_gather).  The keywords (params, among, ef_normal_params fields) as estimateNormals takes them."""
+    est = ef.estimateNormals(**params)
+    rows = np.nonzero(est["status"] == api.NORMAL_ESTIMATED)[0].astype(np.uint32)
+    out = ef.gatherSurfels(rows)
+    out[:, 8:11] = est["normals"][rows]
+    p = params.get("params")
+    set_radius, scale = (p.set_radius, p.radius_scale) if p is not None else (params.get("set_radius", 0), params.get("radius_scale", 1.0))
+    if set_radius:
+        out[:, 11] = np.float32(scale) * est["spacing"][rows]
+    return out
+
+
+CLOUD_RADIUS = 2.0 ** -20     # insert_cloud's placeholder radius: a value no frame and no spacing produces, so that it marks the inserted rows
+
+
+def insert_cloud(ef: "api.ElasticFusion", points: np.ndarray, colours=None, viewpoint=(0.0, 0.0, 0.0), T=None, confidence: float | None = None,
+                 min_separation: float = 0.01, side: int = -1, **normal) -> tuple:
+    """Adds a cloud that has no normals (a LiDAR sweep, a photogrammetry cloud, a mesh's vertices) to ef's map: [m, 3] points in their own
+    frame, moved by T (4 x 4, cloud -> map; None: as they are), optional colours [m, 3] uint8.  The records are built with a ZERO normal and
+    the placeholder radius CLOUD_RADIUS and inserted with min_normal_cos = -1 (insertSurfels: the points the map already holds within
+    min_separation are dropped); then the normals AND radii of the inserted rows alone are estimated from the map's geometry, old rows
+    counting as neighbours (reestimateNormals among the inserted rows, set_radius = 1, VIEWPOINT orientation: `viewpoint` is the sensor's
+    position in the MAP frame, side = -1 the map's convention).  The inserted rows are selected by their ID range where surfel IDs are on,
+    otherwise by the creation time the insert gave them (the context's tick) together with the placeholder radius.  confidence None: just
+    above the context's threshold, so that the rows are stable.  Other keywords are ef_normal_params fields (radius, k, radius_scale, ...).
+    An inserted row whose neighbourhood is SPARSE or DEGENERATE keeps the zero normal and the placeholder radius: normalSelect lists them.
+    Returns (the insert's result, the re-estimate's result)."""
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    rec = np.zeros((len(pts), 12), np.float32)
+    rec[:, :3] = pts
+    rec[:, 3] = float(ef.cfg.confidence) + 1.0 if confidence is None else float(confidence)
+    if colours is None:
+        rec[:, 4] = float(0x808080)
+    else:
+        c = np.ascontiguousarray(colours, np.uint8).reshape(-1, 3).astype(np.int64)
+        rec[:, 4] = ((c[:, 0] << 16) + (c[:, 1] << 8) + c[:, 2]).astype(np.float32)
+    rec[:, 11] = CLOUD_RADIUS
+    tick = ef.insertParams().init_time
+    ins = ef.insertSurfels(rec, T=T, min_separation=float(min_separation), min_normal_cos=-1.0, init_time=tick, last_time=tick)
+    n1 = ins["count_after"]
+    n0 = n1 - ins["inserted"]
+    ends = ef.gatherSurfels(np.array([n0, n1 - 1], np.uint32))[:, 5].view(np.uint32) if n1 > n0 else np.zeros(2, np.uint32)
+    if ends[0] and ends[1]:      # surfel IDs are on (the ID lane is zero otherwise); the gather has numbered the new rows, ascending by row
+        among = dict(tests=api.SEL_ID, id_min=int(ends[0]), id_max=int(ends[1]))
+    else:
+        among = dict(tests=api.SEL_INIT_TIME | api.SEL_RADIUS, init_time_min=tick, init_time_max=tick, radius_min=CLOUD_RADIUS,
+                     radius_max=CLOUD_RADIUS)
+    kw = dict(dict(set_radius=1), **normal)
+    return ins, ef.reestimateNormals(among=among, orientation=api.NORMALS_VIEWPOINT, side=int(side), viewpoint=tuple(float(v) for v in viewpoint), **kw)
+
+
 def map_accuracy(ef: "api.ElasticFusion", gt_surfels: np.ndarray, max_dist: float = 0.05, map_rows=None, gt_rows=None, device: int = 0,
                  align: bool = False, align_schedule=REGISTER_SCHEDULE) -> dict:
     """ef: a context with a map; gt_surfels: [m, 12] float32, laid out as downloadMap() gives them (synth.sample_surfels), in the map's world

@@ -176,7 +176,19 @@ class ef_plane_result(C.Structure):
     _fields_ = [("nodes", c_u32), ("planes", c_u32), ("on_rows", c_u32), ("off_rows", c_u32), ("count_after", c_u32)]
 
 
+class ef_normal_params(C.Structure):
+    _fields_ = [("radius", c_f), ("cell", c_f), ("min_conf", c_f), ("k", c_i), ("min_neighbors", c_i), ("orientation", c_i), ("side", c_i),
+                ("viewpoint", c_f * 3), ("line_ratio", c_f), ("max_curvature", c_f), ("set_radius", c_i), ("radius_scale", c_f)]
+
+
+class ef_normal_result(C.Structure):
+    _fields_ = [("participants", c_u32), ("estimated", c_u32), ("sparse", c_u32), ("degenerate", c_u32), ("flipped", c_u32), ("listed", c_u32)]
+
+
 CARVE_MAX_VIEWS = 32   # EF_CARVE_MAX_VIEWS of include/ef_hip.h
+NORMALS_KEEP_SIDE, NORMALS_VIEWPOINT = 0, 1         # EF_NORMALS_KEEP_SIDE / _VIEWPOINT of include/ef_hip.h: how an estimate is oriented
+NORMAL_NONE, NORMAL_ESTIMATED, NORMAL_SPARSE, NORMAL_DEGENERATE = 0, 1, 2, 3   # EF_NORMAL_*: a row's status byte (the last three also `what`)
+NORMALS_CURVED, NORMALS_FLAT = 4, 5                 # EF_NORMALS_CURVED / _FLAT: `what` of ef_map_normals_select beside the three statuses
 PLANE_NONE = 0xFFFFFFFF                              # EF_PLANE_NONE of include/ef_hip.h: plane[] of a row on no found plane
 PLANE_MAX_PLANES, PLANE_MAX_HYPOTHESES = 16, 4096   # EF_PLANE_MAX_*
 PLANE_AXIS_OFF, PLANE_AXIS_NORMAL, PLANE_AXIS_INPLANE = 0, 1, 2   # EF_PLANE_AXIS_*: the constraint on a plane's normal
@@ -1630,6 +1642,80 @@ class ElasticFusion:
         res = ef_plane_result()
         _chk(lib().ef_map_remove_planes(self.h, C.byref(params), pa, int(which), mods, C.byref(res)), self.h)
         return (self._planeResult(res), self._planeModels(mods, res.planes)) if models else self._planeResult(res)
+
+    # --- estimate normals, curvature and spacing from the map's neighbourhoods (ef_map_normals / ef_map_normals_select / ef_map_reestimate_normals) ---
+    def normalParams(self, **kw) -> ef_normal_params:
+        """ef_default_normal_params (radius 0.03, cell 0.03, min_conf -1, k 12, min_neighbors 5, NORMALS_KEEP_SIDE, side -1, viewpoint (0, 0, 0),
+        line_ratio 1e-4, max_curvature 0.05, set_radius 0, radius_scale 1) with fields replaced by keyword; viewpoint: three floats"""
+        if "viewpoint" in kw:
+            kw = dict(kw, viewpoint=(c_f * 3)(*[float(v) for v in kw["viewpoint"]]))
+        return self._params(ef_normal_params, lib().ef_default_normal_params, kw, "normal")
+
+    def _normalArgs(self, params, among, kw):
+        if params is None:
+            params = self.normalParams(**kw)
+        else:
+            assert not kw, "give params or keywords, not both"
+        if isinstance(among, dict):
+            among = self.mapSelection(**among)
+        return params, among, (C.byref(among) if among is not None else None)
+
+    @staticmethod
+    def _normalResult(res: ef_normal_result) -> dict:
+        return {k: int(getattr(res, k)) for k, _ in ef_normal_result._fields_}
+
+    def estimateNormals(self, params: ef_normal_params | None = None, among=None, **kw) -> dict:
+        """per row of downloadMap(): {"normals" float32 [n, 3], "curvature" float32, "spacing" float32, "count" uint32, "status" uint8
+        (api.NORMAL_*)}: the PCA normal of the k nearest other surfels within radius, oriented by params.orientation, the surface variation,
+        the mean distance to the used neighbours and the number of ALL neighbours; the map does not change.  among: an ef_map_selection, a dict
+        of mapSelection keywords or None (every surfel participates); other keywords are ef_normal_params fields"""
+        params, among, pa = self._normalArgs(params, among, kw)
+        n = self.lastCount()
+        m = max(n, 1)
+        out = dict(normals=np.zeros((m, 3), np.float32), curvature=np.zeros(m, np.float32), spacing=np.zeros(m, np.float32),
+                   count=np.zeros(m, np.uint32), status=np.zeros(m, np.uint8))
+        _chk(lib().ef_map_normals(self.h, C.byref(params), pa, _ptr(out["normals"]), _ptr(out["curvature"]), _ptr(out["spacing"]),
+                                  _ptr(out["count"]), _ptr(out["status"]), n), self.h)
+        return {k: v[:n] for k, v in out.items()}
+
+    def estimateNormalsDevice(self, params: ef_normal_params, among, normals_dev, curvature_dev, spacing_dev, count_dev, status_dev, max_rows: int):
+        """ef_map_normals_dev: raw device pointers (int, c_void_p or None) for max_rows x 3 floats, max_rows floats twice, max_rows uint32 and
+        max_rows bytes, enqueued on the context's stream"""
+        params, among, pa = self._normalArgs(params, among, {})
+        _chk(lib().ef_map_normals_dev(self.h, C.byref(params), pa, _dev(normals_dev), _dev(curvature_dev), _dev(spacing_dev), _dev(count_dev),
+                                      _dev(status_dev), int(max_rows)), self.h)
+
+    def normalSelect(self, params: ef_normal_params | None = None, among=None, what: int = NORMAL_ESTIMATED, max_rows: int | None = None,
+                     count: bool = False, result: bool = False, **kw):
+        """the rows `what` names (NORMAL_ESTIMATED / _SPARSE / _DEGENERATE, NORMALS_CURVED: estimated and curvature > max_curvature,
+        NORMALS_FLAT: estimated and not curved) in ascending order (uint32), at most max_rows of them (None: all); the map does not change.
+        among and the keywords as estimateNormals takes them.  count=True adds the total, result=True the dict of ef_normal_result:
+        rows[, total][, result]"""
+        params, among, pa = self._normalArgs(params, among, kw)
+        cap = self.lastCount() if max_rows is None else int(max_rows)
+        rows = np.zeros(max(cap, 1), np.uint32)
+        total = c_u32(0)
+        res = ef_normal_result()
+        _chk(lib().ef_map_normals_select(self.h, C.byref(params), pa, int(what), _ptr(rows) if cap else None, cap, C.byref(total),
+                                         C.byref(res) if result else None), self.h)
+        out = (rows[:min(cap, total.value)].copy(),) + ((total.value,) if count else ()) + ((self._normalResult(res),) if result else ())
+        return out if len(out) > 1 else out[0]
+
+    def normalSelectDevice(self, params: ef_normal_params, among, what: int, rows_dev, max_rows: int, count_dev, result_dev=None):
+        """ef_map_normals_select_dev: raw device pointers (int, c_void_p or None for rows with max_rows 0 and for the result), enqueued on the
+        context's stream"""
+        params, among, pa = self._normalArgs(params, among, {})
+        _chk(lib().ef_map_normals_select_dev(self.h, C.byref(params), pa, int(what), _dev(rows_dev), int(max_rows), _dev(count_dev),
+                                             _dev(result_dev)), self.h)
+
+    def reestimateNormals(self, params: ef_normal_params | None = None, among=None, **kw) -> dict:
+        """writes the estimate into the normal of every ESTIMATED row and, with set_radius, radius_scale * spacing into its radius
+        (ef_map_reestimate_normals); every other word of the map keeps its bits.  The dict of ef_normal_result: {"participants", "estimated",
+        "sparse", "degenerate", "flipped", "listed"}"""
+        params, among, pa = self._normalArgs(params, among, kw)
+        res = ef_normal_result()
+        _chk(lib().ef_map_reestimate_normals(self.h, C.byref(params), pa, C.byref(res)), self.h)
+        return self._normalResult(res)
 
     def setReferenceDownload(self, on=True):
         """downloadMap / savePly read what GlobalModel::downloadMap reads (the pre-clean buffer, quirk Q14) instead of model()"""

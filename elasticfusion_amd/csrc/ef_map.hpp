@@ -489,6 +489,43 @@ void plane_finish(const PlaneArgs& a, int what, int which, uint8_t* flags, hipSt
 // label[r] of the rows r < min(rows, n), the max_planes models and the result (each may be null)
 void plane_split(const PlaneArgs& a, uint32_t* label, unsigned rows, PlaneModel* models, PlaneResult* res, hipStream_t s);
 
+// ---- estimate normals, curvature and spacing from the map's neighbourhoods (ef_normals.inc; ef_map_normals of include/ef_hip.h) ----
+constexpr int NORMALS_KEEP_SIDE = 0, NORMALS_VIEWPOINT = 1;                                   // EF_NORMALS_KEEP_SIDE / _VIEWPOINT
+constexpr unsigned NORMAL_NONE = 0, NORMAL_ESTIMATED = 1, NORMAL_SPARSE = 2, NORMAL_DEGENERATE = 3;   // EF_NORMAL_*: the status byte
+constexpr int NORMALS_CURVED = 4, NORMALS_FLAT = 5;                                           // EF_NORMALS_*: `what` beside the three statuses
+constexpr unsigned NORMAL_STATUS_MASK = 3u, NORMAL_FLIPPED = 4u;   // the scratch's byte: the status, and the bit of an estimate the orientation turned
+struct NormalResult {       // ef_normal_result, field for field (ef_host_normals.inc asserts the layout)
+  uint32_t participants, estimated, sparse, degenerate, flipped, listed;
+};
+struct NormalArgs {
+  QueryArgs q;              // the index built at the call's cell and the live map; max_dist = radius, r2, min_conf (points, n, k, outputs unused)
+  unsigned n;               // rows of the map: the length of the per-row arrays below
+  int k;                    // neighbours used: 3 .. 16
+  unsigned min_neighbors;
+  int orientation;          // NORMALS_*
+  float side;               // +1 / -1 (VIEWPOINT)
+  float view[3];
+  float line_ratio, max_curvature;
+  int set_radius;
+  float radius_scale;
+  const uint8_t* part_in;   // one byte per row, non-zero = the row passes the selection (may be `status` itself); null: every row does
+  float4* est;              // per row {normal, curvature}; every row is written by the join
+  uint2* stat;              // per row {bits of spacing, count}; every row is written by the join
+  uint8_t* status;          // per row NORMAL_* | NORMAL_FLIPPED; every row is written by the join
+  NormalResult* res;        // the call's result on the device
+};
+// est, stat and status of every row: one lane per record of the index, in index order; nothing is launched for an empty map
+void normal_join(const NormalArgs& a, hipStream_t s);
+// flags[row] = 1 for the rows `what` names, 0 for every other row (every row is written)
+void normal_flags(const NormalArgs& a, int what, uint8_t* flags, hipStream_t s);
+// *a.res (zeroed here first) from the status bytes, listed = *total (0 with total null); then *copy_to = *res unless copy_to is null
+void normal_tally(const NormalArgs& a, const uint32_t* total, NormalResult* copy_to, hipStream_t s);
+// the optional per-row outputs of the rows r < min(rows, n) from the packed words (each may be null)
+void normal_split(const NormalArgs& a, float* normals3, float* curvature, float* spacing, uint32_t* count, uint8_t* status, unsigned rows,
+                  hipStream_t s);
+// the write-back: floats 8 .. 10 (and 11 with set_radius) of every ESTIMATED row of a.q.map, in place
+void normal_apply(const NormalArgs& a, hipStream_t s);
+
 // ---- fuse surfels into the map (ef_fuse.inc; ef_map_fuse of include/ef_hip.h) ----
 constexpr unsigned long long FUSE_KEY_EMPTY = 0xFFFFFFFFFFFFFFFFull;
 constexpr unsigned FUSE_SKIPPED = 0, FUSE_NOVEL = 1, FUSE_WEIGHTLESS = 2, FUSE_ABSORBED = 3, FUSE_FUSED = 4, FUSE_INSERTED = 5;   // EF_FUSE_*

@@ -1526,6 +1526,7 @@ void sample_graph(SurfelSoA map, const unsigned* count_dev, int stride, int max_
 #include "ef_outlier.inc"
 #include "ef_components.inc"
 #include "ef_planes.inc"
+#include "ef_normals.inc"
 #include "ef_fuse.inc"
 
 }  // namespace efm

@@ -11,6 +11,8 @@
 //               depends on a convergence test); the normal is the eigenvector of the smallest eigenvalue (ties: the lowest index), normalised,
 //               flipped to the hypothesis's side; d = -(n . (a + mean)).
 //   OUTPUT      false, and nothing written, when m < 3 or anything along the way is not finite: the caller keeps the hypothesis's plane.
+//   PARTS       plane_fit_eigen (the moments to the diagonalised A, V) and plane_fit_normal (the choice, the normalisation, the flip) are shared
+//               with normal_fit at the end of this file, the per-surfel fit of ef_map_normals; plane_fit adds the offset and the thickness.
 #pragma once
 
 #if defined(__HIPCC__)
@@ -52,11 +54,12 @@ EF_PF_HD void plane_fit_rotate(double A[3][3], double V[3][3], int p, int q, int
   }
 }
 
-EF_PF_HD bool plane_fit(const double S[9], unsigned m, const float a[3], const float hn[3], float n_out[3], float* d_out, float* thickness_out) {
+// The part both fits share, up to the diagonalised matrix: mean = S1 / m, the covariance A, the fixed sweeps; A's diagonal then holds the
+// eigenvalues and V's columns the eigenvectors.  false when m < 3 or the covariance is not finite.
+EF_PF_HD bool plane_fit_eigen(const double S[9], unsigned m, double A[3][3], double V[3][3], double mean[3]) {
   if (m < 3u) return false;
   const double md = (double)m;
   const double mx = S[0] / md, my = S[1] / md, mz = S[2] / md;
-  double A[3][3], V[3][3];
   A[0][0] = S[3] / md - mx * mx;
   A[0][1] = S[4] / md - mx * my;
   A[0][2] = S[5] / md - mx * mz;
@@ -76,6 +79,17 @@ EF_PF_HD bool plane_fit(const double S[9], unsigned m, const float a[3], const f
     plane_fit_rotate(A, V, 0, 2, 1);
     plane_fit_rotate(A, V, 1, 2, 0);
   }
+  mean[0] = mx;
+  mean[1] = my;
+  mean[2] = mz;
+  return true;
+}
+
+// The eigenvector of the smallest eigenvalue (ties: the lowest index), normalised and flipped to hn's side (a zero or NaN hn flips nothing).
+// n = the normal, l = the three diagonal entries, lambda = the chosen one, flipped = whether the sign was turned.  false, and nothing written,
+// when the choice or the normalisation is not finite.
+EF_PF_HD bool plane_fit_normal(const double A[3][3], const double V[3][3], const float hn[3], double n[3], double l[3], double* lambda_out,
+                               bool* flipped) {
   // (every entry is read unconditionally and chosen by value: a choice between two ADDRESSES of V would put the matrix into the device's scratch)
   const double l0 = A[0][0], l1 = A[1][1], l2 = A[2][2];
   const double v00 = V[0][0], v10 = V[1][0], v20 = V[2][0], v01 = V[0][1], v11 = V[1][1], v21 = V[2][1], v02 = V[0][2], v12 = V[1][2], v22 = V[2][2];
@@ -88,11 +102,29 @@ EF_PF_HD bool plane_fit(const double S[9], unsigned m, const float a[3], const f
   nx = nx / len;
   ny = ny / len;
   nz = nz / len;
-  if ((nx * (double)hn[0] + ny * (double)hn[1]) + nz * (double)hn[2] < 0.0) {
+  const bool flip = (nx * (double)hn[0] + ny * (double)hn[1]) + nz * (double)hn[2] < 0.0;
+  if (flip) {
     nx = -nx;
     ny = -ny;
     nz = -nz;
   }
+  n[0] = nx;
+  n[1] = ny;
+  n[2] = nz;
+  l[0] = l0;
+  l[1] = l1;
+  l[2] = l2;
+  *lambda_out = lambda;
+  *flipped = flip;
+  return true;
+}
+
+EF_PF_HD bool plane_fit(const double S[9], unsigned m, const float a[3], const float hn[3], float n_out[3], float* d_out, float* thickness_out) {
+  double A[3][3], V[3][3], mean[3], n[3], l[3], lambda;
+  bool flipped;
+  if (!plane_fit_eigen(S, m, A, V, mean)) return false;
+  if (!plane_fit_normal(A, V, hn, n, l, &lambda, &flipped)) return false;
+  const double nx = n[0], ny = n[1], nz = n[2], mx = mean[0], my = mean[1], mz = mean[2];
   const double d = -((nx * ((double)a[0] + mx) + ny * ((double)a[1] + my)) + nz * ((double)a[2] + mz));
   const double th = __builtin_sqrt(lambda > 0.0 ? lambda : 0.0);
   if (!plane_fit_finite(nx) || !plane_fit_finite(ny) || !plane_fit_finite(nz) || !plane_fit_finite(d) || !plane_fit_finite(th)) return false;
@@ -104,6 +136,46 @@ EF_PF_HD bool plane_fit(const double S[9], unsigned m, const float a[3], const f
   *d_out = fd;
   *thickness_out = ft;
   return true;
+}
+
+// ---- the normals' entry point (ef_normals.inc: k_normal_join; "Estimate normals, curvature and spacing" of include/ef_hip.h) ----
+constexpr int NORMAL_FIT_GAVE_UP = 0, NORMAL_FIT_ESTIMATED = 1, NORMAL_FIT_DEGENERATE = 2;
+
+// From the nine sums over the m members of a neighbourhood (the anchor is the row's own position, so no plane offset is formed) to the
+// oriented normal, the surface variation and the verdict.  With e_i = max(l_i, 0) by comparison: curvature = emin / ((e_0 + e_1) + e_2),
+// 0 when the sum is not > 0; DEGENERATE iff !(emid > (double)line_ratio * emax), emax and emid chosen by comparisons.  Every output is
+// written in every case: n_out, curvature_out and flipped_out are zeros and false unless the return value is NORMAL_FIT_ESTIMATED; l_out = the
+// three diagonal entries of the diagonalised covariance as computed (not clamped), zeros when the fit gave up.
+EF_PF_HD int normal_fit(const double S[9], unsigned m, const float hn[3], float line_ratio, float n_out[3], float* curvature_out, bool* flipped_out,
+                        double l_out[3]) {
+  n_out[0] = n_out[1] = n_out[2] = 0.0f;
+  *curvature_out = 0.0f;
+  *flipped_out = false;
+  l_out[0] = l_out[1] = l_out[2] = 0.0;
+  double A[3][3], V[3][3], mean[3], n[3], l[3], lambda;
+  bool flipped;
+  if (!plane_fit_eigen(S, m, A, V, mean)) return NORMAL_FIT_GAVE_UP;
+  if (!plane_fit_normal(A, V, hn, n, l, &lambda, &flipped)) return NORMAL_FIT_GAVE_UP;
+  if (!plane_fit_finite(l[0]) || !plane_fit_finite(l[1]) || !plane_fit_finite(l[2]) || !plane_fit_finite(n[0]) || !plane_fit_finite(n[1]) ||
+      !plane_fit_finite(n[2]))
+    return NORMAL_FIT_GAVE_UP;
+  l_out[0] = l[0];
+  l_out[1] = l[1];
+  l_out[2] = l[2];
+  const double e0 = l[0] > 0.0 ? l[0] : 0.0, e1 = l[1] > 0.0 ? l[1] : 0.0, e2 = l[2] > 0.0 ? l[2] : 0.0;
+  const double emin = lambda > 0.0 ? lambda : 0.0;
+  // the greatest and the median of three by comparisons: lo / hi of the first two, then the third against both
+  const double lo = e1 < e0 ? e1 : e0, hi = e1 < e0 ? e0 : e1;
+  const double emax = e2 > hi ? e2 : hi;
+  const double emid = e2 > hi ? hi : (e2 < lo ? lo : e2);
+  if (!(emid > (double)line_ratio * emax)) return NORMAL_FIT_DEGENERATE;
+  const double sum = (e0 + e1) + e2;
+  n_out[0] = (float)n[0];
+  n_out[1] = (float)n[1];
+  n_out[2] = (float)n[2];
+  *curvature_out = sum > 0.0 ? (float)(emin / sum) : 0.0f;
+  *flipped_out = flipped;
+  return NORMAL_FIT_ESTIMATED;
 }
 
 }  // namespace efm

@@ -1270,6 +1270,143 @@ int ef_map_planes_select_dev(ef_ctx* ctx, const ef_plane_params* params, const e
 int ef_map_remove_planes(ef_ctx* ctx, const ef_plane_params* params, const ef_map_selection* among_or_null, int which,
                          ef_plane_model* models_or_null, ef_plane_result* result);
 
+/* ---- Estimate normals, curvature and spacing from the map's neighbourhoods (the PCA normal estimation of point-cloud toolkits).  Every other
+ * map tool takes a surfel's normal and radius as given, and the only producer of normals is a depth frame.  This derives them from the positions
+ * the map holds: for a cloud that came without normals (inserted with a zero normal and a placeholder radius), for a map whose stored normals
+ * no longer describe the geometry after fuse, thin, carve or a merged session, and for the per-surfel surface variation that region growing,
+ * edge extraction and smoothness-weighted thinning start from.  Off until first used: no normal call, nothing allocated, nothing run, and no
+ * frame kernel knows of it.
+ *
+ * "Row", the layout of a surfel (position = floats 0 .. 2, confidence = float 3, normal = floats 8 .. 10, radius = float 11), d2, the rule
+ * "t is ELIGIBLE for q iff conf_t > min_conf and d2 <= r2" with r2 = radius * radius computed once in f32 on the host, the PARTICIPANTS (among
+ * NULL: every row with a finite position; else the rows the selection selects that have a finite position) and the NEIGHBOURS of a participant
+ * (all rows t != s eligible for p_s whether or not t participates, self excluded by ROW, ordered by (d2, row) ascending, count_s = the number
+ * of ALL of them) are exactly those of the section "Remove outlier surfels".  All f32 arithmetic rounds once per operation, without
+ * contraction, in the written order; so does all double arithmetic.
+ *
+ * For a participant s, with k in 3 .. 16:
+ *
+ * NEIGHBOURHOOD.  c = min(count_s, k).  The USED neighbours are the first c in that order, t_1 .. t_c, with d2_1 .. d2_c.
+ *
+ * SPACING.  spacing_s = (((sqrt(d2_1) + sqrt(d2_2)) + ...) + sqrt(d2_c)) / (float)c, summed in neighbour order; every square root and the
+ * quotient are the CORRECTLY ROUNDED f32 operations.  +inf if c = 0.  It equals mean_dist of ef_map_neighbor_stats whenever count_s >= k.
+ *
+ * SPARSE.  Row s is SPARSE iff count_s < (uint32_t)min_neighbors, with min_neighbors in 2 .. k.  A sparse row gets no estimate.
+ *
+ * MOMENTS, in double, in neighbour order.  q_j = ((double)x_j - (double)x_s, (double)y_j - (double)y_s, (double)z_j - (double)z_s) for
+ * j = 1 .. c, from the f32 positions of rows t_j and s.  S[0..2] = the sums of q.x, q.y, q.z; S[3..8] = the sums of q.x * q.x, q.x * q.y,
+ * q.x * q.z, q.y * q.y, q.y * q.z, q.z * q.z.  Each product is rounded once and then added to a running sum that starts at +0.0, j ascending.
+ * m = c + 1: the row itself is a member of its neighbourhood and contributes exact zeros.  The anchor is the row's own position, which keeps
+ * the covariance's cancellation small at any distance from the origin.
+ *
+ * EIGEN-DECOMPOSITION.  From S and m on, csrc/ef_plane_fit.hpp is the definition (its normal_fit; the part up to the diagonalised matrix is the
+ * one ef_map_planes' refinement uses): mean = S[0..2] / m, C_ij = S2_ij / m - mean_i * mean_j, the cyclic Jacobi iteration with its fixed
+ * number of sweeps over the pairs (0,1), (0,2), (1,2).  l_0, l_1, l_2 are the diagonal entries it leaves, the columns of V the eigenvectors.
+ * The smallest l_i is chosen by "l_1 < l_0", then "l_2 < the smaller" (ties: the lowest index); its eigenvector is divided by its length
+ * sqrt((x * x + y * y) + z * z).  The fit GIVES UP if an entry of C, a diagonal entry, the length or a component of the normal is not finite,
+ * or the length is not > 0.
+ *
+ * ORIENTATION.  The unit vector n is negated iff (n.x * (double)hn.x + n.y * (double)hn.y) + n.z * (double)hn.z < 0 for the hint hn (f32):
+ *   EF_NORMALS_KEEP_SIDE   hn = the row's stored normal.  A zero or NaN stored normal, or one exactly perpendicular to n, flips nothing.
+ *   EF_NORMALS_VIEWPOINT   hn = side * (v - p_s), each component one f32 subtraction and one (exact) product with side = +1 or -1.  side = +1
+ *                          orients the normals towards the viewpoint v, side = -1 away from it.  -1 is the map's own convention (a surface
+ *                          seen head-on has the normal +z in the camera, Core/Shaders/geometry.glsl:59) and the default.  A surfel at the
+ *                          viewpoint flips nothing.
+ * The estimate is (float)n per component.  An estimate whose sign was turned is FLIPPED.
+ *
+ * CURVATURE (surface variation).  e_i = l_i > 0 ? l_i : 0;  sum = (e_0 + e_1) + e_2;  emin = the clamped chosen eigenvalue;
+ * curvature = sum > 0 ? (float)(emin / sum) : 0.  It lies in [0, 1/3]: 0 on a plane, 1/3 for an isotropic blob.
+ *
+ * DEGENERATE.  A participant that is not SPARSE is DEGENERATE iff the fit gives up or !(emid > (double)line_ratio * emax), where
+ * lo = e_1 < e_0 ? e_1 : e_0, hi = e_1 < e_0 ? e_0 : e_1, emax = e_2 > hi ? e_2 : hi, emid = e_2 > hi ? hi : (e_2 < lo ? lo : e_2): a
+ * neighbourhood that is a line or a point has no normal.  The eigenvalues are variances: line_ratio 1e-4 means "narrower than 1 % of its
+ * length".  Everything is compared in double on values that are the same bits wherever they are computed.  Every other participant that is not
+ * SPARSE is ESTIMATED.
+ *
+ * STATUS, one byte per row: EF_NORMAL_NONE (the row takes no part), EF_NORMAL_ESTIMATED, EF_NORMAL_SPARSE, EF_NORMAL_DEGENERATE.
+ * OUTPUTS by row: normal[3] = the estimate, (0, 0, 0) unless ESTIMATED; curvature, 0 unless ESTIMATED; spacing, +inf for NONE (and for a
+ * participant without a neighbour); count = count_s, 0 for NONE; status.
+ *
+ * ef_map_normals changes nothing.  It writes the five arrays for the rows r < min(max_rows, map count) (normals3 is [rows][3]; every array may
+ * be NULL; entries past that are left as they were).  ef_map_normals_select changes nothing.  what = EF_NORMAL_ESTIMATED, EF_NORMAL_SPARSE or
+ * EF_NORMAL_DEGENERATE (the rows of that status), EF_NORMALS_CURVED (ESTIMATED and curvature > max_curvature, compared in f32) or
+ * EF_NORMALS_FLAT (ESTIMATED and not CURVED).  The list has ef_map_select's conventions: the first min(max_rows, total) rows in ASCENDING order,
+ * *count = total however small max_rows is, rows may be NULL with max_rows 0, entries past min(max_rows, total) are left as they were; it is
+ * what ef_map_erase_rows and ef_map_gather take.  result (optional): participants, estimated, sparse, degenerate, flipped (the FLIPPED
+ * estimates), listed = total.  The _dev variants take DEVICE pointers for the arrays, count and result and only enqueue on the context's stream,
+ * except for what the selection needs (ID numbering, label alignment, the count after a call that can change the map) and except that they
+ * wait for the device once when the index has to be rebuilt or the scratch grows.
+ *
+ * ef_map_reestimate_normals is the write-back.  For every ESTIMATED row it writes floats 8 .. 10 = the estimate and, with set_radius != 0,
+ * float 11 = radius_scale * spacing (one f32 product).  Every other word of every row keeps its bits (position, confidence, colour, the ID
+ * lane, both times), and a row that is not ESTIMATED keeps everything.  result (HOST memory, required): as above, listed = the rows written.
+ * What a re-estimate leaves behind:
+ *   the map       as described, the count unchanged;
+ *   IDs           with IDs on, the rows created since the last ID-consuming call are numbered before the write, as every edit does; no ID changes;
+ *   the context   the state that ef_map_upload of the edited rows followed by ef_restore_state (tick, ef_get_pose_qt, the last processed frame)
+ *                 would leave: tick, pose, trajectory, last frame and tracking statistics are unchanged, and if ef_process_frame* or
+ *                 ef_restore_state has run on the context the model prediction is renewed from the edited map at the current pose.  On a context
+ *                 whose map was only uploaded, only the map changes;
+ *   the index     of the queries and the registration counts as stale, by the rule of every edit, and is rebuilt by their next call;
+ *   labels        untouched: no row moved, every row keeps its C floats;
+ *   the shadow buffer of ef_set_reference_download is left as it is.
+ * The call synchronises before and after, like the insert.  A call that estimates nothing is valid and still leaves that state.  In
+ * EF_NORMALS_KEEP_SIDE mode without set_radius it is IDEMPOTENT bit for bit: positions do not change, so a second call forms the same n, and
+ * the stored normal it is compared with is (float)n or (float)-n of the first call, whose double dot product with that n cannot be negative.
+ * (With set_radius too: the radius takes no part in the estimate.)
+ *
+ * cell is the cell of the queries' index, which is built at that cell where needed; a later query at another cell rebuilds it, as after
+ * ef_set_query_cell.  No result depends on it.  Defaults (ef_default_normal_params): radius 0.03 m, cell 0.03 m (the outlier filter's measured
+ * choice for the same walk), min_conf -1, k 12, min_neighbors 5, EF_NORMALS_KEEP_SIDE, side -1, viewpoint (0, 0, 0), line_ratio 1e-4 (a
+ * definition, see above, not a measurement), max_curvature 0.05 (likewise), set_radius 0, radius_scale 1.
+ *
+ * Not provided: region growing itself (curvature and the lists are its inputs); smoothing of positions (moving least squares); a method of the
+ * C++ shim; the write-back on loop-closing contexts; normals of a point set that is not in the map (it needs an index over that set: insert
+ * the set first, see accuracy.insert_cloud).
+ *
+ * EF_EINVAL, before any GPU work (the arguments are checked before the context, so with a NULL context ef_last_error(NULL) names what is wrong
+ * with them): a NULL context, params, count or (ef_map_reestimate_normals) result; radius or cell not finite and positive, or 1 / cell not
+ * finite; radius / cell above EF_QUERY_MAX_RATIO; NaN min_conf; k outside 3 .. 16; min_neighbors outside 2 .. k; orientation outside its two
+ * values; side not +1 or -1; in EF_NORMALS_VIEWPOINT mode a non-finite viewpoint coordinate; NaN or negative line_ratio, max_curvature or
+ * radius_scale; what outside its five values; max_rows > 0 with NULL rows; with among given, everything ef_map_select refuses for a selection.
+ * EF_ESTATE: the context's stream is being captured; with among given, what ef_map_select answers with EF_ESTATE.
+ * ef_map_reestimate_normals only: a context created with close_loops = 1 (the erase's reason; the map is unchanged); the other calls work on
+ * such contexts. */
+#define EF_NORMALS_KEEP_SIDE 0     /* orientation: the side of the row's stored normal */
+#define EF_NORMALS_VIEWPOINT 1     /* orientation: towards (side +1) or away from (side -1) params.viewpoint */
+#define EF_NORMAL_NONE       0     /* status: the row takes no part */
+#define EF_NORMAL_ESTIMATED  1     /* status, and `what`: the rows with an estimate */
+#define EF_NORMAL_SPARSE     2     /* status, and `what`: fewer than min_neighbors neighbours */
+#define EF_NORMAL_DEGENERATE 3     /* status, and `what`: a line or a point */
+#define EF_NORMALS_CURVED    4     /* `what`: ESTIMATED and curvature > max_curvature */
+#define EF_NORMALS_FLAT      5     /* `what`: ESTIMATED and not CURVED */
+typedef struct ef_normal_params {
+  float radius; float cell; float min_conf;
+  int k;                  /* neighbours used, 3 .. 16 */
+  int min_neighbors;      /* 2 .. k */
+  int orientation;        /* EF_NORMALS_KEEP_SIDE / EF_NORMALS_VIEWPOINT */
+  int side;               /* VIEWPOINT: +1 towards, -1 away */
+  float viewpoint[3];
+  float line_ratio;
+  float max_curvature;    /* ef_map_normals_select: EF_NORMALS_CURVED / EF_NORMALS_FLAT */
+  int set_radius;         /* ef_map_reestimate_normals: also write the radius */
+  float radius_scale;
+} ef_normal_params;
+typedef struct ef_normal_result {
+  uint32_t participants, estimated, sparse, degenerate, flipped, listed;
+} ef_normal_result;
+int ef_default_normal_params(ef_ctx* ctx, ef_normal_params* params);
+int ef_map_normals(ef_ctx* ctx, const ef_normal_params* params, const ef_map_selection* among_or_null, float* normals3_or_null,
+                   float* curvature_or_null, float* spacing_or_null, uint32_t* count_or_null, uint8_t* status_or_null, uint32_t max_rows);
+int ef_map_normals_dev(ef_ctx* ctx, const ef_normal_params* params, const ef_map_selection* among_or_null, float* normals3_dev_or_null,
+                       float* curvature_dev_or_null, float* spacing_dev_or_null, uint32_t* count_dev_or_null, uint8_t* status_dev_or_null,
+                       uint32_t max_rows);
+int ef_map_normals_select(ef_ctx* ctx, const ef_normal_params* params, const ef_map_selection* among_or_null, int what, uint32_t* rows,
+                          uint32_t max_rows, uint32_t* count, ef_normal_result* result_or_null);
+int ef_map_normals_select_dev(ef_ctx* ctx, const ef_normal_params* params, const ef_map_selection* among_or_null, int what, uint32_t* rows_dev,
+                              uint32_t max_rows, uint32_t* count_dev, ef_normal_result* result_dev_or_null);
+int ef_map_reestimate_normals(ef_ctx* ctx, const ef_normal_params* params, const ef_map_selection* among_or_null, ef_normal_result* result);
+
 /* named internal images, copied to HOST (synchronises); for tests and for a front-end's drawing code */
 enum ef_image {
   EF_IMG_DEPTH_FILTERED = 0,      /* u16  */
