@@ -150,6 +150,24 @@ def plane_segments(ef: "api.ElasticFusion", **params) -> list:
     return [(m, ef.gatherSurfels(order[a:a + m["inliers"]].astype(np.uint32))) for m, a in zip(models, first)]
 
 
+def smooth_regions(ef: "api.ElasticFusion", min_size: int = 50, max_regions: int | None = None, **params) -> list:
+    """ef's map cut along its creases into smooth regions: a list of [k, 12] float32 arrays as downloadMap() gives them, one per region of at
+    least min_size rows (cores and attached borders; with max_size among the keywords, of at most that many), LARGEST FIRST with ties by
+    label (the region's smallest core row), at most max_regions of them, each in ascending row order; the map does not change and is not
+    downloaded: regions + one gatherSurfels per region (ef_map_regions + ef_map_gather).  The keywords (params, among, ef_region_params
+    fields) as regions takes them."""
+    label, size, _ = ef.regions(**params)
+    p = params.get("params")
+    max_size = int(p.max_size if p is not None else params.get("max_size", 0))
+    roots = np.nonzero((label == np.arange(len(label), dtype=np.uint32)) & (size >= max(int(min_size), 1)) & ((max_size == 0) | (size <= max_size)))[0]
+    roots = roots[np.lexsort((roots, -size[roots].astype(np.int64)))]
+    if max_regions is not None:
+        roots = roots[:max_regions]
+    order = np.argsort(label, kind="stable")                # one pass: the rows of every label, ascending within it
+    first = np.searchsorted(label[order], roots)
+    return [ef.gatherSurfels(order[a:a + int(size[r])].astype(np.uint32)) for r, a in zip(roots, first)]
+
+
 def without_planes(ef: "api.ElasticFusion", **params) -> np.ndarray:
     """a gathered copy of the participants that lie on no found plane (the PLANES_OFF rows: what removePlanes leaves of them), [k, 12] float32;
     the map does not change and is not downloaded.  The keywords as plane_segments takes them."""

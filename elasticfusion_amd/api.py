@@ -185,7 +185,23 @@ class ef_normal_result(C.Structure):
     _fields_ = [("participants", c_u32), ("estimated", c_u32), ("sparse", c_u32), ("degenerate", c_u32), ("flipped", c_u32), ("listed", c_u32)]
 
 
+class ef_region_params(C.Structure):
+    _fields_ = [("radius", c_f), ("cell", c_f), ("min_conf", c_f), ("k", c_i), ("min_neighbors", c_i), ("line_ratio", c_f),
+                ("normal_source", c_i), ("two_sided", c_i), ("min_normal_cos", c_f), ("max_curvature", c_f), ("attach_borders", c_i),
+                ("min_size", c_u32), ("max_size", c_u32)]
+
+
+class ef_region_result(C.Structure):
+    _fields_ = [("nodes", c_u32), ("cores", c_u32), ("borders", c_u32), ("attached", c_u32), ("unassigned", c_u32), ("regions", c_u32),
+                ("largest", c_u32), ("rejected_rows", c_u32), ("rejected_regions", c_u32), ("listed", c_u32), ("count_after", c_u32),
+                ("status", c_u32)]
+
+
 CARVE_MAX_VIEWS = 32   # EF_CARVE_MAX_VIEWS of include/ef_hip.h
+REGION_NONE = 0xFFFFFFFF                             # EF_REGION_NONE of include/ef_hip.h: the label of a row without a region
+REGION_KIND_NONE, REGION_KIND_CORE, REGION_KIND_BORDER = 0, 1, 2   # EF_REGION_KIND_*: a row's kind byte
+REGIONS_ESTIMATED, REGIONS_STORED = 0, 1            # EF_REGIONS_ESTIMATED / _STORED: normal_source of ef_region_params
+REGIONS_REJECTED, REGIONS_ACCEPTED, REGIONS_UNASSIGNED, REGIONS_BORDERS = 0, 1, 2, 3   # EF_REGIONS_*: which rows ef_map_regions_select lists
 NORMALS_KEEP_SIDE, NORMALS_VIEWPOINT = 0, 1         # EF_NORMALS_KEEP_SIDE / _VIEWPOINT of include/ef_hip.h: how an estimate is oriented
 NORMAL_NONE, NORMAL_ESTIMATED, NORMAL_SPARSE, NORMAL_DEGENERATE = 0, 1, 2, 3   # EF_NORMAL_*: a row's status byte (the last three also `what`)
 NORMALS_CURVED, NORMALS_FLAT = 4, 5                 # EF_NORMALS_CURVED / _FLAT: `what` of ef_map_normals_select beside the three statuses
@@ -1716,6 +1732,78 @@ class ElasticFusion:
         res = ef_normal_result()
         _chk(lib().ef_map_reestimate_normals(self.h, C.byref(params), pa, C.byref(res)), self.h)
         return self._normalResult(res)
+
+    # --- smooth regions of the map (ef_map_regions / ef_map_regions_select / ef_map_remove_regions) ---
+    def regionParams(self, **kw) -> ef_region_params:
+        """ef_default_region_params (radius 0.03, cell 0.03, min_conf -1, k 12, min_neighbors 5, line_ratio 1e-4, REGIONS_ESTIMATED, two_sided 0,
+        min_normal_cos cos 15 deg, max_curvature 0.05, attach_borders 1, min_size 50, max_size 0) with fields replaced by keyword"""
+        return self._params(ef_region_params, lib().ef_default_region_params, kw, "region")
+
+    def _regionArgs(self, params, among, kw):
+        if params is None:
+            params = self.regionParams(**kw)
+        else:
+            assert not kw, "give params or keywords, not both"
+        if isinstance(among, dict):
+            among = self.mapSelection(**among)
+        return params, among, (C.byref(among) if among is not None else None)
+
+    @staticmethod
+    def _regionResult(res: ef_region_result) -> dict:
+        return {k: int(getattr(res, k)) for k, _ in ef_region_result._fields_}
+
+    def regions(self, params: ef_region_params | None = None, among=None, result: bool = False, **kw):
+        """(label uint32, size uint32, kind uint8) per row of downloadMap(): the smallest core row of the surfel's smooth region (the connected
+        components of the low-curvature surfels under "within radius and normals within min_normal_cos", crease surfels attached to the region
+        of their nearest smooth core), the region's number of rows, and REGION_KIND_*; REGION_NONE and 0 for a row without a region; the map
+        does not change.  among: an ef_map_selection, a dict of mapSelection keywords or None (every surfel participates); other keywords are
+        ef_region_params fields.  result=True adds the dict of ef_region_result"""
+        params, among, pa = self._regionArgs(params, among, kw)
+        n = self.lastCount()
+        label = np.zeros(max(n, 1), np.uint32)
+        size = np.zeros(max(n, 1), np.uint32)
+        kind = np.zeros(max(n, 1), np.uint8)
+        res = ef_region_result()
+        _chk(lib().ef_map_regions(self.h, C.byref(params), pa, _ptr(label), _ptr(size), _ptr(kind), n, C.byref(res)), self.h)
+        return (label[:n], size[:n], kind[:n]) + ((self._regionResult(res),) if result else ())
+
+    def regionSelect(self, params: ef_region_params | None = None, among=None, what: int = REGIONS_REJECTED, max_rows: int | None = None,
+                     count: bool = False, result: bool = False, **kw):
+        """the rows of one list in ascending order (uint32), at most max_rows of them (None: all): the nodes of the rejected regions (what =
+        REGIONS_REJECTED: fewer than min_size or, with max_size != 0, more than max_size rows) or of the accepted ones (REGIONS_ACCEPTED), the
+        borders without a region (REGIONS_UNASSIGNED) or every border, the crease lines (REGIONS_BORDERS); the map does not change.  among
+        and the keywords as regions takes them.  count=True adds the total, result=True the dict of ef_region_result: rows[, total][, result]"""
+        params, among, pa = self._regionArgs(params, among, kw)
+        cap = self.lastCount() if max_rows is None else int(max_rows)
+        rows = np.zeros(max(cap, 1), np.uint32)
+        total = c_u32(0)
+        res = ef_region_result()
+        _chk(lib().ef_map_regions_select(self.h, C.byref(params), pa, int(what), _ptr(rows) if cap else None, cap, C.byref(total),
+                                         C.byref(res) if result else None), self.h)
+        out = (rows[:min(cap, total.value)].copy(),) + ((total.value,) if count else ()) + ((self._regionResult(res),) if result else ())
+        return out if len(out) > 1 else out[0]
+
+    def regionSelectDevice(self, params: ef_region_params, among, what: int, rows_dev, max_rows: int, count_dev, result_dev=None):
+        """ef_map_regions_select_dev: raw device pointers (int, c_void_p or None for rows with max_rows 0 and for the result), enqueued on the
+        context's stream"""
+        params, among, pa = self._regionArgs(params, among, {})
+        _chk(lib().ef_map_regions_select_dev(self.h, C.byref(params), pa, int(what), _dev(rows_dev), int(max_rows), _dev(count_dev),
+                                             _dev(result_dev)), self.h)
+
+    def regionsDevice(self, params: ef_region_params, among, label_dev, size_dev, kind_dev, max_rows: int, result_dev=None):
+        """ef_map_regions_dev: raw device pointers (int, c_void_p or None) for max_rows uint32 twice, max_rows bytes and the result"""
+        params, among, pa = self._regionArgs(params, among, {})
+        _chk(lib().ef_map_regions_dev(self.h, C.byref(params), pa, _dev(label_dev), _dev(size_dev), _dev(kind_dev), int(max_rows),
+                                      _dev(result_dev)), self.h)
+
+    def removeRegions(self, params: ef_region_params | None = None, among=None, what: int = REGIONS_REJECTED, **kw) -> dict:
+        """removes the rows of the list `what` (ef_map_remove_regions: what eraseRows(regionSelect(..., what=what)) leaves); not idempotent:
+        the rows that stay have other neighbours, and with them other normals and curvatures.  The dict of ef_region_result for the map as it
+        was, with listed = the rows removed and count_after = the count left"""
+        params, among, pa = self._regionArgs(params, among, kw)
+        res = ef_region_result()
+        _chk(lib().ef_map_remove_regions(self.h, C.byref(params), pa, int(what), C.byref(res)), self.h)
+        return self._regionResult(res)
 
     def setReferenceDownload(self, on=True):
         """downloadMap / savePly read what GlobalModel::downloadMap reads (the pre-clean buffer, quirk Q14) instead of model()"""

@@ -342,6 +342,12 @@ struct ef_ctx {
     DevBuf scratch;                        // the result | {normal, curvature} per row | {spacing, count} per row | chunk counts | chunk offsets | 4 words | status bytes
     size_t rows = 0;
   } normals;
+  // regions (ef_map_regions, ef_map_regions_select, ef_map_remove_regions; kernels in ef_regions.inc and the normals' join): scratch of its own,
+  // sized by the map's rows, grown by the first call, freed with the context.  The normals' scratch is not touched
+  struct RegionState {
+    DevBuf scratch;                        // the result | {normal, curvature}, the stored-normal word, {spacing, count} per row | parent, attach, label, members per row | chunk counts | chunk offsets | 4 words | status bytes | kind bytes
+    size_t rows = 0;
+  } regions;
   // fuse (ef_map_fuse; kernels in ef_fuse.inc) beside the insert's scratch, which its gate and append use: the election's keys (one per map row),
   // match_row and the outcome bytes (one each per record), and the two counts' words (FuseScratch / fuse_scratch in ef_host_insert.inc, beside
   // append_run, which carves it).  Grown by the first call, freed with the context
@@ -720,7 +726,7 @@ void ctx_free(ef_ctx* c) {
   for (KernelSampler* k : {&c->sample_step, &c->sample_all, &c->sample_splat}) k->release();
   drop_track_graphs(c);
   if (c->debug_stream) { (void)hipStreamSynchronize(c->debug_stream); (void)hipStreamDestroy(c->debug_stream); }
-  for (DevBuf* b : {&c->stage, &c->render.zbuf, &c->labels.index, &c->query.sorted, &c->query.rows, &c->query.cells, &c->reg.slabs, &c->sel.scratch, &c->ins.scratch, &c->thin.scratch, &c->carve.scratch, &c->outlier.scratch, &c->components.scratch, &c->planes.scratch, &c->normals.scratch, &c->fuse.scratch})
+  for (DevBuf* b : {&c->stage, &c->render.zbuf, &c->labels.index, &c->query.sorted, &c->query.rows, &c->query.cells, &c->reg.slabs, &c->sel.scratch, &c->ins.scratch, &c->thin.scratch, &c->carve.scratch, &c->outlier.scratch, &c->components.scratch, &c->planes.scratch, &c->normals.scratch, &c->regions.scratch, &c->fuse.scratch})
     b->release();
   for (int k = 0; k < 2; ++k) {
     if (c->labels.tab[k]) (void)hipFree(c->labels.tab[k]);
@@ -1205,4 +1211,5 @@ int ef_set_depth_cutoff(ef_ctx* c, float v) { if (!c) return EF_EINVAL; c->cfg.d
 #include "ef_host_components.inc"
 #include "ef_host_planes.inc"
 #include "ef_host_normals.inc"
+#include "ef_host_regions.inc"
 #include "ef_host_fuse.inc"

@@ -526,6 +526,40 @@ void normal_split(const NormalArgs& a, float* normals3, float* curvature, float*
 // the write-back: floats 8 .. 10 (and 11 with set_radius) of every ESTIMATED row of a.q.map, in place
 void normal_apply(const NormalArgs& a, hipStream_t s);
 
+// ---- segment the map into smooth regions (ef_regions.inc; ef_map_regions of include/ef_hip.h) ----
+constexpr unsigned REGION_NONE = 0xFFFFFFFFu;                                                 // EF_REGION_NONE
+constexpr unsigned REGION_KIND_NONE = 0, REGION_KIND_CORE = 1, REGION_KIND_BORDER = 2;        // EF_REGION_KIND_*: the kind byte
+constexpr int REGIONS_ESTIMATED = 0, REGIONS_STORED = 1;                                      // EF_REGIONS_ESTIMATED / _STORED: normal_source
+constexpr int REGIONS_REJECTED = 0, REGIONS_ACCEPTED = 1, REGIONS_UNASSIGNED = 2, REGIONS_BORDERS = 3;   // EF_REGIONS_*: `what`
+struct RegionResult {       // ef_region_result, field for field (ef_host_regions.inc asserts the layout)
+  uint32_t nodes, cores, borders, attached, unassigned, regions, largest, rejected_rows, rejected_regions, listed, count_after, status;
+};
+struct RegionArgs {
+  NormalArgs nrm;           // the estimate's arguments and outputs (normal_join, unchanged): q, n, est, stat, status by row
+  float min_normal_cos, max_curvature;
+  int two_sided, normal_source, attach_borders;
+  unsigned min_size, max_size;
+  const float4* nw;         // per row {n_s, curvature}: nrm.est itself (REGIONS_ESTIMATED) or `stored`, which region_init fills (REGIONS_STORED)
+  float4* stored;
+  uint8_t* kind;            // one byte per row: REGION_KIND_*; every row is written by region_init
+  uint32_t* parent;         // the union-find's word per row (ef_unionfind.hpp); REGION_NONE for a row that is no core
+  uint32_t* attach;         // per row the core a border joins, REGION_NONE for every other row and for a border without one
+  uint32_t* label;          // per row the smallest core row of its region, REGION_NONE for a row without a region
+  uint32_t* members;        // members[l] = cores and attached borders of the region labelled l (0 at every row that is no label)
+  RegionResult* res;        // the call's result on the device, zeroed by region_hook's caller; status != 0: a loop cap tripped
+};
+// kind, parent, attach and members of every row (and `stored`), the link to the smallest lower smooth core neighbour, then every core edge's
+// union (one lane per record of the index, in index order), with pointer-jumping passes after each of the two, then the borders' attachment
+// (attach_borders != 0 only).  a.nrm's join has been enqueued before.  Nothing for an empty map
+void region_hook(const RegionArgs& a, hipStream_t s);
+// label and members; then the result's counts but count_after and, unless flags is null, flags[row] = 1 for the rows of the list `what`
+// (REGIONS_*), 0 for every other row; res->listed = the number of those rows whether or not flags is null
+void region_label(const RegionArgs& a, int what, uint8_t* flags, hipStream_t s);
+// res->count_after = n - res->listed; then *copy_to = *res unless copy_to is null
+void region_tally(const RegionArgs& a, RegionResult* copy_to, hipStream_t s);
+// label[r] / size[r] / kind[r] of the rows r < min(rows, n) (each may be null)
+void region_split(const RegionArgs& a, uint32_t* label, uint32_t* size, uint8_t* kind, unsigned rows, hipStream_t s);
+
 // ---- fuse surfels into the map (ef_fuse.inc; ef_map_fuse of include/ef_hip.h) ----
 constexpr unsigned long long FUSE_KEY_EMPTY = 0xFFFFFFFFFFFFFFFFull;
 constexpr unsigned FUSE_SKIPPED = 0, FUSE_NOVEL = 1, FUSE_WEIGHTLESS = 2, FUSE_ABSORBED = 3, FUSE_FUSED = 4, FUSE_INSERTED = 5;   // EF_FUSE_*

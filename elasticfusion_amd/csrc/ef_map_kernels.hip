@@ -1527,6 +1527,7 @@ void sample_graph(SurfelSoA map, const unsigned* count_dev, int stride, int max_
 #include "ef_components.inc"
 #include "ef_planes.inc"
 #include "ef_normals.inc"
+#include "ef_regions.inc"
 #include "ef_fuse.inc"
 
 }  // namespace efm

@@ -1360,9 +1360,9 @@ int ef_map_remove_planes(ef_ctx* ctx, const ef_plane_params* params, const ef_ma
  * choice for the same walk), min_conf -1, k 12, min_neighbors 5, EF_NORMALS_KEEP_SIDE, side -1, viewpoint (0, 0, 0), line_ratio 1e-4 (a
  * definition, see above, not a measurement), max_curvature 0.05 (likewise), set_radius 0, radius_scale 1.
  *
- * Not provided: region growing itself (curvature and the lists are its inputs); smoothing of positions (moving least squares); a method of the
- * C++ shim; the write-back on loop-closing contexts; normals of a point set that is not in the map (it needs an index over that set: insert
- * the set first, see accuracy.insert_cloud).
+ * Not provided: smoothing of positions (moving least squares); a method of the C++ shim; the write-back on loop-closing contexts; normals of a
+ * point set that is not in the map (it needs an index over that set: insert the set first, see accuracy.insert_cloud).  (Region growing on
+ * these estimates is the next section.)
  *
  * EF_EINVAL, before any GPU work (the arguments are checked before the context, so with a NULL context ef_last_error(NULL) names what is wrong
  * with them): a NULL context, params, count or (ef_map_reestimate_normals) result; radius or cell not finite and positive, or 1 / cell not
@@ -1406,6 +1406,125 @@ int ef_map_normals_select(ef_ctx* ctx, const ef_normal_params* params, const ef_
 int ef_map_normals_select_dev(ef_ctx* ctx, const ef_normal_params* params, const ef_map_selection* among_or_null, int what, uint32_t* rows_dev,
                               uint32_t max_rows, uint32_t* count_dev, ef_normal_result* result_dev_or_null);
 int ef_map_reestimate_normals(ef_ctx* ctx, const ef_normal_params* params, const ef_map_selection* among_or_null, ef_normal_result* result);
+
+/* ---- Segment the map into smooth regions (the smoothness-constrained region growing of point-cloud toolkits).  ef_map_components separates
+ * objects only once they are detached, and ef_map_planes takes out what is flat; this splits a CONNECTED map along its creases: the faces of a
+ * box, a cylinder from the table it stands on, the two sides of a thin wall.  Textbook region growing is sequential, and its result depends on
+ * the order of its seeds.  The formulation here is order-free, a function of the graph alone, whatever order anything was evaluated in: the
+ * low-curvature surfels (CORES) form regions as the connected components of "close and smooth", and the crease surfels (BORDERS) are attached to
+ * the region of their nearest smooth core and never bridge two regions.  Off until first used: no region call, nothing allocated, nothing run,
+ * and no frame kernel knows of it.
+ *
+ * "Row", the layout of a surfel, d2 (symmetric in f32), r2 = radius * radius computed once in f32 on the host, the PARTICIPANTS, the rule
+ * "ELIGIBLE", the NEIGHBOURS of a participant and the whole estimate (NEIGHBOURHOOD, MOMENTS, EIGEN-DECOMPOSITION, ORIENTATION, CURVATURE,
+ * SPARSE, DEGENERATE, STATUS) are exactly those of the sections "Connected components of the map" and "Estimate normals, curvature and spacing
+ * from the map's neighbourhoods".  All f32 arithmetic rounds once per operation, without contraction, in the written order.
+ *
+ * ESTIMATE.  Every participant gets the estimate of ef_map_normals with this call's radius, cell, min_conf, k, min_neighbors and line_ratio and
+ * the orientation EF_NORMALS_KEEP_SIDE.  The neighbours of the estimate are the normals' neighbours: all rows eligible for the participant,
+ * whether they participate or not.
+ *
+ * NODE.  A participant with conf > min_conf (a NaN confidence compares false) whose status is EF_NORMAL_ESTIMATED.  SPARSE, DEGENERATE and
+ * non-participating rows are not nodes: they carry no edge and attach nowhere.
+ *
+ * THE NORMAL n_s of a node.  normal_source = EF_REGIONS_ESTIMATED: the (float)n estimate.  EF_REGIONS_STORED: floats 8 .. 10 of the row as they
+ * are, not renormalised (the curvature, and with it core / border, is the estimate's in both cases).
+ *
+ * SMOOTH(s, t).  dot = (n_s.x * n_t.x + n_s.y * n_t.y) + n_s.z * n_t.z in f32.  The rule is dot >= min_normal_cos; with two_sided != 0 it is
+ * fabsf(dot) >= min_normal_cos.  A NaN compares false (a NaN stored normal is smooth with nothing; a zero one only for min_normal_cos <= 0).
+ * The products commute, so dot is the same bits from either end and the graph is undirected by construction, like d2.  Signed is the default:
+ * a map's normals are oriented by the sensor, and the two sides of a thin wall must not merge.
+ *
+ * CORE / BORDER.  A node is a CORE iff curvature <= max_curvature, compared in f32.  Every other node is a BORDER.
+ *
+ * EDGE.  Two distinct cores s != t are joined iff d2(p_s, p_t) <= r2 and SMOOTH(s, t).  REGIONS are the connected components of the cores under
+ * these edges.  label = the SMALLEST CORE ROW of the region.  Smoothness is pairwise, between neighbours, never against a seed: a cylinder's
+ * side is one region although its normals turn all the way round.
+ *
+ * ATTACH (attach_borders != 0).  For a border b take the cores t with d2(p_b, p_t) <= r2 and SMOOTH(b, t), ordered by (d2, row) ascending.  b
+ * joins the region of the first of them: label[b] = that region's label.  If there is none, or if attach_borders == 0, the border is
+ * UNASSIGNED and its label is EF_REGION_NONE.  A border never carries an edge: two regions that touch only through borders stay two.
+ *
+ * SIZE.  size[s] = the cores plus the attached borders of the region of s.  A row without a region (no node, or UNASSIGNED) has
+ * label = EF_REGION_NONE and size = 0.  kind[s] = EF_REGION_KIND_CORE, EF_REGION_KIND_BORDER, or EF_REGION_KIND_NONE for a row that is no node.
+ *
+ * VERDICT.  A node with a region is REJECTED iff size < min_size or (max_size != 0 and size > max_size), otherwise ACCEPTED; all rows of a
+ * region share the verdict.  A row without a region is neither.
+ *
+ * THE FOUR LISTS (what).  EF_REGIONS_REJECTED, EF_REGIONS_ACCEPTED: the nodes with that verdict.  EF_REGIONS_UNASSIGNED: the borders without a
+ * region.  EF_REGIONS_BORDERS: every border node, attached or not: the crease lines.
+ *
+ * ef_region_result: nodes; cores; borders (nodes = cores + borders); attached and unassigned (borders = attached + unassigned); regions = the
+ * number of core rows r with label[r] == r; largest = the greatest size (0 without regions); rejected_rows and rejected_regions = the rejected
+ * nodes and their regions; listed = the number of rows of the list `what` (ef_map_regions, which takes no what: of EF_REGIONS_REJECTED);
+ * count_after = the map count minus listed, which is the count ef_map_remove_regions with that what leaves; status = 0, or non-zero if one of
+ * the device loops ran into its step bound, which no input can cause (the host variants then return EF_EHIP and ef_map_remove_regions removes
+ * nothing; the _dev variants can only report it here).  But for listed and count_after the result does not depend on what.
+ *
+ * ef_map_regions changes nothing.  It writes label[r], size[r] and kind[r] of the rows r < min(max_rows, map count) (each array may be NULL;
+ * entries past that are left as they were) and the optional result.  ef_map_regions_select changes nothing.  It writes the list `what` with
+ * ef_map_select's conventions: the first min(max_rows, total) rows in ASCENDING order, *count = total however small max_rows is, rows may be
+ * NULL with max_rows 0, entries past min(max_rows, total) are left as they were.  The list is what ef_map_erase_rows and ef_map_gather take.
+ * The _dev variants take DEVICE pointers for the arrays, count and result and only enqueue on the context's stream, except for what the
+ * selection needs (ID numbering, label alignment, the count after a call that can change the map) and except that they wait for the device once
+ * when the index has to be rebuilt or the scratch grows.
+ *
+ * ef_map_remove_regions removes the rows of the list `what` and leaves everything exactly as ef_map_erase_rows(that list) would: see "What an
+ * erase leaves behind" above, with one more synchronisation (the result is read before a row changes).  result (HOST memory, required): as
+ * above for the map as it WAS, listed = the rows removed, count_after = the map count the call leaves.  Unlike ef_map_remove_components it is
+ * NOT IDEMPOTENT: a removed row was a neighbour of rows that stay, so their neighbourhoods, and with them their normals, curvatures, kinds and
+ * edges, are different in a second call, which may list rows again.
+ *
+ * cell is the cell of the queries' index, which is built at that cell where needed; a later query at another cell rebuilds it, as after
+ * ef_set_query_cell.  No result depends on it.  Defaults (ef_default_region_params): radius 0.03 m, cell 0.03 m, min_conf -1, k 12,
+ * min_neighbors 5, line_ratio 1e-4, EF_REGIONS_ESTIMATED, two_sided 0, min_normal_cos 0.9659258 (the cosine of 15 degrees: a definition, not
+ * a measurement), max_curvature 0.05 (the normals' default), attach_borders 1, min_size 50, max_size 0 (no upper bound).
+ *
+ * Not provided: a model per region (a plane, a cylinder: ef_map_planes fits planes); writing the region labels into the label table of
+ * ef_enable_labels; a method of the C++ shim.
+ *
+ * EF_EINVAL, before any GPU work (the arguments are checked before the context, so with a NULL context ef_last_error(NULL) names what is wrong
+ * with them): a NULL context, params, count or (ef_map_remove_regions) result; radius or cell not finite and positive, or 1 / cell not finite;
+ * radius / cell above EF_QUERY_MAX_RATIO; NaN min_conf; k outside 3 .. 16; min_neighbors outside 2 .. k; NaN or negative line_ratio or
+ * max_curvature; NaN min_normal_cos; normal_source outside its two values; what outside its four values; max_rows > 0 with NULL rows; with
+ * among given, everything ef_map_select refuses for a selection.
+ * EF_ESTATE: the context's stream is being captured; with among given, what ef_map_select answers with EF_ESTATE.  ef_map_remove_regions only:
+ * a context created with close_loops = 1 (the erase's reason; the map is unchanged); the other calls work on such contexts. */
+#define EF_REGION_NONE 0xFFFFFFFFu   /* label of a row without a region */
+#define EF_REGION_KIND_NONE   0      /* kind: the row is no node */
+#define EF_REGION_KIND_CORE   1      /* kind: a node with curvature <= max_curvature */
+#define EF_REGION_KIND_BORDER 2      /* kind: every other node */
+#define EF_REGIONS_ESTIMATED 0       /* normal_source: the estimate */
+#define EF_REGIONS_STORED    1       /* normal_source: the row's stored normal */
+#define EF_REGIONS_REJECTED   0      /* what: the nodes of regions below min_size or above max_size */
+#define EF_REGIONS_ACCEPTED   1      /* what: every other node with a region */
+#define EF_REGIONS_UNASSIGNED 2      /* what: the borders without a region */
+#define EF_REGIONS_BORDERS    3      /* what: every border node */
+typedef struct ef_region_params {
+  float radius; float cell; float min_conf;
+  int k;                  /* the estimate: neighbours used, 3 .. 16 */
+  int min_neighbors;      /* the estimate: 2 .. k */
+  float line_ratio;       /* the estimate */
+  int normal_source;      /* EF_REGIONS_ESTIMATED / EF_REGIONS_STORED */
+  int two_sided;          /* non-zero: |dot| is compared */
+  float min_normal_cos;
+  float max_curvature;
+  int attach_borders;     /* non-zero: borders join the region of their nearest smooth core */
+  uint32_t min_size; uint32_t max_size;   /* max_size 0: no upper bound */
+} ef_region_params;
+typedef struct ef_region_result {
+  uint32_t nodes, cores, borders, attached, unassigned, regions, largest, rejected_rows, rejected_regions, listed, count_after, status;
+} ef_region_result;
+int ef_default_region_params(ef_ctx* ctx, ef_region_params* params);
+int ef_map_regions(ef_ctx* ctx, const ef_region_params* params, const ef_map_selection* among_or_null, uint32_t* label_or_null,
+                   uint32_t* size_or_null, uint8_t* kind_or_null, uint32_t max_rows, ef_region_result* result_or_null);
+int ef_map_regions_dev(ef_ctx* ctx, const ef_region_params* params, const ef_map_selection* among_or_null, uint32_t* label_dev_or_null,
+                       uint32_t* size_dev_or_null, uint8_t* kind_dev_or_null, uint32_t max_rows, ef_region_result* result_dev_or_null);
+int ef_map_regions_select(ef_ctx* ctx, const ef_region_params* params, const ef_map_selection* among_or_null, int what, uint32_t* rows,
+                          uint32_t max_rows, uint32_t* count, ef_region_result* result_or_null);
+int ef_map_regions_select_dev(ef_ctx* ctx, const ef_region_params* params, const ef_map_selection* among_or_null, int what, uint32_t* rows_dev,
+                              uint32_t max_rows, uint32_t* count_dev, ef_region_result* result_dev_or_null);
+int ef_map_remove_regions(ef_ctx* ctx, const ef_region_params* params, const ef_map_selection* among_or_null, int what, ef_region_result* result);
 
 /* named internal images, copied to HOST (synchronises); for tests and for a front-end's drawing code */
 enum ef_image {
