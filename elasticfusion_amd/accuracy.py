@@ -190,6 +190,22 @@ def estimated_normals(ef: "api.ElasticFusion", **params) -> np.ndarray:
     return out
 
 
+def smoothed_map(ef: "api.ElasticFusion", **params) -> np.ndarray:
+    """a smoothed copy of the map's records, [n, 12] float32 as downloadMap() gives them with floats 0 .. 2 of every participant replaced by
+    its moving-least-squares position and, with set_normal, floats 8 .. 10 of the SMOOTHED rows by the last fit's normal: what applySmooth
+    with the same arguments would leave.  The map does not change: smoothMap + gatherSurfels (ef_map_smooth + ef_map_gather).  The keywords
+    (params, among, ef_smooth_params fields) as smoothMap takes them."""
+    sm = ef.smoothMap(**params)
+    out = ef.gatherSurfels(np.arange(len(sm["status"]), dtype=np.uint32))
+    part = sm["status"] != api.SMOOTH_NONE
+    out[part, 0:3] = sm["position"][part]
+    p = params.get("params")
+    if p.set_normal if p is not None else params.get("set_normal", 0):
+        done = sm["status"] == api.SMOOTH_SMOOTHED
+        out[done, 8:11] = sm["normal"][done]
+    return out
+
+
 CLOUD_RADIUS = 2.0 ** -20     # insert_cloud's placeholder radius: a value no frame and no spacing produces, so that it marks the inserted rows
 
 

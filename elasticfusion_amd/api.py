@@ -197,7 +197,21 @@ class ef_region_result(C.Structure):
                 ("status", c_u32)]
 
 
+class ef_smooth_params(C.Structure):
+    _fields_ = [("radius", c_f), ("cell", c_f), ("min_conf", c_f), ("k", c_i), ("min_neighbors", c_i), ("iterations", c_i), ("weighting", c_i),
+                ("normal_gate", c_i), ("min_normal_cos", c_f), ("strength", c_f), ("max_shift", c_f), ("line_ratio", c_f), ("set_normal", c_i),
+                ("shift_threshold", c_f)]
+
+
+class ef_smooth_result(C.Structure):
+    _fields_ = [("participants", c_u32), ("smoothed", c_u32), ("sparse", c_u32), ("degenerate", c_u32), ("clamped", c_u32), ("moved", c_u32),
+                ("listed", c_u32), ("largest_shift", c_f)]
+
+
 CARVE_MAX_VIEWS = 32   # EF_CARVE_MAX_VIEWS of include/ef_hip.h
+SMOOTH_UNIFORM, SMOOTH_COMPACT = 0, 1               # EF_SMOOTH_UNIFORM / _COMPACT of include/ef_hip.h: weighting of ef_smooth_params
+SMOOTH_NONE, SMOOTH_SMOOTHED, SMOOTH_SPARSE, SMOOTH_DEGENERATE = 0, 1, 2, 3   # EF_SMOOTH_*: a row's status byte (the last three also `what`)
+SMOOTH_CLAMPED, SMOOTH_SHIFTED = 4, 5               # EF_SMOOTH_CLAMPED / _SHIFTED: `what` of ef_map_smooth_select beside the three statuses
 REGION_NONE = 0xFFFFFFFF                             # EF_REGION_NONE of include/ef_hip.h: the label of a row without a region
 REGION_KIND_NONE, REGION_KIND_CORE, REGION_KIND_BORDER = 0, 1, 2   # EF_REGION_KIND_*: a row's kind byte
 REGIONS_ESTIMATED, REGIONS_STORED = 0, 1            # EF_REGIONS_ESTIMATED / _STORED: normal_source of ef_region_params
@@ -1804,6 +1818,84 @@ class ElasticFusion:
         res = ef_region_result()
         _chk(lib().ef_map_remove_regions(self.h, C.byref(params), pa, int(what), C.byref(res)), self.h)
         return self._regionResult(res)
+
+    # --- smooth the map's positions by moving least squares (ef_map_smooth / ef_map_smooth_select / ef_map_smooth_apply) ---
+    def smoothParams(self, **kw) -> ef_smooth_params:
+        """ef_default_smooth_params (radius 0.03, cell 0.03, min_conf -1, k 12, min_neighbors 5, iterations 1, SMOOTH_COMPACT, normal_gate 0,
+        min_normal_cos 0.9, strength 1, max_shift = radius, line_ratio 1e-4, set_normal 0, shift_threshold 0) with fields replaced by keyword;
+        max_shift follows a radius given by keyword unless it is given too"""
+        if "radius" in kw and "max_shift" not in kw:
+            kw = dict(kw, max_shift=kw["radius"])
+        return self._params(ef_smooth_params, lib().ef_default_smooth_params, kw, "smooth")
+
+    def _smoothArgs(self, params, among, kw):
+        if params is None:
+            params = self.smoothParams(**kw)
+        else:
+            assert not kw, "give params or keywords, not both"
+        if isinstance(among, dict):
+            among = self.mapSelection(**among)
+        return params, among, (C.byref(among) if among is not None else None)
+
+    @staticmethod
+    def _smoothResult(res: ef_smooth_result) -> dict:
+        return {k: (float(getattr(res, k)) if k == "largest_shift" else int(getattr(res, k))) for k, _ in ef_smooth_result._fields_}
+
+    def smoothMap(self, params: ef_smooth_params | None = None, among=None, result: bool = False, **kw):
+        """per row of downloadMap(): {"position" float32 [n, 3], "normal" float32 [n, 3], "curvature" float32, "shift" float32, "count" uint32,
+        "status" uint8 (api.SMOOTH_*)}: the position after `iterations` projections onto the weighted least-squares plane of the k nearest
+        other surfels within radius (the neighbourhoods are those of the map as it stands), the last fit's normal and surface variation, the
+        distance moved and the number of ALL neighbours; the map does not change.  among: an ef_map_selection, a dict of mapSelection keywords
+        or None (every surfel participates); other keywords are ef_smooth_params fields.  result=True adds the dict of ef_smooth_result"""
+        params, among, pa = self._smoothArgs(params, among, kw)
+        n = self.lastCount()
+        m = max(n, 1)
+        out = dict(position=np.zeros((m, 3), np.float32), normal=np.zeros((m, 3), np.float32), curvature=np.zeros(m, np.float32),
+                   shift=np.zeros(m, np.float32), count=np.zeros(m, np.uint32), status=np.zeros(m, np.uint8))
+        res = ef_smooth_result()
+        _chk(lib().ef_map_smooth(self.h, C.byref(params), pa, _ptr(out["position"]), _ptr(out["normal"]), _ptr(out["curvature"]),
+                                 _ptr(out["shift"]), _ptr(out["count"]), _ptr(out["status"]), n, C.byref(res)), self.h)
+        out = {k: v[:n] for k, v in out.items()}
+        return (out, self._smoothResult(res)) if result else out
+
+    def smoothMapDevice(self, params: ef_smooth_params, among, position_dev, normal_dev, curvature_dev, shift_dev, count_dev, status_dev,
+                        max_rows: int, result_dev=None):
+        """ef_map_smooth_dev: raw device pointers (int, c_void_p or None) for max_rows x 3 floats twice, max_rows floats twice, max_rows uint32,
+        max_rows bytes and the result, enqueued on the context's stream"""
+        params, among, pa = self._smoothArgs(params, among, {})
+        _chk(lib().ef_map_smooth_dev(self.h, C.byref(params), pa, _dev(position_dev), _dev(normal_dev), _dev(curvature_dev), _dev(shift_dev),
+                                     _dev(count_dev), _dev(status_dev), int(max_rows), _dev(result_dev)), self.h)
+
+    def smoothSelect(self, params: ef_smooth_params | None = None, among=None, what: int = SMOOTH_SHIFTED, max_rows: int | None = None,
+                     count: bool = False, result: bool = False, **kw):
+        """the rows `what` names (SMOOTH_SMOOTHED / _SPARSE / _DEGENERATE, SMOOTH_CLAMPED: a step was cut at max_shift, SMOOTH_SHIFTED: moved
+        further than shift_threshold) in ascending order (uint32), at most max_rows of them (None: all); the map does not change.  among and
+        the keywords as smoothMap takes them.  count=True adds the total, result=True the dict of ef_smooth_result: rows[, total][, result]"""
+        params, among, pa = self._smoothArgs(params, among, kw)
+        cap = self.lastCount() if max_rows is None else int(max_rows)
+        rows = np.zeros(max(cap, 1), np.uint32)
+        total = c_u32(0)
+        res = ef_smooth_result()
+        _chk(lib().ef_map_smooth_select(self.h, C.byref(params), pa, int(what), _ptr(rows) if cap else None, cap, C.byref(total),
+                                        C.byref(res) if result else None), self.h)
+        out = (rows[:min(cap, total.value)].copy(),) + ((total.value,) if count else ()) + ((self._smoothResult(res),) if result else ())
+        return out if len(out) > 1 else out[0]
+
+    def smoothSelectDevice(self, params: ef_smooth_params, among, what: int, rows_dev, max_rows: int, count_dev, result_dev=None):
+        """ef_map_smooth_select_dev: raw device pointers (int, c_void_p or None for rows with max_rows 0 and for the result), enqueued on the
+        context's stream"""
+        params, among, pa = self._smoothArgs(params, among, {})
+        _chk(lib().ef_map_smooth_select_dev(self.h, C.byref(params), pa, int(what), _dev(rows_dev), int(max_rows), _dev(count_dev),
+                                            _dev(result_dev)), self.h)
+
+    def applySmooth(self, params: ef_smooth_params | None = None, among=None, **kw) -> dict:
+        """writes the smoothed position of every participant into the map and, with set_normal, the last fit's normal into the SMOOTHED rows
+        (ef_map_smooth_apply); every other word of the map keeps its bits.  Not idempotent.  The dict of ef_smooth_result: {"participants",
+        "smoothed", "sparse", "degenerate", "clamped", "moved", "listed", "largest_shift"}"""
+        params, among, pa = self._smoothArgs(params, among, kw)
+        res = ef_smooth_result()
+        _chk(lib().ef_map_smooth_apply(self.h, C.byref(params), pa, C.byref(res)), self.h)
+        return self._smoothResult(res)
 
     def setReferenceDownload(self, on=True):
         """downloadMap / savePly read what GlobalModel::downloadMap reads (the pre-clean buffer, quirk Q14) instead of model()"""

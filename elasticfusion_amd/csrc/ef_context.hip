@@ -348,6 +348,13 @@ struct ef_ctx {
     DevBuf scratch;                        // the result | {normal, curvature}, the stored-normal word, {spacing, count} per row | parent, attach, label, members per row | chunk counts | chunk offsets | 4 words | status bytes | kind bytes
     size_t rows = 0;
   } regions;
+  // smoothing (ef_map_smooth, ef_map_smooth_select, ef_map_smooth_apply; kernels in ef_smooth.inc): scratch of its own, sized by the map's rows and
+  // by the list's slots K (4 / 8 / 16 for the k in use), grown by the first call and by a call with more of either, freed with the context
+  struct SmoothState {
+    DevBuf scratch;                        // the result | two position buffers and {normal, curvature} per row | K list slots per row | count, shift per row | chunk counts | chunk offsets | 4 words | status bytes
+    size_t rows = 0;
+    int slots = 0;
+  } smooth;
   // fuse (ef_map_fuse; kernels in ef_fuse.inc) beside the insert's scratch, which its gate and append use: the election's keys (one per map row),
   // match_row and the outcome bytes (one each per record), and the two counts' words (FuseScratch / fuse_scratch in ef_host_insert.inc, beside
   // append_run, which carves it).  Grown by the first call, freed with the context
@@ -726,7 +733,7 @@ void ctx_free(ef_ctx* c) {
   for (KernelSampler* k : {&c->sample_step, &c->sample_all, &c->sample_splat}) k->release();
   drop_track_graphs(c);
   if (c->debug_stream) { (void)hipStreamSynchronize(c->debug_stream); (void)hipStreamDestroy(c->debug_stream); }
-  for (DevBuf* b : {&c->stage, &c->render.zbuf, &c->labels.index, &c->query.sorted, &c->query.rows, &c->query.cells, &c->reg.slabs, &c->sel.scratch, &c->ins.scratch, &c->thin.scratch, &c->carve.scratch, &c->outlier.scratch, &c->components.scratch, &c->planes.scratch, &c->normals.scratch, &c->regions.scratch, &c->fuse.scratch})
+  for (DevBuf* b : {&c->stage, &c->render.zbuf, &c->labels.index, &c->query.sorted, &c->query.rows, &c->query.cells, &c->reg.slabs, &c->sel.scratch, &c->ins.scratch, &c->thin.scratch, &c->carve.scratch, &c->outlier.scratch, &c->components.scratch, &c->planes.scratch, &c->normals.scratch, &c->regions.scratch, &c->smooth.scratch, &c->fuse.scratch})
     b->release();
   for (int k = 0; k < 2; ++k) {
     if (c->labels.tab[k]) (void)hipFree(c->labels.tab[k]);
@@ -1212,4 +1219,5 @@ int ef_set_depth_cutoff(ef_ctx* c, float v) { if (!c) return EF_EINVAL; c->cfg.d
 #include "ef_host_planes.inc"
 #include "ef_host_normals.inc"
 #include "ef_host_regions.inc"
+#include "ef_host_smooth.inc"
 #include "ef_host_fuse.inc"

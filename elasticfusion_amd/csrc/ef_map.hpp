@@ -560,6 +560,54 @@ void region_tally(const RegionArgs& a, RegionResult* copy_to, hipStream_t s);
 // label[r] / size[r] / kind[r] of the rows r < min(rows, n) (each may be null)
 void region_split(const RegionArgs& a, uint32_t* label, uint32_t* size, uint8_t* kind, unsigned rows, hipStream_t s);
 
+// ---- smooth the map's positions by moving least squares (ef_smooth.inc; ef_map_smooth of include/ef_hip.h) ----
+constexpr int SMOOTH_UNIFORM = 0, SMOOTH_COMPACT = 1;                                         // EF_SMOOTH_UNIFORM / _COMPACT: weighting
+constexpr unsigned SMOOTH_NONE = 0, SMOOTH_SMOOTHED = 1, SMOOTH_SPARSE = 2, SMOOTH_DEGENERATE = 3;   // EF_SMOOTH_*: the status byte
+constexpr int SMOOTH_CLAMPED = 4, SMOOTH_SHIFTED = 5;                                         // EF_SMOOTH_*: `what` beside the three statuses
+constexpr unsigned SMOOTH_STATUS_MASK = 3u, SMOOTH_CLAMPED_BIT = 4u;   // the scratch's byte: the status, and the sticky bit of a row whose step was clamped
+struct SmoothResult {       // ef_smooth_result, field for field (ef_host_smooth.inc asserts the layout)
+  uint32_t participants, smoothed, sparse, degenerate, clamped, moved, listed;
+  float largest_shift;
+};
+struct SmoothArgs {
+  QueryArgs q;              // the index built at the call's cell and the live map; max_dist = radius, r2, min_conf (points, n, k, outputs unused)
+  unsigned n;               // rows of the map: the length of the per-row arrays below
+  int k;                    // neighbours used: 3 .. 16
+  unsigned min_neighbors;
+  int iterations;           // 1 .. 16
+  int weighting;            // SMOOTH_UNIFORM / SMOOTH_COMPACT
+  int gate;                 // non-zero: a neighbour counts only if its stored normal agrees with the row's
+  float min_normal_cos, strength, max_shift, line_ratio, shift_threshold;
+  int set_normal;
+  const uint8_t* part_in;   // one byte per row, non-zero = the row passes the selection (may be `status` itself); null: every row does
+  unsigned stride;          // rows between two slots of nbr
+  uint32_t* nbr;            // slot-major: nbr[j * stride + row] = the row's j-th used neighbour, the row itself from slot c on; slots 0 .. k - 1
+  uint32_t* count;          // per row count_s (0 for a row that takes no part); every row is written by smooth_neighbours
+  uint8_t* status;          // per row SMOOTH_* | SMOOTH_CLAMPED_BIT: NONE / SPARSE / SMOOTHED (= "is fitted") after smooth_neighbours, the last verdict after a step
+  float4* buf[2];           // the ping-pong positions {x, y, z, conf}: iteration i writes buf[(i - 1) & 1]
+  float4* est;              // per row {normal, curvature} of the last step; every row is written by every step
+  float* shift;             // per row; every row is written by smooth_finish
+  SmoothResult* res;        // the call's result on the device
+};
+// the positions after the last iteration
+inline const float4* smooth_final(const SmoothArgs& a) { return a.buf[(a.iterations - 1) & 1]; }
+// count, status and the neighbour list of every row: one lane per record of the index, in index order; nothing is launched for an empty map
+void smooth_neighbours(const SmoothArgs& a, hipStream_t s);
+// iteration i (1 ..): one lane per row reads the list, gathers from the iteration's input (the map for i = 1, buf[i & 1] after) and writes
+// buf[(i - 1) & 1], est and status of every row
+void smooth_step(const SmoothArgs& a, int i, hipStream_t s);
+// shift[] of every row from the last iteration's positions and the map's
+void smooth_finish(const SmoothArgs& a, hipStream_t s);
+// flags[row] = 1 for the rows `what` names, 0 for every other row (every row is written)
+void smooth_flags(const SmoothArgs& a, int what, uint8_t* flags, hipStream_t s);
+// *a.res (zeroed here first) from status and shift, listed = *total (0 with total null); then *copy_to = *res unless copy_to is null
+void smooth_tally(const SmoothArgs& a, const uint32_t* total, SmoothResult* copy_to, hipStream_t s);
+// the optional per-row outputs of the rows r < min(rows, n) (each may be null)
+void smooth_split(const SmoothArgs& a, float* position3, float* normal3, float* curvature, float* shift, uint32_t* count, uint8_t* status,
+                  unsigned rows, hipStream_t s);
+// the write-back: floats 0 .. 2 of every participant of a.q.map, and floats 8 .. 10 of the SMOOTHED rows with set_normal, in place
+void smooth_apply(const SmoothArgs& a, hipStream_t s);
+
 // ---- fuse surfels into the map (ef_fuse.inc; ef_map_fuse of include/ef_hip.h) ----
 constexpr unsigned long long FUSE_KEY_EMPTY = 0xFFFFFFFFFFFFFFFFull;
 constexpr unsigned FUSE_SKIPPED = 0, FUSE_NOVEL = 1, FUSE_WEIGHTLESS = 2, FUSE_ABSORBED = 3, FUSE_FUSED = 4, FUSE_INSERTED = 5;   // EF_FUSE_*

@@ -1528,6 +1528,7 @@ void sample_graph(SurfelSoA map, const unsigned* count_dev, int stride, int max_
 #include "ef_planes.inc"
 #include "ef_normals.inc"
 #include "ef_regions.inc"
+#include "ef_smooth.inc"
 #include "ef_fuse.inc"
 
 }  // namespace efm

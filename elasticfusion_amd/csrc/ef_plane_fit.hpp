@@ -12,7 +12,8 @@
 //               flipped to the hypothesis's side; d = -(n . (a + mean)).
 //   OUTPUT      false, and nothing written, when m < 3 or anything along the way is not finite: the caller keeps the hypothesis's plane.
 //   PARTS       plane_fit_eigen (the moments to the diagonalised A, V) and plane_fit_normal (the choice, the normalisation, the flip) are shared
-//               with normal_fit at the end of this file, the per-surfel fit of ef_map_normals; plane_fit adds the offset and the thickness.
+//               with normal_fit, the per-surfel fit of ef_map_normals, and with smooth_fit at the end of this file, the weighted per-surfel fit
+//               of ef_map_smooth; plane_fit adds the offset and the thickness.
 #pragma once
 
 #if defined(__HIPCC__)
@@ -56,9 +57,9 @@ EF_PF_HD void plane_fit_rotate(double A[3][3], double V[3][3], int p, int q, int
 
 // The part both fits share, up to the diagonalised matrix: mean = S1 / m, the covariance A, the fixed sweeps; A's diagonal then holds the
 // eigenvalues and V's columns the eigenvectors.  false when m < 3 or the covariance is not finite.
-EF_PF_HD bool plane_fit_eigen(const double S[9], unsigned m, double A[3][3], double V[3][3], double mean[3]) {
+// md = the divisor of the moments: (double)m for the unweighted fits, the sum of the weights for smooth_fit below (the one text for both).
+EF_PF_HD bool plane_fit_eigen_w(const double S[9], unsigned m, double md, double A[3][3], double V[3][3], double mean[3]) {
   if (m < 3u) return false;
-  const double md = (double)m;
   const double mx = S[0] / md, my = S[1] / md, mz = S[2] / md;
   A[0][0] = S[3] / md - mx * mx;
   A[0][1] = S[4] / md - mx * my;
@@ -83,6 +84,9 @@ EF_PF_HD bool plane_fit_eigen(const double S[9], unsigned m, double A[3][3], dou
   mean[1] = my;
   mean[2] = mz;
   return true;
+}
+EF_PF_HD bool plane_fit_eigen(const double S[9], unsigned m, double A[3][3], double V[3][3], double mean[3]) {
+  return plane_fit_eigen_w(S, m, (double)m, A, V, mean);
 }
 
 // The eigenvector of the smallest eigenvalue (ties: the lowest index), normalised and flipped to hn's side (a zero or NaN hn flips nothing).
@@ -175,6 +179,42 @@ EF_PF_HD int normal_fit(const double S[9], unsigned m, const float hn[3], float 
   n_out[2] = (float)n[2];
   *curvature_out = sum > 0.0 ? (float)(emin / sum) : 0.0f;
   *flipped_out = flipped;
+  return NORMAL_FIT_ESTIMATED;
+}
+
+// ---- the smoothing's entry point (ef_smooth.inc: k_smooth_step; "Smooth the map's positions" of include/ef_hip.h) ----
+// normal_fit for WEIGHTED moments: S = the nine weighted sums about the row's own position, W = 1 + the sum of the weights (the divisor of the
+// moments), m = c + 1 = the members of the neighbourhood (the "fewer than three" test only).  From plane_fit_eigen_w on it is normal_fit's
+// text: the same choice, normalisation and flip to hn's side, the same finiteness checks, DEGENERATE test and curvature.  What the projection
+// needs comes back in double: n_out = the unit normal, mean_out = the weighted mean of the differences.  Every output is written in every
+// case: zeros unless the return value is NORMAL_FIT_ESTIMATED.  With unit weights (W == (double)m) normal, curvature and verdict are
+// normal_fit's bit for bit.
+EF_PF_HD int smooth_fit(const double S[9], double W, unsigned m, const float hn[3], float line_ratio, double n_out[3], double mean_out[3],
+                        float* curvature_out) {
+  n_out[0] = n_out[1] = n_out[2] = 0.0;
+  mean_out[0] = mean_out[1] = mean_out[2] = 0.0;
+  *curvature_out = 0.0f;
+  double A[3][3], V[3][3], mean[3], n[3], l[3], lambda;
+  bool flipped;
+  if (!plane_fit_eigen_w(S, m, W, A, V, mean)) return NORMAL_FIT_GAVE_UP;
+  if (!plane_fit_normal(A, V, hn, n, l, &lambda, &flipped)) return NORMAL_FIT_GAVE_UP;
+  if (!plane_fit_finite(l[0]) || !plane_fit_finite(l[1]) || !plane_fit_finite(l[2]) || !plane_fit_finite(n[0]) || !plane_fit_finite(n[1]) ||
+      !plane_fit_finite(n[2]))
+    return NORMAL_FIT_GAVE_UP;
+  const double e0 = l[0] > 0.0 ? l[0] : 0.0, e1 = l[1] > 0.0 ? l[1] : 0.0, e2 = l[2] > 0.0 ? l[2] : 0.0;
+  const double emin = lambda > 0.0 ? lambda : 0.0;
+  const double lo = e1 < e0 ? e1 : e0, hi = e1 < e0 ? e0 : e1;
+  const double emax = e2 > hi ? e2 : hi;
+  const double emid = e2 > hi ? hi : (e2 < lo ? lo : e2);
+  if (!(emid > (double)line_ratio * emax)) return NORMAL_FIT_DEGENERATE;
+  const double sum = (e0 + e1) + e2;
+  n_out[0] = n[0];
+  n_out[1] = n[1];
+  n_out[2] = n[2];
+  mean_out[0] = mean[0];
+  mean_out[1] = mean[1];
+  mean_out[2] = mean[2];
+  *curvature_out = sum > 0.0 ? (float)(emin / sum) : 0.0f;
   return NORMAL_FIT_ESTIMATED;
 }
 

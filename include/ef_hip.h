@@ -1360,9 +1360,9 @@ int ef_map_remove_planes(ef_ctx* ctx, const ef_plane_params* params, const ef_ma
  * choice for the same walk), min_conf -1, k 12, min_neighbors 5, EF_NORMALS_KEEP_SIDE, side -1, viewpoint (0, 0, 0), line_ratio 1e-4 (a
  * definition, see above, not a measurement), max_curvature 0.05 (likewise), set_radius 0, radius_scale 1.
  *
- * Not provided: smoothing of positions (moving least squares); a method of the C++ shim; the write-back on loop-closing contexts; normals of a
- * point set that is not in the map (it needs an index over that set: insert the set first, see accuracy.insert_cloud).  (Region growing on
- * these estimates is the next section.)
+ * Not provided: a method of the C++ shim; the write-back on loop-closing contexts; normals of a point set that is not in the map (it needs an
+ * index over that set: insert the set first, see accuracy.insert_cloud).  (Region growing on these estimates is the next section; smoothing of
+ * the positions by moving least squares is the section "Smooth the map's positions" after it.)
  *
  * EF_EINVAL, before any GPU work (the arguments are checked before the context, so with a NULL context ef_last_error(NULL) names what is wrong
  * with them): a NULL context, params, count or (ef_map_reestimate_normals) result; radius or cell not finite and positive, or 1 / cell not
@@ -1525,6 +1525,140 @@ int ef_map_regions_select(ef_ctx* ctx, const ef_region_params* params, const ef_
 int ef_map_regions_select_dev(ef_ctx* ctx, const ef_region_params* params, const ef_map_selection* among_or_null, int what, uint32_t* rows_dev,
                               uint32_t max_rows, uint32_t* count_dev, ef_region_result* result_dev_or_null);
 int ef_map_remove_regions(ef_ctx* ctx, const ef_region_params* params, const ef_map_selection* among_or_null, int what, ef_region_result* result);
+
+/* ---- Smooth the map's positions (the moving-least-squares projection of point-cloud toolkits, plane fits only).  The cleaning tools remove
+ * surfels and the analysis tools read them; none reduces the noise in the positions themselves.  A merged second session, an inserted cloud
+ * (accuracy.insert_cloud) or a thinned map keeps its sensor noise, and every later normal, plane or region estimate is computed on it.  This
+ * fits a weighted plane to each surfel's neighbourhood and moves the surfel onto it, along the plane's normal only, several times if asked,
+ * without leaving the device.  Off until first used: no smooth call, nothing allocated, nothing run, and no frame kernel knows of it.
+ *
+ * "Row", the layout of a surfel, d2 (the queries' expression: dx = q.x - p.x, ..., (dx * dx + dy * dy) + dz * dz in f32), r2 = radius * radius
+ * computed once in f32 on the host, the PARTICIPANTS, the rule "ELIGIBLE", the NEIGHBOURS of a participant, count_s, c = min(count_s, k), the
+ * USED neighbours t_1 .. t_c in (d2, row) order and SPARSE (count_s < (uint32_t)min_neighbors) are exactly those of the section "Estimate
+ * normals, curvature and spacing from the map's neighbourhoods".  All f32 arithmetic rounds once per operation, without contraction, in the
+ * written order; so does all double arithmetic.
+ *
+ * NEIGHBOURHOODS.  They are taken ONCE, from the map's own positions P^0, and stay fixed for the whole call: the same rows t_1 .. t_c in the
+ * same order in every iteration, however far anything moves.  A row that does not participate and a SPARSE row never move; they still serve
+ * as neighbours, at their fixed positions.
+ *
+ * ITERATION i = 1 .. iterations reads P^(i-1) and writes P^i, every row (nothing is updated in place: a row's fit never sees a position of the
+ * same iteration).  For a participant s that is not SPARSE, with p = P^(i-1)_s:
+ *   d2_j       = d2(p, P^(i-1)_{t_j}) in f32.  For i = 1 these are the list's own bits.
+ *   WEIGHT     w_j, a double.  EF_SMOOTH_UNIFORM: w_j = 1.0.  EF_SMOOTH_COMPACT: u = 1.0 - (double)d2_j / (double)r2, then
+ *              w_j = u > 0.0 ? u * u : 0.0: a neighbour that drifted past the radius counts for nothing, and a NaN takes 0.  With
+ *              normal_gate != 0, after that: w_j = 0.0 unless dot >= min_normal_cos, where dot is SMOOTH's expression of the section "Segment
+ *              the map into smooth regions" in f32, (n_s.x * n_t.x + n_s.y * n_t.y) + n_s.z * n_t.z, on the STORED normals (floats 8 .. 10) of
+ *              rows s and t_j as the map holds them; they do not change during the call.  A NaN compares false: the weight is 0.
+ *   DIFFERENCE q_j = ((double)x_{t_j} - (double)p.x, ...) per component, from the f32 positions of P^(i-1).
+ *   SUMS       in double, j ascending.  a = w_j * q.x, b = w_j * q.y, g = w_j * q.z;  S[0..2] += a, b, g;  S[3..8] += a * q.x, a * q.y,
+ *              a * q.z, b * q.y, b * q.z, g * q.z;  W = W + w_j.  Every product is rounded once and then added.  Every S starts at +0.0 and
+ *              W at 1.0: the row itself is a member of its neighbourhood with the weight 1 and contributes exact zeros to S.  With
+ *              EF_SMOOTH_UNIFORM and no gate these are the normals' S bit for bit, and W == (double)(c + 1).
+ *   FIT        csrc/ef_plane_fit.hpp is the definition (its smooth_fit): the text of the normals' EIGEN-DECOMPOSITION with the divisor W in
+ *              place of (double)m (mean = S[0..2] / W, C_ij = S2_ij / W - mean_i * mean_j); its "fewer than three members" test is on c + 1;
+ *              then the normals' choice of the eigenvector, its normalisation and the ORIENTATION EF_NORMALS_KEEP_SIDE (the hint is the row's
+ *              stored normal), the same finiteness checks, the CURVATURE and the DEGENERATE test with line_ratio.  The fit of the iteration
+ *              is ESTIMATED, with the unit normal n and the mean in double and the curvature in f32, or it is not.
+ *   PROJECTION only for an ESTIMATED fit.  t = (n.x * mean.x + n.y * mean.y) + n.z * mean.z: the signed distance from p to the fitted plane
+ *              along n.  s = (double)strength * t.  If s > (double)max_shift then s = (double)max_shift, else if s < -(double)max_shift then
+ *              s = -(double)max_shift; either sets the row's CLAMPED bit, which stays set for the rest of the call.  p'.x = (float)((double)p.x +
+ *              s * n.x), likewise y and z.  If a component of p' is not finite, the row keeps p and this iteration's verdict is DEGENERATE (a
+ *              CLAMPED bit the iteration set stays).  Otherwise P^i_s = p' and the verdict is SMOOTHED.
+ *   OTHERWISE  a row whose fit is not ESTIMATED keeps p for this iteration, with the verdict DEGENERATE; a later iteration fits it again.
+ * A surfel moves along its plane's normal only: the sampling pattern does not contract, and a flat region's border does not creep inwards as
+ * it does under Laplacian smoothing.
+ *
+ * STATUS, one byte per row: EF_SMOOTH_NONE (the row takes no part), EF_SMOOTH_SPARSE, and for every other participant the LAST iteration's
+ * verdict, EF_SMOOTH_SMOOTHED or EF_SMOOTH_DEGENERATE.
+ * OUTPUTS by row after the last iteration I: position[3] = P^I, the map's own bits for a row that never moved; normal[3] = (float)n per
+ * component and curvature of the last iteration's fit, zeros unless the status is SMOOTHED; shift = the CORRECTLY ROUNDED f32 square root of
+ * d2(P^I_s, P^0_s) for a SMOOTHED or DEGENERATE row and 0 for every other row (NONE and SPARSE rows never move; a NONE row may have no finite
+ * position to measure from); count = count_s, 0 for NONE; status.
+ * RESULT: participants, smoothed, sparse, degenerate = the status counts (participants = their sum); clamped = the rows with the CLAMPED bit;
+ * moved = the rows with shift > 0; largest_shift = the greatest shift (0 without any); listed (below).
+ *
+ * ef_map_smooth changes nothing.  It writes the six arrays for the rows r < min(max_rows, map count) (position3 and normal3 are [rows][3];
+ * every array may be NULL; entries past that are left as they were) and the optional result with listed = 0.  ef_map_smooth_select changes
+ * nothing.  what = EF_SMOOTH_SMOOTHED, EF_SMOOTH_SPARSE or EF_SMOOTH_DEGENERATE (the rows of that status), EF_SMOOTH_CLAMPED (the rows with
+ * the CLAMPED bit) or EF_SMOOTH_SHIFTED (shift > shift_threshold, compared in f32).  The list has ef_map_select's conventions: the first
+ * min(max_rows, total) rows in ASCENDING order, *count = total however small max_rows is, rows may be NULL with max_rows 0, entries past
+ * min(max_rows, total) are left as they were; it is what ef_map_erase_rows and ef_map_gather take.  result (optional): as above, listed =
+ * total.  The _dev variants take DEVICE pointers for the arrays, count and result and only enqueue on the context's stream, except for what
+ * the selection needs (ID numbering, label alignment, the count after a call that can change the map) and except that they wait for the
+ * device once when the index has to be rebuilt or the scratch grows.
+ *
+ * ef_map_smooth_apply is the write-back.  For every participant it writes floats 0 .. 2 = P^I (the same bits for a row that did not move)
+ * and, with set_normal != 0, floats 8 .. 10 = the last iteration's normal for the rows whose status is SMOOTHED.  Every other word of every
+ * row keeps its bits (confidence, colour, the ID lane, both times, the radius; the normal without set_normal), and a row that takes no part
+ * keeps everything.  result (HOST memory, required): as above, listed = moved.  All counts are read back before a row is written.
+ * What a write-back leaves behind:
+ *   the map       as described, the count unchanged;
+ *   IDs           with IDs on, the rows created since the last ID-consuming call are numbered before the write, as every edit does; no ID changes;
+ *   the context   the state that ef_map_upload of the edited rows followed by ef_restore_state (tick, ef_get_pose_qt, the last processed frame)
+ *                 would leave: tick, pose, trajectory, last frame and tracking statistics are unchanged, and if ef_process_frame* or
+ *                 ef_restore_state has run on the context the model prediction is renewed from the edited map at the current pose.  On a context
+ *                 whose map was only uploaded, only the map changes;
+ *   the index     of the queries and the registration is stale, here in earnest (positions moved), and is rebuilt by their next call;
+ *   labels        untouched: no row moved to another row, every row keeps its C floats;
+ *   the shadow buffer of ef_set_reference_download is left as it is.
+ * The call synchronises before and after, like the insert.  A call that moves nothing is valid and still leaves that state.  It is NOT
+ * idempotent: a second call fits the moved positions.
+ *
+ * cell is the cell of the queries' index, which is built at that cell where needed; a later query at another cell rebuilds it, as after
+ * ef_set_query_cell.  No result depends on it.  Defaults (ef_default_smooth_params): radius 0.03 m, cell 0.03 m, min_conf -1, k 12,
+ * min_neighbors 5 (the normals' defaults), iterations 1, EF_SMOOTH_COMPACT, normal_gate 0, min_normal_cos 0.9, strength 1, max_shift =
+ * radius, line_ratio 1e-4, set_normal 0, shift_threshold 0.  These defaults are definitions, not measurements.
+ *
+ * Not provided: polynomial surfaces (the fit is a plane); tangential (Laplacian) motion; upsampling; smoothing of colour or radius; a method
+ * of the C++ shim; the write-back on loop-closing contexts.
+ *
+ * EF_EINVAL, before any GPU work (the arguments are checked before the context, so with a NULL context ef_last_error(NULL) names what is wrong
+ * with them): a NULL context, params, count or (ef_map_smooth_apply) result; radius or cell not finite and positive, or 1 / cell not finite;
+ * radius / cell above EF_QUERY_MAX_RATIO; NaN min_conf; k outside 3 .. 16; min_neighbors outside 2 .. k; iterations outside 1 .. 16;
+ * weighting outside its two values; normal_gate not 0 or 1; NaN min_normal_cos; strength not in (0, 1]; max_shift not > 0 (+inf is allowed: no
+ * bound); NaN or negative line_ratio or shift_threshold; what outside its five values; max_rows > 0 with NULL rows; with among given,
+ * everything ef_map_select refuses for a selection.
+ * EF_ESTATE: the context's stream is being captured; with among given, what ef_map_select answers with EF_ESTATE.  ef_map_smooth_apply only:
+ * a context created with close_loops = 1 (the erase's reason; the map is unchanged); the other calls work on such contexts. */
+#define EF_SMOOTH_UNIFORM    0     /* weighting: every used neighbour counts 1 */
+#define EF_SMOOTH_COMPACT    1     /* weighting: (1 - d2 / r2)^2, 0 from the radius on */
+#define EF_SMOOTH_NONE       0     /* status: the row takes no part */
+#define EF_SMOOTH_SMOOTHED   1     /* status, and `what`: the last iteration moved the row onto its plane */
+#define EF_SMOOTH_SPARSE     2     /* status, and `what`: fewer than min_neighbors neighbours */
+#define EF_SMOOTH_DEGENERATE 3     /* status, and `what`: the last iteration found no plane */
+#define EF_SMOOTH_CLAMPED    4     /* `what`: a step was cut at max_shift */
+#define EF_SMOOTH_SHIFTED    5     /* `what`: shift > shift_threshold */
+typedef struct ef_smooth_params {
+  float radius; float cell; float min_conf;
+  int k;                  /* neighbours used, 3 .. 16 */
+  int min_neighbors;      /* 2 .. k */
+  int iterations;         /* 1 .. 16 */
+  int weighting;          /* EF_SMOOTH_UNIFORM / EF_SMOOTH_COMPACT */
+  int normal_gate;        /* 1: a neighbour counts only if its stored normal agrees with the row's */
+  float min_normal_cos;   /* the gate's bound */
+  float strength;         /* the share of the distance to the plane a step covers, (0, 1] */
+  float max_shift;        /* the longest step, > 0 (+inf: no bound) */
+  float line_ratio;
+  int set_normal;         /* ef_map_smooth_apply: also write the last iteration's normal */
+  float shift_threshold;  /* ef_map_smooth_select: EF_SMOOTH_SHIFTED */
+} ef_smooth_params;
+typedef struct ef_smooth_result {
+  uint32_t participants, smoothed, sparse, degenerate, clamped, moved, listed;
+  float largest_shift;
+} ef_smooth_result;
+int ef_default_smooth_params(ef_ctx* ctx, ef_smooth_params* params);
+int ef_map_smooth(ef_ctx* ctx, const ef_smooth_params* params, const ef_map_selection* among_or_null, float* position3_or_null,
+                  float* normal3_or_null, float* curvature_or_null, float* shift_or_null, uint32_t* count_or_null, uint8_t* status_or_null,
+                  uint32_t max_rows, ef_smooth_result* result_or_null);
+int ef_map_smooth_dev(ef_ctx* ctx, const ef_smooth_params* params, const ef_map_selection* among_or_null, float* position3_dev_or_null,
+                      float* normal3_dev_or_null, float* curvature_dev_or_null, float* shift_dev_or_null, uint32_t* count_dev_or_null,
+                      uint8_t* status_dev_or_null, uint32_t max_rows, ef_smooth_result* result_dev_or_null);
+int ef_map_smooth_select(ef_ctx* ctx, const ef_smooth_params* params, const ef_map_selection* among_or_null, int what, uint32_t* rows,
+                         uint32_t max_rows, uint32_t* count, ef_smooth_result* result_or_null);
+int ef_map_smooth_select_dev(ef_ctx* ctx, const ef_smooth_params* params, const ef_map_selection* among_or_null, int what, uint32_t* rows_dev,
+                             uint32_t max_rows, uint32_t* count_dev, ef_smooth_result* result_dev_or_null);
+int ef_map_smooth_apply(ef_ctx* ctx, const ef_smooth_params* params, const ef_map_selection* among_or_null, ef_smooth_result* result);
 
 /* named internal images, copied to HOST (synchronises); for tests and for a front-end's drawing code */
 enum ef_image {
