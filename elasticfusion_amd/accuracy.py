@@ -13,6 +13,8 @@ A ground truth that is not in the map's world frame (another dataset's model, a 
 point-to-plane ICP against the map (register_to_map over ef_register_cloud; map_accuracy(align=True))."""
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 
 from . import api
@@ -203,6 +205,50 @@ def smoothed_map(ef: "api.ElasticFusion", **params) -> np.ndarray:
     if p.set_normal if p is not None else params.get("set_normal", 0):
         done = sm["status"] == api.SMOOTH_SMOOTHED
         out[done, 8:11] = sm["normal"][done]
+    return out
+
+
+def map_boundaries(ef: "api.ElasticFusion", max_loops: int | None = None, **params) -> list:
+    """where ef's map ends: the loops of its boundary surfels (the rim of the scanned surface and the rims of the holes in it), what a
+    next-view planner consumes.  A list of dicts, one per ACCEPTED loop (min_size / max_size among the keywords), LARGEST FIRST with ties by
+    label, at most max_loops of them:
+        label      the loop's smallest row
+        rows       its rows, ascending (uint32): what gatherSurfels and eraseRows take
+        size       their number
+        surfels    [size, 12] float32 as downloadMap() gives them
+        centroid   the mean position (float64 [3])
+        axes       [3, 3] float64: the principal axes of the positions as rows, longest first (the last is the normal of the loop's plane)
+        extent     float64 [3]: max - min of the positions along each axis (a round hole: two equal extents and a small third)
+    The map does not change and is not downloaded.  Which rows belong to an accepted loop is the device's verdict (boundarySelect with
+    BOUNDARY_LOOPS_ACCEPTED: ef_map_boundaries_select); the select lists carry no labels, so a second call brings the label word of every
+    row (ef_map_boundaries with every other array NULL: 4 bytes per row; the device work runs twice) and is looked at in the listed rows only; then one gatherSurfels
+    per loop (ef_map_gather), the moments in double on the host.  The keywords (params, among, ef_boundary_params fields) as boundaries
+    takes them."""
+    prm, among, pa = ef._boundaryArgs(params.pop("params", None), params.pop("among", None), params)
+    listed = ef.boundarySelect(prm, among, what=api.BOUNDARY_LOOPS_ACCEPTED)
+    n = ef.lastCount()
+    label = np.zeros(max(n, 1), np.uint32)
+    api._chk(api.lib().ef_map_boundaries(ef.h, C.byref(prm), pa, None, None, None, api._ptr(label), None, n, None), ef.h)
+    mine = label[listed]                                    # (ascending rows, so every loop's rows stay ascending below)
+    roots, size = np.unique(mine, return_counts=True)
+    keep = np.lexsort((roots, -size.astype(np.int64)))
+    roots, size = roots[keep], dict(zip(roots.tolist(), size.tolist()))
+    if max_loops is not None:
+        roots = roots[:max_loops]
+    order = np.argsort(mine, kind="stable")                 # one pass: the listed rows of every label, ascending within it
+    first = np.searchsorted(mine[order], roots)
+    listed = listed[order]
+    out = []
+    for r, a in zip(roots, first):
+        rows = listed[a:a + size[int(r)]]
+        S = ef.gatherSurfels(rows)
+        P = S[:, :3].astype(np.float64)
+        centroid = P.mean(0)
+        Q = P - centroid
+        w, v = np.linalg.eigh(Q.T @ Q)
+        axes = v[:, ::-1].T.copy()
+        proj = Q @ axes.T
+        out.append(dict(label=int(r), rows=rows, size=size[int(r)], surfels=S, centroid=centroid, axes=axes, extent=proj.max(0) - proj.min(0)))
     return out
 
 

@@ -11,6 +11,7 @@ There is NO fallback: if the shared library is missing or no GPU is present, eve
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import re
 
@@ -208,7 +209,20 @@ class ef_smooth_result(C.Structure):
                 ("listed", c_u32), ("largest_shift", c_f)]
 
 
+class ef_boundary_params(C.Structure):
+    _fields_ = [("radius", c_f), ("cell", c_f), ("min_conf", c_f), ("k", c_i), ("min_neighbors", c_i), ("normal_source", c_i), ("line_ratio", c_f),
+                ("max_gap", c_f), ("min_size", c_u32), ("max_size", c_u32)]
+
+
+class ef_boundary_result(C.Structure):
+    _fields_ = [("participants", c_u32), ("interior", c_u32), ("boundary", c_u32), ("sparse", c_u32), ("degenerate", c_u32), ("loops", c_u32),
+                ("accepted", c_u32), ("largest", c_u32), ("listed", c_u32), ("status", c_u32)]
+
+
 CARVE_MAX_VIEWS = 32   # EF_CARVE_MAX_VIEWS of include/ef_hip.h
+BOUNDARY_STORED, BOUNDARY_ESTIMATED = 0, 1          # EF_BOUNDARY_STORED / _ESTIMATED of include/ef_hip.h: normal_source of ef_boundary_params
+BOUNDARY_NONE, BOUNDARY_INTERIOR, BOUNDARY_BOUNDARY, BOUNDARY_SPARSE, BOUNDARY_DEGENERATE = 0, 1, 2, 3, 4   # EF_BOUNDARY_*: a row's status byte (the last four also `what`)
+BOUNDARY_LOOPS_ACCEPTED, BOUNDARY_LOOPS_REJECTED = 5, 6   # EF_BOUNDARY_LOOPS_*: `what` of ef_map_boundaries_select beside the four verdicts
 SMOOTH_UNIFORM, SMOOTH_COMPACT = 0, 1               # EF_SMOOTH_UNIFORM / _COMPACT of include/ef_hip.h: weighting of ef_smooth_params
 SMOOTH_NONE, SMOOTH_SMOOTHED, SMOOTH_SPARSE, SMOOTH_DEGENERATE = 0, 1, 2, 3   # EF_SMOOTH_*: a row's status byte (the last three also `what`)
 SMOOTH_CLAMPED, SMOOTH_SHIFTED = 4, 5               # EF_SMOOTH_CLAMPED / _SHIFTED: `what` of ef_map_smooth_select beside the three statuses
@@ -277,6 +291,25 @@ def register_update(sums, T=None):
     return out.reshape(4, 4), xi, rc == REG_DEGENERATE
 
 
+def boundary_gap(radians: float) -> float:
+    """ef_boundary_gap_from_angle (plain double on the host: needs neither a context nor a GPU): the max_gap of ef_boundary_params, in TURN
+    units, for an angle inside (0, 2 pi); exact at the quarter turns (pi / 2 -> 1, pi -> 2)"""
+    g = C.c_double(0.0)
+    _chk(lib().ef_boundary_gap_from_angle(float(radians), C.byref(g)))
+    return g.value
+
+
+def boundary_angle(gap: float) -> float:
+    """the inverse of boundary_gap: the angle in radians of a gap in TURN units inside (0, 4).  gap = n + sin b / (sin b + cos b) with n whole
+    quarter turns and b in [0, pi / 2), so tan b = f / (1 - f) for the fraction f"""
+    gap = float(gap)
+    if not 0.0 < gap < 4.0:
+        raise ValueError("a gap lies inside (0, 4)")
+    n = math.floor(gap)
+    f = gap - n
+    return n * (math.pi / 2) + math.atan2(f, 1.0 - f)
+
+
 DATATERM = np.dtype([("zero", np.int16, 2), ("one", np.int16, 2), ("diff", np.float32), ("valid", np.uint8),
                      ("pad", np.uint8, 3)])
 
@@ -302,7 +335,7 @@ def use_library(path: str | None = None):
 
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "ef_hip.h")
 _PROTOTYPE = re.compile(r"(?:^|[;}])\s*((?:const\s+)?\w+[\s*]+)(ef_\w+)\s*\(([^()]*)\)\s*;", re.M)
-_SCALARS = {"int": c_i, "unsigned": c_u32, "uint32_t": c_u32, "float": c_f, "size_t": C.c_size_t, "int64_t": C.c_int64}
+_SCALARS = {"int": c_i, "unsigned": c_u32, "uint32_t": c_u32, "float": c_f, "double": C.c_double, "size_t": C.c_size_t, "int64_t": C.c_int64}
 _RETURNS = {"int": c_i, "void": None, "float": c_f}
 _signatures = None
 
@@ -1896,6 +1929,73 @@ class ElasticFusion:
         res = ef_smooth_result()
         _chk(lib().ef_map_smooth_apply(self.h, C.byref(params), pa, C.byref(res)), self.h)
         return self._smoothResult(res)
+
+    # --- the map's open boundaries and holes (ef_map_boundaries / ef_map_boundaries_select) ---
+    def boundaryParams(self, **kw) -> ef_boundary_params:
+        """ef_default_boundary_params (radius 0.03, cell 0.03, min_conf -1, k 12, min_neighbors 5, BOUNDARY_STORED, line_ratio 1e-4, max_gap 1 = a
+        right angle in TURN units (boundary_gap / boundary_angle convert), min_size 1, max_size 0) with fields replaced by keyword"""
+        return self._params(ef_boundary_params, lib().ef_default_boundary_params, kw, "boundary")
+
+    def _boundaryArgs(self, params, among, kw):
+        if params is None:
+            params = self.boundaryParams(**kw)
+        else:
+            assert not kw, "give params or keywords, not both"
+        if isinstance(among, dict):
+            among = self.mapSelection(**among)
+        return params, among, (C.byref(among) if among is not None else None)
+
+    @staticmethod
+    def _boundaryResult(res: ef_boundary_result) -> dict:
+        return {k: int(getattr(res, k)) for k, _ in ef_boundary_result._fields_}
+
+    def boundaries(self, params: ef_boundary_params | None = None, among=None, result: bool = False, **kw):
+        """per row of downloadMap(): {"gap" float32 (the widest angular gap the neighbours leave seen along the normal, in TURN units: 1 = a right
+        angle), "count" uint32, "status" uint8 (api.BOUNDARY_*), "label" uint32, "size" uint32 (the boundary loop of a BOUNDARY row: its smallest
+        row and its number of rows; COMPONENT_NONE and 0 for every other row)}; the map does not change.  among: an ef_map_selection, a dict of
+        mapSelection keywords or None (every surfel participates); other keywords are ef_boundary_params fields.  result=True adds the dict of
+        ef_boundary_result"""
+        params, among, pa = self._boundaryArgs(params, among, kw)
+        n = self.lastCount()
+        m = max(n, 1)
+        out = dict(gap=np.zeros(m, np.float32), count=np.zeros(m, np.uint32), status=np.zeros(m, np.uint8), label=np.zeros(m, np.uint32),
+                   size=np.zeros(m, np.uint32))
+        res = ef_boundary_result()
+        _chk(lib().ef_map_boundaries(self.h, C.byref(params), pa, _ptr(out["gap"]), _ptr(out["count"]), _ptr(out["status"]), _ptr(out["label"]),
+                                     _ptr(out["size"]), n, C.byref(res)), self.h)
+        out = {k: v[:n] for k, v in out.items()}
+        return (out, self._boundaryResult(res)) if result else out
+
+    def boundariesDevice(self, params: ef_boundary_params, among, gap_dev, count_dev, status_dev, label_dev, size_dev, max_rows: int,
+                         result_dev=None):
+        """ef_map_boundaries_dev: raw device pointers (int, c_void_p or None) for max_rows floats, max_rows uint32, max_rows bytes, max_rows
+        uint32 twice and the result, enqueued on the context's stream"""
+        params, among, pa = self._boundaryArgs(params, among, {})
+        _chk(lib().ef_map_boundaries_dev(self.h, C.byref(params), pa, _dev(gap_dev), _dev(count_dev), _dev(status_dev), _dev(label_dev),
+                                         _dev(size_dev), int(max_rows), _dev(result_dev)), self.h)
+
+    def boundarySelect(self, params: ef_boundary_params | None = None, among=None, what: int = BOUNDARY_BOUNDARY, max_rows: int | None = None,
+                       count: bool = False, result: bool = False, **kw):
+        """the rows `what` names (BOUNDARY_INTERIOR / _BOUNDARY / _SPARSE / _DEGENERATE: the rows of that status; BOUNDARY_LOOPS_ACCEPTED /
+        _REJECTED: the rows of the boundary loops within / outside min_size .. max_size) in ascending order (uint32), at most max_rows of them
+        (None: all); the map does not change.  among and the keywords as boundaries takes them.  count=True adds the total, result=True the
+        dict of ef_boundary_result: rows[, total][, result]"""
+        params, among, pa = self._boundaryArgs(params, among, kw)
+        cap = self.lastCount() if max_rows is None else int(max_rows)
+        rows = np.zeros(max(cap, 1), np.uint32)
+        total = c_u32(0)
+        res = ef_boundary_result()
+        _chk(lib().ef_map_boundaries_select(self.h, C.byref(params), pa, int(what), _ptr(rows) if cap else None, cap, C.byref(total),
+                                            C.byref(res) if result else None), self.h)
+        out = (rows[:min(cap, total.value)].copy(),) + ((total.value,) if count else ()) + ((self._boundaryResult(res),) if result else ())
+        return out if len(out) > 1 else out[0]
+
+    def boundarySelectDevice(self, params: ef_boundary_params, among, what: int, rows_dev, max_rows: int, count_dev, result_dev=None):
+        """ef_map_boundaries_select_dev: raw device pointers (int, c_void_p or None for rows with max_rows 0 and for the result), enqueued on
+        the context's stream"""
+        params, among, pa = self._boundaryArgs(params, among, {})
+        _chk(lib().ef_map_boundaries_select_dev(self.h, C.byref(params), pa, int(what), _dev(rows_dev), int(max_rows), _dev(count_dev),
+                                                _dev(result_dev)), self.h)
 
     def setReferenceDownload(self, on=True):
         """downloadMap / savePly read what GlobalModel::downloadMap reads (the pre-clean buffer, quirk Q14) instead of model()"""

@@ -355,6 +355,13 @@ struct ef_ctx {
     size_t rows = 0;
     int slots = 0;
   } smooth;
+  // boundaries (ef_map_boundaries, ef_map_boundaries_select; kernels in ef_boundary.inc, the normals' join and the components' union-find):
+  // scratch of its own, sized by the map's rows, grown by the first call, freed with the context.  The normals' and the components' scratch are
+  // not touched
+  struct BoundaryState {
+    DevBuf scratch;                        // the two results | {normal, curvature}, {spacing, count}, {gap, count} per row | parent, label, members per row | chunk counts | chunk offsets | 4 words | selection / normal-status / node bytes | status bytes
+    size_t rows = 0;
+  } boundary;
   // fuse (ef_map_fuse; kernels in ef_fuse.inc) beside the insert's scratch, which its gate and append use: the election's keys (one per map row),
   // match_row and the outcome bytes (one each per record), and the two counts' words (FuseScratch / fuse_scratch in ef_host_insert.inc, beside
   // append_run, which carves it).  Grown by the first call, freed with the context
@@ -733,7 +740,7 @@ void ctx_free(ef_ctx* c) {
   for (KernelSampler* k : {&c->sample_step, &c->sample_all, &c->sample_splat}) k->release();
   drop_track_graphs(c);
   if (c->debug_stream) { (void)hipStreamSynchronize(c->debug_stream); (void)hipStreamDestroy(c->debug_stream); }
-  for (DevBuf* b : {&c->stage, &c->render.zbuf, &c->labels.index, &c->query.sorted, &c->query.rows, &c->query.cells, &c->reg.slabs, &c->sel.scratch, &c->ins.scratch, &c->thin.scratch, &c->carve.scratch, &c->outlier.scratch, &c->components.scratch, &c->planes.scratch, &c->normals.scratch, &c->regions.scratch, &c->smooth.scratch, &c->fuse.scratch})
+  for (DevBuf* b : {&c->stage, &c->render.zbuf, &c->labels.index, &c->query.sorted, &c->query.rows, &c->query.cells, &c->reg.slabs, &c->sel.scratch, &c->ins.scratch, &c->thin.scratch, &c->carve.scratch, &c->outlier.scratch, &c->components.scratch, &c->planes.scratch, &c->normals.scratch, &c->regions.scratch, &c->smooth.scratch, &c->boundary.scratch, &c->fuse.scratch})
     b->release();
   for (int k = 0; k < 2; ++k) {
     if (c->labels.tab[k]) (void)hipFree(c->labels.tab[k]);
@@ -1220,4 +1227,5 @@ int ef_set_depth_cutoff(ef_ctx* c, float v) { if (!c) return EF_EINVAL; c->cfg.d
 #include "ef_host_normals.inc"
 #include "ef_host_regions.inc"
 #include "ef_host_smooth.inc"
+#include "ef_host_boundary.inc"
 #include "ef_host_fuse.inc"

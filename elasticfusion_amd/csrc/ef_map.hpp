@@ -608,6 +608,40 @@ void smooth_split(const SmoothArgs& a, float* position3, float* normal3, float* 
 // the write-back: floats 0 .. 2 of every participant of a.q.map, and floats 8 .. 10 of the SMOOTHED rows with set_normal, in place
 void smooth_apply(const SmoothArgs& a, hipStream_t s);
 
+// ---- find the map's boundaries by the angle criterion (ef_boundary.inc; ef_map_boundaries of include/ef_hip.h) ----
+constexpr int BOUNDARY_STORED = 0, BOUNDARY_ESTIMATED = 1;                                    // EF_BOUNDARY_STORED / _ESTIMATED: normal_source
+constexpr unsigned BOUNDARY_NONE = 0, BOUNDARY_INTERIOR = 1, BOUNDARY_BOUNDARY = 2, BOUNDARY_SPARSE = 3, BOUNDARY_DEGENERATE = 4;   // EF_BOUNDARY_*: the status byte
+constexpr int BOUNDARY_LOOPS_ACCEPTED = 5, BOUNDARY_LOOPS_REJECTED = 6;                       // EF_BOUNDARY_LOOPS_*: `what` beside the four verdicts
+struct BoundaryResult {     // ef_boundary_result, field for field (ef_host_boundary.inc asserts the layout)
+  uint32_t participants, interior, boundary, sparse, degenerate, loops, accepted, largest, listed, status;
+};
+struct BoundaryArgs {
+  QueryArgs q;              // the index built at the call's cell and the live map; max_dist = radius, r2, min_conf (points, n, k, outputs unused)
+  unsigned n;               // rows of the map: the length of the per-row arrays below
+  int k;                    // neighbours used: 3 .. 16
+  unsigned min_neighbors;
+  int normal_source;        // BOUNDARY_*
+  float max_gap;
+  const uint8_t* part_in;   // STORED: one byte per row, non-zero = the row passes the selection; null: every row does
+  NormalArgs nrm;           // ESTIMATED: the estimate's arguments and outputs (normal_join, unchanged, enqueued before the join)
+  const float4* nest;       // ESTIMATED: nrm.est
+  const uint8_t* nstatus;   // ESTIMATED: nrm.status (NORMAL_NONE at every row that takes no part)
+  uint2* stat;              // per row {bits of gap, count}; every row is written by the join
+  uint8_t* status;          // per row BOUNDARY_*; every row is written by the join
+  ComponentArgs loops;      // the loops: component_hook / component_label, unchanged, with sel = node = the BOUNDARY byte of every row
+  BoundaryResult* res;      // the call's result on the device
+};
+// stat and status of every row: one lane per record of the index, in index order; nothing is launched for an empty map
+void boundary_join(const BoundaryArgs& a, hipStream_t s);
+// flags[row] = 1 for the rows whose status is `what`, 0 for every other row (every row is written)
+void boundary_flags(const BoundaryArgs& a, unsigned what, uint8_t* flags, hipStream_t s);
+// *a.res (zeroed by the caller) from the status bytes and *a.loops.res, listed = *total (0 with total null); then *copy_to = *res unless
+// copy_to is null
+void boundary_tally(const BoundaryArgs& a, const uint32_t* total, BoundaryResult* copy_to, hipStream_t s);
+// the optional per-row outputs of the rows r < min(rows, n) (each may be null)
+void boundary_split(const BoundaryArgs& a, float* gap, uint32_t* count, uint8_t* status, uint32_t* label, uint32_t* size, unsigned rows,
+                    hipStream_t s);
+
 // ---- fuse surfels into the map (ef_fuse.inc; ef_map_fuse of include/ef_hip.h) ----
 constexpr unsigned long long FUSE_KEY_EMPTY = 0xFFFFFFFFFFFFFFFFull;
 constexpr unsigned FUSE_SKIPPED = 0, FUSE_NOVEL = 1, FUSE_WEIGHTLESS = 2, FUSE_ABSORBED = 3, FUSE_FUSED = 4, FUSE_INSERTED = 5;   // EF_FUSE_*

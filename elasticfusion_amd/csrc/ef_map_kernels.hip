@@ -12,6 +12,7 @@
 #include "ef_zkey.hpp"
 #include "ef_unionfind.hpp"
 #include "ef_plane_fit.hpp"
+#include "ef_boundary_gap.hpp"
 
 using namespace ef;
 
@@ -1529,6 +1530,7 @@ void sample_graph(SurfelSoA map, const unsigned* count_dev, int stride, int max_
 #include "ef_normals.inc"
 #include "ef_regions.inc"
 #include "ef_smooth.inc"
+#include "ef_boundary.inc"
 #include "ef_fuse.inc"
 
 }  // namespace efm

@@ -1660,6 +1660,126 @@ int ef_map_smooth_select_dev(ef_ctx* ctx, const ef_smooth_params* params, const 
                              uint32_t max_rows, uint32_t* count_dev, ef_smooth_result* result_dev_or_null);
 int ef_map_smooth_apply(ef_ctx* ctx, const ef_smooth_params* params, const ef_map_selection* among_or_null, ef_smooth_result* result);
 
+/* ---- Find the map's boundaries (the boundary estimation by the angle criterion of point-cloud toolkits).  The tools above clean, thin, carve,
+ * label, segment, re-estimate and smooth a map; this says WHERE THE MAP ENDS: the rim of the scanned surface and the rims of the holes in it,
+ * which are the frontiers a reconstruction looks at next and the places a merged or carved map is still missing.  A surfel is on the boundary
+ * if, seen along its normal, its neighbours leave an angular gap wider than a threshold; the boundary surfels are strung into LOOPS.  Off until
+ * first used: no boundary call, nothing allocated, nothing run, and no frame kernel knows of it.  It changes no map and takes no part in a frame.
+ *
+ * "Row", the layout of a surfel, d2, ELIGIBLE, the PARTICIPANTS (among), the NEIGHBOURS of a participant with their (d2, row) order, count_s,
+ * c = min(count_s, k), the USED neighbours t_1 .. t_c and SPARSE (count_s < (uint32_t)min_neighbors) are exactly those of the section "Estimate
+ * normals, curvature and spacing".  All double arithmetic rounds once per operation, in the written order, without contraction; |v| is exact.
+ * From FRAME to GAP, csrc/ef_boundary_gap.hpp is the definition (its boundary_gap); what follows restates it.
+ *
+ * For a participant s that is not SPARSE, with the used neighbours in SLOTS 1 .. c in neighbour order:
+ *
+ * NORMAL m_s (three f32).
+ *   EF_BOUNDARY_STORED      floats 8 .. 10 of the row as they are (any length).
+ *   EF_BOUNDARY_ESTIMATED   the (float)n estimate of ef_map_normals with this call's radius, cell, min_conf, k, min_neighbors and line_ratio and
+ *                           the orientation EF_NORMALS_KEEP_SIDE.  A row whose estimate is SPARSE or DEGENERATE has that status here.
+ *
+ * FRAME, in double.  a = ((double)m.x, (double)m.y, (double)m.z);  nn = (a.x * a.x + a.y * a.y) + a.z * a.z.  The row is DEGENERATE unless nn is
+ * finite and > 0.  h = (a.x / sqrt(nn), a.y / sqrt(nn), a.z / sqrt(nn)) with the correctly rounded square root.  i0 = the index of the smallest
+ * |h_i|, chosen by "|h_1| < |h_0|", then "|h_2| < the smaller" (ties: the lowest index); e = the unit vector of axis i0.  e1 = e x h and
+ * e2 = h x e1, both by the one formula u x v = (u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x) with e's exact zeros and ones
+ * as doubles (so a component of e1 may be either zero).  No further normalisation: |e1| = |e2| = sqrt(1 - h_i0^2) >= sqrt(2 / 3) up to
+ * rounding, and the two axes scale every direction alike, which no angle sees.
+ *
+ * PROJECTION.  q_j = ((double)x_j - (double)x_s, (double)y_j - (double)y_s, (double)z_j - (double)z_s) from the f32 positions of rows t_j and s
+ * (the q_j of the normals' MOMENTS).  x_j = (q.x * e1.x + q.y * e1.y) + q.z * e1.z;  y_j = (q.x * e2.x + q.y * e2.y) + q.z * e2.z.  The used
+ * neighbour in slot j is a DIRECTION iff x_j and y_j are finite and |x_j| + |y_j| > 0.  m_s = the number of directions.  The row is DEGENERATE if
+ * m_s = 0 (every used neighbour lies along the normal, or on the row itself).
+ *
+ * TURN(j, i) for the directions in slots j != i: a monotone measure in [0, 4] of the counter-clockwise angle from j to i that needs divisions
+ * only (1 = 90 degrees, 2 = 180, 3 = 270).  d = x_j * x_i + y_j * y_i;  c = x_j * y_i - y_j * x_i;  s = |d| + |c|.
+ *   s is zero or not finite:   t = 0
+ *   else d >= 0 and c >= 0:    t = c / s
+ *   else d < 0:                t = 2 - c / s
+ *   else:                      t = 4 + c / s
+ * then, if t == 0 and i < j, t = 4.  c is EXACTLY antisymmetric in IEEE arithmetic (the products commute and a - b = -(b - a)) and d is
+ * symmetric; the definition relies on it: TURN(j, i) and TURN(i, j) see the same |c| and d, so two directions agree on whether they coincide,
+ * and of a group of coincident directions only the highest slot looks past the group (the others' gap is 0).
+ *
+ * GAP.  g_j starts at 4 and is replaced by every TURN(j, i) < g_j over the directions i != j, i ascending (4 with no other direction).  G_s
+ * starts at +0.0 and is replaced by every g_j > G_s over the directions j, j ascending.  gap_s = (float)G_s.  The row is BOUNDARY iff
+ * G_s > (double)max_gap; otherwise it is INTERIOR.  On a regular grid seen along its normal with the eight surrounding surfels as neighbours,
+ * an inner surfel has G = 0.5, one on a straight edge 2, a convex corner 3 and the concave corner of a hole 1.
+ *
+ * STATUS, one byte per row: EF_BOUNDARY_NONE (the row takes no part), EF_BOUNDARY_INTERIOR, EF_BOUNDARY_BOUNDARY, EF_BOUNDARY_SPARSE,
+ * EF_BOUNDARY_DEGENERATE.  SPARSE is decided first, then DEGENERATE, then the verdict.
+ * OUTPUTS by row: gap = gap_s, 0 unless INTERIOR or BOUNDARY; count = count_s, 0 for NONE; status; the loop's label and size.
+ *
+ * LOOPS are the connected components of the section "Connected components of the map", unchanged, of the graph whose NODES are the BOUNDARY
+ * rows that are nodes by that section's rule (so a BOUNDARY row with conf <= min_conf is in no loop) and whose radius is this call's radius.
+ * label = the SMALLEST ROW of the loop, size = the number of its nodes; min_size / max_size give ACCEPTED / REJECTED as there.  Every row that
+ * is in no loop has label = EF_COMPONENT_NONE and size = 0.
+ *
+ * max_gap is in TURN units, finite and in (0, 4).  The default 1.0 is a right angle, the toolkits' default: a definition, not a measurement.
+ * ef_boundary_gap_from_angle (host only, no context, no GPU) gives the TURN from the direction (1, 0) to (cos a, sin a) for an angle a in
+ * (0, 2 pi): with n = the whole quarter turns in a and b = a - n (pi / 2), *gap = n + sin b / (sin b + cos b) in double, which is exact at the
+ * quarter turns.  Nothing above depends on it or on libm.
+ *
+ * ef_boundary_result: participants, interior, boundary, sparse, degenerate (they add up to participants); loops = the number of loops,
+ * accepted = the ACCEPTED ones among them, largest = the greatest size (0 without loops); listed = the list's total (0 for ef_map_boundaries);
+ * status = the union-find's word of ef_component_result, always 0 (the host variants return EF_EHIP otherwise).
+ *
+ * ef_map_boundaries changes nothing.  It writes the five arrays for the rows r < min(max_rows, map count) (every array may be NULL; entries
+ * past that are left as they were) and the optional result.  ef_map_boundaries_select changes nothing.  what = EF_BOUNDARY_INTERIOR,
+ * EF_BOUNDARY_BOUNDARY, EF_BOUNDARY_SPARSE or EF_BOUNDARY_DEGENERATE (the rows of that status), EF_BOUNDARY_LOOPS_ACCEPTED or
+ * EF_BOUNDARY_LOOPS_REJECTED (the nodes of those loops).  The list has ef_map_select's conventions: the first min(max_rows, total) rows in
+ * ASCENDING order, *count = total however small max_rows is, rows may be NULL with max_rows 0, entries past min(max_rows, total) are left as
+ * they were; it is what ef_map_erase_rows and ef_map_gather take.  The _dev variants take DEVICE pointers for the arrays, count and result and
+ * only enqueue on the context's stream, except for what the selection needs (ID numbering, label alignment, the count after a call that can
+ * change the map) and except that they wait for the device once when the index has to be rebuilt or the scratch grows.
+ *
+ * cell is the cell of the queries' index, which is built at that cell where needed; a later query at another cell rebuilds it, as after
+ * ef_set_query_cell.  No result depends on it.  Defaults (ef_default_boundary_params): radius 0.03 m, cell 0.03 m, min_conf -1, k 12,
+ * min_neighbors 5 (the normals' defaults), EF_BOUNDARY_STORED, line_ratio 1e-4, max_gap 1, min_size 1, max_size 0 (no upper bound).
+ *
+ * Not provided: a write-back (nothing of the result is a field of a surfel); a remove call (ef_map_erase_rows takes the lists); the order of
+ * a loop's rows along the loop; a method of the C++ shim.
+ *
+ * EF_EINVAL, before any GPU work (the arguments are checked before the context, so with a NULL context ef_last_error(NULL) names what is wrong
+ * with them): a NULL context, params or count; radius or cell not finite and positive, or 1 / cell not finite; radius / cell above
+ * EF_QUERY_MAX_RATIO; NaN min_conf; k outside 3 .. 16; min_neighbors outside 2 .. k; normal_source outside its two values; NaN or negative
+ * line_ratio; max_gap not finite or not in (0, 4); what outside its six values; max_rows > 0 with NULL rows; with among given, everything
+ * ef_map_select refuses for a selection.  ef_boundary_gap_from_angle: a NULL gap, an angle that is not inside (0, 2 pi).
+ * EF_ESTATE: the context's stream is being captured; with among given, what ef_map_select answers with EF_ESTATE.  All calls work on contexts
+ * created with close_loops = 1. */
+#define EF_BOUNDARY_STORED         0     /* normal_source: the row's stored normal */
+#define EF_BOUNDARY_ESTIMATED      1     /* normal_source: ef_map_normals' estimate */
+#define EF_BOUNDARY_NONE           0     /* status: the row takes no part */
+#define EF_BOUNDARY_INTERIOR       1     /* status, and `what`: no gap wider than max_gap */
+#define EF_BOUNDARY_BOUNDARY       2     /* status, and `what`: a gap wider than max_gap */
+#define EF_BOUNDARY_SPARSE         3     /* status, and `what`: fewer than min_neighbors neighbours */
+#define EF_BOUNDARY_DEGENERATE     4     /* status, and `what`: no normal, or no neighbour off the normal */
+#define EF_BOUNDARY_LOOPS_ACCEPTED 5     /* `what`: the nodes of the loops within min_size .. max_size */
+#define EF_BOUNDARY_LOOPS_REJECTED 6     /* `what`: the nodes of the other loops */
+typedef struct ef_boundary_params {
+  float radius; float cell; float min_conf;
+  int k;                  /* neighbours used, 3 .. 16 */
+  int min_neighbors;      /* 2 .. k */
+  int normal_source;      /* EF_BOUNDARY_STORED / EF_BOUNDARY_ESTIMATED */
+  float line_ratio;       /* EF_BOUNDARY_ESTIMATED: the estimate's */
+  float max_gap;          /* TURN units, (0, 4) */
+  uint32_t min_size; uint32_t max_size;   /* of a loop; max_size 0: no upper bound */
+} ef_boundary_params;
+typedef struct ef_boundary_result {
+  uint32_t participants, interior, boundary, sparse, degenerate, loops, accepted, largest, listed, status;
+} ef_boundary_result;
+int ef_default_boundary_params(ef_ctx* ctx, ef_boundary_params* params);
+int ef_boundary_gap_from_angle(double radians, double* gap);
+int ef_map_boundaries(ef_ctx* ctx, const ef_boundary_params* params, const ef_map_selection* among_or_null, float* gap_or_null,
+                      uint32_t* count_or_null, uint8_t* status_or_null, uint32_t* label_or_null, uint32_t* size_or_null, uint32_t max_rows,
+                      ef_boundary_result* result_or_null);
+int ef_map_boundaries_dev(ef_ctx* ctx, const ef_boundary_params* params, const ef_map_selection* among_or_null, float* gap_dev_or_null,
+                          uint32_t* count_dev_or_null, uint8_t* status_dev_or_null, uint32_t* label_dev_or_null, uint32_t* size_dev_or_null,
+                          uint32_t max_rows, ef_boundary_result* result_dev_or_null);
+int ef_map_boundaries_select(ef_ctx* ctx, const ef_boundary_params* params, const ef_map_selection* among_or_null, int what, uint32_t* rows,
+                             uint32_t max_rows, uint32_t* count, ef_boundary_result* result_or_null);
+int ef_map_boundaries_select_dev(ef_ctx* ctx, const ef_boundary_params* params, const ef_map_selection* among_or_null, int what,
+                                 uint32_t* rows_dev, uint32_t max_rows, uint32_t* count_dev, ef_boundary_result* result_dev_or_null);
+
 /* named internal images, copied to HOST (synchronises); for tests and for a front-end's drawing code */
 enum ef_image {
   EF_IMG_DEPTH_FILTERED = 0,      /* u16  */
